@@ -10,10 +10,16 @@ Contract (driver): `python bench.py --gpus N --steps K --warmup W` prints ONE JS
     simulator on the device (k_simulate, seeded; --host-data: the numpy one of round 1).  N>1: one such chunk per GPU (weak scaling: chunks are independent,
     smcsmc/model.py:563-662), then one RCCL all-gather of the packed CountModel buffers summed
     in rank order (deterministic), the functional equivalent of smcsmc/model.py:1176-1184.
-  * value = (segments processed by all ranks over K steps) / (max over ranks of the timed wall time).
+  * value = (segments processed by all ranks over K steps) / (max over ranks of the timed wall time);
+    ms_per_step = that wall time / K.
 Extra objects: "roofline" for the dominant kernel (the row kernel of the extend role: k_sweep4 for the default workload, one launch per
-row on the filter stream; the ledger and count roles run beside it as k_sweep_blc4 on the counting stream) and "cpu_baseline" (the CPU
-oracle, kind "port": the reference binary cannot be built here) timed on a bounded sample on rank 0.
+row on the filter stream; the ledger and count roles run beside it as k_sweep_blc4 on the counting stream), from what the timed steps
+recorded.
+A plain run sets up, warms up, times the K steps and prints the line.  What needs work of its own runs only with --full: the
+device-to-device copy bandwidth (roofline.measured_copy_GBs), the timed lag calibration and all-in rate (config.lag_calibration_ms,
+config.all_in_segments_per_s) and "cpu_baseline" / "cpu_baseline_all_cores" (the CPU oracle, kind "port": the reference binary cannot
+be built here) timed on a bounded sample on rank 0 (--no-cpu, --no-cpu-all-cores leave those out).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64; see dump_outputs).
 """
 import argparse
 import json
@@ -98,6 +104,46 @@ def run_sweep(pf, segs):
     pf.init_prior(float(segs["start"][0]))
     pf.run()
     pf.finish()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, chunks, logl, counts, local_recomb):
+    """What the last timed step handed its caller, as float64 .npy files in out_dir: the log-likelihood and the CountModel
+    statistics summed over this rank's chunks, and chunk 0's per-row trace (position, ESS, running log-likelihood, resampling
+    flag), its 100-bp local recombination map (when recorded) and its final particles.  An array too large for the 64 MB budget
+    is replaced by the values at a fixed, seeded sample of its flat indices, written beside it as <name>_index.npy.
+    Two runs with the same arguments agree bit for bit except in the local recombination map, which the library sums with
+    floating-point atomics: there they agree to rounding (measured: at most 1e-15 of the map's largest value)."""
+    pf = chunks[0][0]
+    arrays = {"logl": np.array([logl])}
+    for k, v in counts.items():
+        arrays["counts_" + k] = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    for k, v in pf.trace().items():
+        arrays["trace_" + k] = v
+    if local_recomb:
+        for k, v in pf.local_recomb().items():
+            arrays["local_recomb_" + k] = v
+    for k, v in pf.particles().items():
+        arrays["particles_" + k] = v
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    cap = 1 << 22
+    while True:
+        out = {}
+        for k, v in arrays.items():
+            if v.size > cap:
+                idx = np.sort(np.random.default_rng(12345).choice(v.size, cap, replace=False))
+                out[k] = v.reshape(-1)[idx]
+                out[k + "_index"] = idx.astype(np.float64)
+            else:
+                out[k] = v
+        if sum(v.nbytes for v in out.values()) <= DUMP_BUDGET_BYTES:
+            break
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def cpu_baseline(args, model, segs):
@@ -215,8 +261,8 @@ def main():
                          "(samples split evenly, symmetric migration 4*N0*m = 1, all populations join at 0.5*4N0)")
     ap.add_argument("--cpu-segments", type=int, default=2000)
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-cpu-all-cores", action="store_true", help="skip the one-oracle-process-per-core baseline")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-cpu-all-cores", action="store_true", help="with --full: skip the one-oracle-process-per-core baseline")
     ap.add_argument("--timing-period", type=int, default=16, help="time every k-th segment's kernels with HIP events")
     ap.add_argument("--no-local-recomb", action="store_true",
                     help="do not record the 100-bp local recombination map (the binary always records it, smcsmc.cpp:376-383)")
@@ -240,6 +286,10 @@ def main():
                     "cost 2.4 %% in address translation: 3.27e4 -> 3.35e4 segments/s)")
     ap.add_argument("--chunk-threads", action="store_true",
                     help="with --chunks-per-gpu: one host thread and stream per chunk (rounds 1 and 2) instead of pf_run_many")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that need work of their own: copy bandwidth, timed lag calibration, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, at most 64 MB; see dump_outputs)")
     args = ap.parse_args()
 
     if args.log_cap < 0:
@@ -247,10 +297,11 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    import torch
+    torch = None                        # only the collectives (and --full's copy probe) need PyTorch
     dist = None
     cdev = "cuda"                       # where the tensors of the collectives live
     if world > 1:
+        import torch
         import torch.distributed as dist
         if args.rehearse_on_one_gpu:
             dist.init_process_group("gloo")
@@ -286,7 +337,7 @@ def main():
     def barrier():
         if dist is not None:
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
 
     many = C > 1 and not args.chunk_threads and args.pops == 1 and args.nsam <= 8 and not (args.debug & (8 | 16))
 
@@ -329,6 +380,8 @@ def main():
         for kk in counts:
             counts[kk] = counts[kk] + cc[kk]
     n_seg0 = len(segs["start"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, chunks, logl, counts, not args.no_local_recomb)
 
     if dist is not None:
         tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
@@ -415,36 +468,38 @@ def main():
                          "kernel_ms_estimate": {k: v[0] for k, v in kt.items()},
                          "kernel_launches": {k: v[1] for k, v in kt.items()}},
         }
-        try:
-            # achievable HBM bandwidth on this device, for scale: a 1 GiB device-to-device copy (bytes read + written)
-            src = torch.empty(1 << 27, dtype=torch.float64, device="cuda:%d" % dev).fill_(1.0)
-            dst = torch.empty_like(src)
-            torch.cuda.synchronize()
-            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            best = 1e30
-            for _ in range(4):
-                e0.record(); dst.copy_(src); e1.record(); torch.cuda.synchronize()
-                best = min(best, e0.elapsed_time(e1))
-            out["roofline"]["measured_copy_GBs"] = 2 * src.numel() * 8 / (best * 1e-3) / 1e9
-            del src, dst
-        except Exception:
-            pass
-        if world == 1:
-            # the lag calibration (calculate_median_survival_distances, smcsmc.cpp:169-263: prior ARGs until every
-            # epoch has 200 survival distances) is model-only work outside the sweep: timed separately, and an
-            # all-in rate with it included, as the reference pays it once per chunk and E-step
-            from smcsmc_amd import pf as _pf
-            tc0 = time.perf_counter()
-            _, cal_trees = _pf.median_survival(model, seed=1, device=dev)
-            cal_s = time.perf_counter() - tc0
-            sweep_s = dt_max / args.steps
-            out["config"]["lag_calibration_ms"] = 1e3 * cal_s
-            out["config"]["lag_calibration_trees"] = int(cal_trees)
-            out["config"]["all_in_segments_per_s"] = total_segments / (sweep_s + cal_s)
-        if not args.no_cpu and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args, model, segs)
-            if not args.no_cpu_all_cores:
-                out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, model, segs)
+        if args.full:
+            try:
+                import torch
+                # achievable HBM bandwidth on this device, for scale: a 1 GiB device-to-device copy (bytes read + written)
+                src = torch.empty(1 << 27, dtype=torch.float64, device="cuda:%d" % dev).fill_(1.0)
+                dst = torch.empty_like(src)
+                torch.cuda.synchronize()
+                e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+                best = 1e30
+                for _ in range(4):
+                    e0.record(); dst.copy_(src); e1.record(); torch.cuda.synchronize()
+                    best = min(best, e0.elapsed_time(e1))
+                out["roofline"]["measured_copy_GBs"] = 2 * src.numel() * 8 / (best * 1e-3) / 1e9
+                del src, dst
+            except Exception:
+                pass
+            if world == 1:
+                # the lag calibration (calculate_median_survival_distances, smcsmc.cpp:169-263: prior ARGs until every
+                # epoch has 200 survival distances) is model-only work outside the sweep: timed separately, and an
+                # all-in rate with it included, as the reference pays it once per chunk and E-step
+                from smcsmc_amd import pf as _pf
+                tc0 = time.perf_counter()
+                _, cal_trees = _pf.median_survival(model, seed=1, device=dev)
+                cal_s = time.perf_counter() - tc0
+                sweep_s = dt_max / args.steps
+                out["config"]["lag_calibration_ms"] = 1e3 * cal_s
+                out["config"]["lag_calibration_trees"] = int(cal_trees)
+                out["config"]["all_in_segments_per_s"] = total_segments / (sweep_s + cal_s)
+            if not args.no_cpu and world == 1:
+                out["cpu_baseline"] = cpu_baseline(args, model, segs)
+                if not args.no_cpu_all_cores:
+                    out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(args, model, segs)
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()
