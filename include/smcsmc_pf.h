@@ -39,7 +39,7 @@ extern "C" {
 typedef struct pf_model {
     int32_t n_epochs;            /* E  (Model::change_times_.size()) */
     int32_t n_pops;              /* P  (1..4; scrm -I) */
-    int32_t nsam;                /* haplotypes n, 2..16 */
+    int32_t nsam;                /* haplotypes n: 2..64 with one population (beyond 16 without -arg and -apf), 2..16 with several */
     int32_t flags;               /* bit0 -ancestral_aware, bit1 -dephase (pfparam.cpp:143-146) */
     double loci_length;          /* Model::loci_length() */
     double mutation_rate;        /* per bp per generation */
@@ -136,6 +136,9 @@ typedef struct pf_params {
                                   * (run_sweep_split).  A/B, same bits */
 
 #define PF_DEBUG_CU_MASK 1024     /* with PF_DEBUG_SPLIT_ROLES: the two streams on disjoint sets of compute units (experiment) */
+
+#define PF_DEBUG_FORCE_WIDE 2048  /* one population: run the wide kernels of nsam > 16 (64-lane workgroups, 64-bit masks, the records' extra
+                                   * descendant word, k_count<64>) whatever nsam is -- how that path is pinned against the oracle at n <= 16 */
 
 typedef struct pf_segments {
     int64_t n;
@@ -282,6 +285,9 @@ int pf_get_stats(pf_handle* h, int64_t* n_records, int64_t* state_bytes_per_part
  * reference's fallbacks (smcsmc.cpp:250-258).  lags = median * lag_fraction (count.cpp:261-265). */
 int pf_median_survival(const pf_model* model, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
                        int64_t* trees_used, int device);
+/* The same with pf_params.debug switches: PF_DEBUG_FORCE_WIDE runs the wide kernel (that of nsam > 16) at any nsam. */
+int pf_median_survival_opts(const pf_model* model, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
+                            int64_t* trees_used, int32_t debug, int device);
 
 /* Synthetic data next to the path (the reference shells out to scrm and converts, populationmodels.py:440-577): `nchunks`
  * independent chunks of the model's length under the same SMC' process the filter simulates (one population, or a
@@ -289,7 +295,10 @@ int pf_median_survival(const pf_model* model, uint64_t seed, int32_t min_events,
  * ascending continuous site positions pos[c*max_sites + k] and carrier masks (bit i = sample i carries the mutation).
  * n_sites[c] < 0 means more than max_sites sites were drawn (the first max_sites are returned). */
 int pf_simulate_sites(const pf_model* model, uint64_t seed, int32_t nchunks, int64_t max_sites, double* pos, uint32_t* masks,
-                      int64_t* n_sites, int device);
+                      int64_t* n_sites, int device);  /* nsam <= 16 */
+/* One population, 2..64 haplotypes: the same with 64-bit carrier masks (the wide kernel). */
+int pf_simulate_sites_wide(const pf_model* model, uint64_t seed, int32_t nchunks, int64_t max_sites, double* pos, uint64_t* masks,
+                        int64_t* n_sites, int device);
 
 /* unit-level entry points used by the parity tests (device implementations of the math and
  * of the canonical reductions; each runs one small kernel on the handle-independent default stream) */

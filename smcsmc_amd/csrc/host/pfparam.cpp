@@ -482,6 +482,13 @@ void PfParam::finalize() {
     }
     model.nsam = (int)nsam;
     model.parse(model_tokens);
+    // haplotypes: up to 64 with one population (the wide kernels); what those kernels do not cover is refused here, before any work
+    if (nsam > 64) throw std::invalid_argument("-nsam " + to_string(nsam) + ": at most 64 haplotypes are supported");
+    if (nsam > 16) {
+        if (model.npop > 1) throw Unsupported("-nsam " + to_string(nsam) + " with " + to_string(model.npop) + " populations (more than 16 haplotypes need one population)");
+        if (record_trees) throw Unsupported("-arg with more than 16 haplotypes");
+        if (apf_level > 0) throw Unsupported("-apf with more than 16 haplotypes");
+    }
     if (!guide_path.empty()) {
         read_guide_file(guide_path);
     }

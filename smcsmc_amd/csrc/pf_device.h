@@ -18,7 +18,8 @@
 #ifndef PF_BS
 #define PF_BS 256          // threads per workgroup of the per-particle kernels (4 wavefronts) = LDS stride of per-lane columns
 #endif
-#define PF_NMAX 16         // maximum number of haplotypes
+#define PF_NMAX 16         // maximum number of haplotypes of the 256-lane kernels and of structured models
+#define PF_NMAX_WIDE 64    // one population: the wide kernels (pf_wide.hip, 64-lane workgroups, 64-bit masks; children stay int8: 2n - 2 = 126)
 #define PF_INF (__longlong_as_double(0x7ff0000000000000LL))
 
 namespace pf {

@@ -29,311 +29,22 @@
 #include "pf_types.h"
 #include "pf_lane.h"
 #include "pf_tree_reg.h"
+#include "pf_lds_body.h"
 #include "pf_mp_host.h"
+#include "pf_wide_host.h"
 #include "pf_pipe.h"
 
 using namespace pf;
 
-// ------------------------------------------------------------------ k_init  (particleContainer.cpp:33-65)
+// ------------------------------------------------------------------ k_init, k_extend (bodies in pf_lds_body.h)
 __global__ __launch_bounds__(PF_BS) void k_init(KArgs A, double initial_position) {
     extern __shared__ double smem[];
-    Smem m = carve(smem, A.n, A.E);
-    load_model(A, m);
-    __syncthreads();
-    long long p = (long long)blockIdx.x * PF_BS + threadIdx.x;
-    if (p == 0) {
-        Ctrl* c = A.ctrl;
-        c->cur_pos = initial_position;
-        c->logl = 0; c->inv_T = 1; c->T = 1; c->flag = 0; c->cur = 0; c->gen = 0; c->n_resample = 0; c->lver = 0;
-        c->first_epoch = A.E; c->err = 0; c->delayed_opp = 0; c->delayed_count = 0; c->count_active = 0; c->end_seq = 0;
-        c->g_retain = 0; c->g_safe = 0; c->delay_peak = 0; c->n_delay_evict = 0; c->pending_fin = 0;
-        for (int k = 0; k < PF_RING; ++k) c->ri[k].g_retain = 0;      // (what Ctrl::g_safe is read from in the first rows of a sweep) c->nbx_used = A.nbx; c->gen_prev = 0; c->nres_prev = 0;
-        for (int e = 0; e < A.E; ++e) { c->counted_to[e] = 0; c->update_to[e] = 0; c->g_lo[e] = 0; c->g_hi[e] = 0; }
-        A.gen_x0[0] = 0.0;
-    }
-    if (p >= A.Np) return;
-    const int n = A.n;
-    Lane ln = make_lane(A, m, p);
-    ln.ebuf = -dlog(uni(ln));
-    unsigned widx = 0;
-    int root = 0;
-    double w0 = 1.0 / (double)A.Np;
-    // Forest::buildInitialTree(true): add the samples one by one; every coalescence is logged
-    // as a type-2 record at position 0 (record_all_event, particle.cpp:251-300)
-    for (int i = 1; i < n; ++i) {
-        int ni = i - 1;
-        double* rec = rec_ptr(A, p, widx);
-        rec[0] = 0.0; rec[1] = 0.0; rec[2] = 0.0;
-        for (int r = 0; r < n - 1; ++r) rec[5 + r] = r < ni ? LS(ln, r) : 0.0;
-        double tc = coalesce_up(ln, [&](int k) { return LS(ln, k); }, ni, i, 0.0);
-        if (ln.vbc) { w0 *= ln.upd_fac; ln.upd_fac = 1.0; }
-        rec[3] = tc;
-        ++widx;
-        int pr = -1, ps = 0;
-        int k = lineages_at(ln, ni, tc, -1, &pr, &ps);
-        bool above_root = (ni == 0) || (tc >= LS(ln, ni - 1));
-        int kk = above_root ? 1 : k;
-        double u = uni(ln);
-        int idx = min((int)(u * (double)kk), kk - 1);
-        unsigned dn = (2u << i) - 1u;                 // above the root: all samples added so far
-        if (above_root) {
-            insert_node(ln, ni, tc, i, -1, 0, root);
-        } else {
-            lineages_at(ln, ni, tc, idx, &pr, &ps);
-            if (A.rec_trees) dn = (1u << i) | lane_desc_mask(ln, LC(ln, pr, ps), m.t0 + threadIdx.x);
-            insert_node(ln, ni, tc, i, pr, ps, root);
-        }
-        rec[4] = __longlong_as_double((long long)make_meta(2, A.E - 1, A.E - 1, i, 0, A.rec_trees ? dn : 0u));
-        root = n + ni;
-    }
-    ln.Ltree = tree_length(ln, n);
-    if (A.g_K > 0) {
-        // with a guide the first draw uses the rate of the first segment and stops at its end
-        ln.rho = A.g_rho[0];
-        if (A.g_K > 1 && A.g_pos[1] < A.L) ln.L = A.g_pos[1];
-    }
-    double nb = sample_next_base(ln, 0.0);
-    const DState st = A.st0;
-    for (int r = 0; r < n - 1; ++r) {
-        st.S[(size_t)r * A.Np + p] = LS(ln, r);
-        st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
-        st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
-    }
-    st.w_post[p] = w0;
-    st.w_pilot[p] = w0;
-    st.next_base[p] = nb;
-    st.x_mark[p] = 0.0;
-    st.Ltree[p] = ln.Ltree;
-    st.mark_limit[p] = A.E - 1;
-    if (A.n_bias > 0 || A.g_K > 0) { st.total_delayed[p] = 1.0; st.dcount[p] = 0; }
-    if (A.g_K > 0) st.ridx[p] = 0;
-    if (st.lookahead) st.lookahead[p] = 1.0;
-    A.rng_ctr[p] = ln.ctr;
-    A.ebuf[p] = ln.ebuf;
-    A.widx[p] = widx;
-    A.gstart[p] = 0;   // generation 0 starts with an empty log (the init records belong to it)
+    init_lds_body(A, initial_position, smem);
 }
 
-// ------------------------------------------------------------------ k_extend
-// ParticleContainer::extend_ARGs + update_weight_at_site (particleContainer.cpp:98-135, 187-224)
-// with ForestState::extend_ARG (particle.cpp:743-918) per lane.
 __global__ __launch_bounds__(PF_BS) void k_extend(KArgs A, long long s) {
     extern __shared__ double smem[];
-    Smem m = carve(smem, A.n, A.E);
-    load_model(A, m);
-    __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
-    if (threadIdx.x < PF_BIAS_MAX + 2) {
-        sBH[threadIdx.x] = A.bias_H[threadIdx.x];
-        if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
-    }
-    __syncthreads();
-    const bool guided = A.g_K > 0;
-    const bool biased = A.n_bias > 0 || guided;          // a guide alone runs with one band of strength 1
-    bool has_pending = false;
-    const Ctrl* c = A.ctrl;
-    const int n = A.n;
-    const int cur = __builtin_amdgcn_readfirstlane(c->cur);
-    const long long p = (long long)blockIdx.x * PF_BS + threadIdx.x;
-    const bool active = p < A.Np;
-    const int lane = threadIdx.x & 63;
-    double w_post = 0.0, w_pilot = 0.0;
-    if (active) {
-        const DState st = state_slot(A, cur);
-        Lane ln = make_lane(A, m, p);
-        for (int r = 0; r < n - 1; ++r) {
-            LS(ln, r) = st.S[(size_t)r * A.Np + p];
-            LC(ln, r, 0) = st.C[(size_t)(2 * r) * A.Np + p];
-            LC(ln, r, 1) = st.C[(size_t)(2 * r + 1) * A.Np + p];
-        }
-        w_post = st.w_post[p];
-        w_pilot = st.w_pilot[p];
-        double next_base = st.next_base[p];
-        double x_mark = st.x_mark[p];
-        int mark_limit = st.mark_limit[p];
-        ln.Ltree = st.Ltree[p];
-        ln.ctr = A.rng_ctr[p];
-        ln.ebuf = A.ebuf[p];
-        unsigned widx = A.widx[p];
-        DStore ds;
-        d_bind(ds, A, st, p);
-        ds.count = 0; ds.total = 1.0;
-        if (biased) { ds.count = st.dcount[p]; ds.total = st.total_delayed[p]; }
-        int ridx = guided ? st.ridx[p] : 0;
-        double* tmp0 = m.t0 + threadIdx.x;
-        double* tmp1 = m.t1 + threadIdx.x;
-
-        const int8_t* data = A.seg_alleles + (size_t)s * n;
-        const double seg_end = A.seg_start[s] + A.seg_len[s];
-        const double extend_to = seg_end < A.L ? seg_end : A.L;
-        const int limit = A.seg_limit[s];
-        int missing = 0;
-        for (int i = 0; i < n; ++i) missing += data[i] == -1;
-        int leaf_status = 0;
-        if (missing == 0) leaf_status = 1;
-        if (missing == n) leaf_status = -1;
-
-        double updated_to = c->cur_pos;
-        double B;
-        if (leaf_status == -1) B = 0;
-        else if (leaf_status == 1) B = ln.Ltree;
-        else B = tracked_len_lane(ln, data, tmp0);
-
-        while (updated_to < extend_to) {
-            double new_to = extend_to < next_base ? extend_to : next_base;
-            double f = fastexp(-A.mu * B * (new_to - updated_to));
-            w_post *= f;
-            w_pilot *= f;
-            if (guided) {
-                // importance_weight_over_segment (particle.cpp:1138-1181): true over guide rate for the stretch
-                // without recombination
-                const double dist = new_to - updated_to;
-                const double target_rate = dist * A.rho * ln.Ltree;
-                const double sampled_rate = dist * A.g_rho[ridx] * ln.Ltree;
-                const double iws = fastexp(sampled_rate - target_rate);
-                w_post *= iws;
-                w_pilot *= iws;
-            }
-            updated_to = new_to;
-            if (guided && updated_to < extend_to && ridx + 1 < A.g_K && updated_to == A.g_pos[ridx + 1]) {
-                // reached a change of the guide rate: no genealogy change, new draw under the new rate
-                ridx += 1;
-                next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
-                continue;
-            }
-            if (updated_to < extend_to) {
-                // a recombination: log the stretch that ends here together with the event
-                double* rec = rec_ptr(A, p, widx);
-                rec[0] = x_mark;
-                rec[1] = updated_to;
-                for (int r = 0; r < n - 1; ++r) rec[5 + r] = LS(ln, r);
-                double h, tc, sp_removed;
-                bool changed;
-                unsigned desc = 0, desc_new = 0;
-                double iw = 1.0, rbiw = 1.0;
-                genealogy_update(ln, &h, &tc, &sp_removed, &changed, (A.lmap_opp || A.rec_trees) ? &desc : nullptr, tmp0,
-                                 biased ? sBH : nullptr, sBS, A.n_bias + 1, &iw,
-                                 guided ? A.g_leaf + (size_t)ridx * n : nullptr, guided ? A.rho / A.g_rho[ridx] : 1.0, &rbiw,
-                                 A.rec_trees ? &desc_new : nullptr);
-                if (ln.vbc) { w_post *= ln.upd_fac; w_pilot *= ln.upd_fac; ln.upd_fac = 1.0; }
-                rec[2] = h;
-                rec[3] = tc;
-                rec[4] = __longlong_as_double((long long)make_meta(0, mark_limit, limit, n, desc, desc_new));
-                ++widx;
-                if (leaf_status == 0) B = tracked_len_lane(ln, data, tmp0);
-                if (leaf_status == 1) B = ln.Ltree;
-                if (biased) {
-                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
-                    const int nbands = A.n_bias + 1;
-                    const double delay_height = (A.delay_type & 3) == 0 ? h : tc;
-                    int idx = 0;
-                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
-                    if (idx >= nbands) idx = nbands - 1;
-                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
-                    const double delay = A.app_delays[epoch_of(ln, delay_height)];
-                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
-                }
-                next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
-                ln.uqn = 0;                    // the update's unused uniforms are dropped
-                x_mark = updated_to;
-                mark_limit = limit;
-            }
-        }
-
-        if (biased) {
-            // apply the factors that fell due during this extension (particle.cpp:910-916)
-            for (;;) {
-                if (ds.count == 0) break;
-                double pm = ds.pos[0];
-                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
-                if (!(pm < extend_to)) break;
-                d_apply_earliest(ds, w_pilot);
-            }
-            st.dcount[p] = ds.count;
-            st.total_delayed[p] = ds.total;
-            if (guided) st.ridx[p] = ridx;
-            has_pending = ds.count > 0;
-        }
-        if (A.seg_state[s] == 0) {
-            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
-            const bool dephase = A.flags & 2;
-            const bool anc = A.flags & 1;
-            unsigned one_mask = 0, zero_mask = 0, het_pairs = 0;
-            int ncfg = 1;
-            for (int i = 0; i < n; ++i) {
-                if (data[i] == 1) one_mask |= 1u << i;
-                if (data[i] == 0) zero_mask |= 1u << i;
-            }
-            for (int i = 0; i + 1 < n; i += 2) {
-                bool het = (data[i] == 2) || (dephase && data[i] + data[i + 1] == 1);
-                if (het) {
-                    ncfg *= 2;
-                    het_pairs |= 1u << i;
-                    one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
-                    zero_mask |= 1u << i;          // hap[i] = 0
-                    one_mask |= 1u << (i + 1);     // hap[i+1] = 1
-                }
-            }
-            double norm = 1.0 / (double)ncfg;
-            double lik = 0;
-            for (;;) {
-                lik += site_lik_lane(ln, one_mask, zero_mask, anc, tmp0, tmp1);
-                if (ncfg == 1) break;
-                bool more = false;                  // next_haplotype (pc.cpp:163-181)
-                for (int i = 0; i + 1 < n; i += 2) {
-                    if (!((het_pairs >> i) & 1)) continue;
-                    if ((zero_mask >> i) & 1) {     // phase 0 -> phase 1
-                        zero_mask &= ~(1u << i); one_mask |= 1u << i;
-                        one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
-                        more = true;
-                        break;
-                    }
-                    one_mask &= ~(1u << i); zero_mask |= 1u << i;
-                    zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
-                }
-                if (!more) break;
-            }
-            lik *= norm;
-            w_post *= lik;
-            w_pilot *= lik;
-        }
-
-        for (int r = 0; r < n - 1; ++r) {
-            st.S[(size_t)r * A.Np + p] = LS(ln, r);
-            st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
-            st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
-        }
-        st.w_post[p] = w_post;
-        st.w_pilot[p] = w_pilot;
-        st.next_base[p] = next_base;
-        st.x_mark[p] = x_mark;
-        st.mark_limit[p] = mark_limit;
-        st.Ltree[p] = ln.Ltree;
-        A.rng_ctr[p] = ln.ctr;
-        A.ebuf[p] = ln.ebuf;
-        A.widx[p] = widx;
-        if (A.rec_trees && widx >= A.cap) A.ctrl->err = ERR_LOG_OVERFLOW;
-        for (int r = 0; r < n - 1; ++r) A.snap_S[A.sp][(size_t)r * A.Np + p] = LS(ln, r);
-        A.snap_w[A.sp][p] = w_post; A.snap_xm[A.sp][p] = x_mark; A.snap_ml[A.sp][p] = mark_limit; A.snap_widx[A.sp][p] = widx;
-    }
-    // per-wavefront canonical partials (level 1 of the radix-64 reduction / scan)
-    double sp = wave_tree_sum(w_post);
-    double sq = wave_tree_sum(w_pilot * w_pilot);
-    double sc = wave_hs_scan(w_pilot, lane);
-    double scp = wave_hs_scan(w_post, lane);
-    double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
-    long long chunk = p >> 6;
-    if (active) { A.scan1[p] = sc; A.scanp2[A.sp][p] = scp; A.scan1m[p] = scm; }
-    if (lane == 63 && chunk < (A.Np + 63) / 64) {
-        A.chunk_post[chunk] = sp;
-        A.chunk_sq[chunk] = sq;
-        A.chunk_pil[chunk] = sc;
-        A.chunk_pp[chunk] = scp;
-        A.chunk_mx1[chunk] = scm;
-    }
-    if (biased) {
-        unsigned long long pend = __ballot(has_pending);
-        if (lane == 0 && chunk < (A.Np + 63) / 64) A.chunk_dpend[chunk] = __popcll(pend);
-    }
+    extend_lds_body(A, s, smem);
 }
 
 // A wave-uniform value moved into vector registers on purpose.  The extend kernels are short of scalar registers (the
@@ -1341,10 +1052,12 @@ __device__ __forceinline__ void lmap_opportunity(const LMap& L, double x_lo, dou
     }
 }
 // a recombination event at event_base, height h, below which the samples `desc` hang (count.cpp:590-612)
-__device__ __forceinline__ void lmap_event(const LMap& L, int n, double event_base, double h, unsigned desc, double weight) {
+// (M: the 32-bit masks of the records' meta word, or the 64-bit word of a record written by the wide kernels)
+template <class M>
+__device__ __forceinline__ void lmap_event(const LMap& L, int n, double event_base, double h, M desc, double weight) {
     long long idx = (long long)(event_base / 100.0);
     if (idx < 0 || idx >= L.nbins) return;
-    const int nd = __popc(desc);
+    const int nd = sizeof(M) == 8 ? __popcll((unsigned long long)desc) : __popc((unsigned)desc);
     const long long k = idx - L.b0;
     if (k >= 0 && k < L.ncnt) {
         // the workgroup's own rows of the counts: a row's events all fall into the few intervals of its epoch's window, and every one
@@ -1352,13 +1065,13 @@ __device__ __forceinline__ void lmap_event(const LMap& L, int n, double event_ba
         typedef __attribute__((address_space(3))) double lds_double;
         lds_double* base = (lds_double*)L.lds + L.nlds + k;
         for (int i = 0; i < n; ++i)
-            if ((desc >> i) & 1u) __hip_atomic_fetch_add(base + (size_t)i * L.ncnt, weight / nd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if ((desc >> i) & (M)1) __hip_atomic_fetch_add(base + (size_t)i * L.ncnt, weight / nd, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_add(base + (size_t)n * L.ncnt, weight * h, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __hip_atomic_fetch_add(base + (size_t)(n + 1) * L.ncnt, weight * dlog(h + 1.0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         return;
     }
     for (int i = 0; i < n; ++i)
-        if ((desc >> i) & 1u) atomicAdd(&L.gcnt[(size_t)i * L.nbins + idx], weight / nd);
+        if ((desc >> i) & (M)1) atomicAdd(&L.gcnt[(size_t)i * L.nbins + idx], weight / nd);
     atomicAdd(&L.gcnt[(size_t)n * L.nbins + idx], weight * h);
     atomicAdd(&L.gcnt[(size_t)(n + 1) * L.nbins + idx], weight * dlog(h + 1.0));
 }
@@ -1383,7 +1096,8 @@ __device__ __forceinline__ void stretch_contrib(AccT<P>& acc, const KA& A, const
 // record's head [x0, x1, h, t_c | piece reference, meta], S the heights of the tree in force over [x0, x1].
 template <int NI, int P, class KA>
 __device__ __forceinline__ void record_contrib_one(AccT<P>& acc, const KA& A, const Win& W, const LMap& L, double w, long long a,
-                                                   double f0, double f1, double f2, double f3, double f4, const double (&S)[NI]) {
+                                                   double f0, double f1, double f2, double f3, double f4, const double (&S)[NI],
+                                                   unsigned long long desc_wide = 0) {
     using AC = AccT<P>;
     const int n = A.n;
     double x0 = f0, x1 = f1;
@@ -1447,7 +1161,8 @@ __device__ __forceinline__ void record_contrib_one(AccT<P>& acc, const KA& A, co
             bool inwin_r = (W.a_e <= x1) && ((x1 < W.b_e) || W.end_seq);
             if (inwin_r && (W.rf & REC_RECOMB) && W.e <= lim_event && W.T0 <= h && h < W.T1) {
                 acc.v[AC::RC] += w;
-                if (L.gopp) lmap_event(L, n, x1, h, (unsigned)((meta >> 32) & 0xffff), w);
+                if constexpr (NI >= PF_NMAX) { if (L.gopp) lmap_event(L, n, x1, h, desc_wide, w); }     // the wide kernels' records
+                else { if (L.gopp) lmap_event(L, n, x1, h, (unsigned)((meta >> 32) & 0xffff), w); }
             }
         }
     }
@@ -1481,7 +1196,9 @@ __device__ __forceinline__ void records_contrib(AccT<P>& acc, const KA& A, const
 #pragma unroll
         for (int r = 0; r < NI; ++r) S[r] = r < n - 1 ? rec[5 + r] : 0.0;
         if (f0 >= W.b_e && !W.end_seq) break;           // this record and all behind it start past the window
-        record_contrib_one<NI, P>(acc, A, W, L, w, a, f0, f1, f2, f3, f4, S);
+        unsigned long long dw = 0;
+        if constexpr (NI >= PF_NMAX) if (L.gopp) dw = (unsigned long long)__double_as_longlong(rec[4 + n]);
+        record_contrib_one<NI, P>(acc, A, W, L, w, a, f0, f1, f2, f3, f4, S, dw);
     }
 }
 
@@ -1752,7 +1469,9 @@ __device__ __forceinline__ void count_body(const KA& A, const CountSrc& Q, int e
                 double S[NI];
 #pragma unroll
                 for (int q = 0; q < NI; ++q) S[q] = q < n - 1 ? rec[5 + q] : 0.0;
-                record_contrib_one<NI, P>(acc, A, W, L, w_r, a_r, f0, f1, f2, f3, f4, S);
+                unsigned long long dw = 0;
+                if constexpr (NI >= PF_NMAX) if (L.gopp) dw = (unsigned long long)__double_as_longlong(rec[4 + n]);
+                record_contrib_one<NI, P>(acc, A, W, L, w_r, a_r, f0, f1, f2, f3, f4, S, dw);
             }
             __syncthreads();                                 // (the next trip, or the next tile's staging, writes the arrays again)
         }
@@ -2594,110 +2313,12 @@ __global__ __launch_bounds__(PF_BS) void k_partials(KArgs A) {
     }
 }
 
-// ------------------------------------------------------------------ k_calibrate
-// calculate_median_survival_distances (smcsmc.cpp:169-263): one prior ARG per lane; evolve it along
-// the sequence without data until every internal node of the initial tree has been removed (or
-// 0.6 L is reached) and report, per original node, its epoch and the position where it disappeared.
-// NM = 0: the recombination loop runs on the LDS tree (any nsam); NM = 4 / 8: on the register tree of the extend
-// kernels (nsam <= NM), same arithmetic operation for operation, about half the instructions.  The epoch tables of
-// the register path sit behind the LDS-tree block.
+// ------------------------------------------------------------------ k_calibrate (body in pf_lds_body.h)
 template <int NM>
 __global__ __launch_bounds__(PF_BS) void k_calibrate(KArgs A, unsigned long long seed, long long rep0, long long nrep,
                                                      int* out_epoch, double* out_dist) {
     extern __shared__ double smem[];
-    Smem m = carve(smem, A.n, A.E);
-    load_model(A, m);
-    double* sT = (double*)((char*)smem + smem_bytes(A.n, A.E));
-    double* sH = sT + PF_EPAD;
-    double* sI = sH + PF_EPAD;
-    if (NM > 0)
-        for (int e = threadIdx.x; e < PF_EPAD; e += blockDim.x) {
-            sT[e] = e < A.E ? A.T[e] : PF_INF;
-            sH[e] = e < A.E ? A.Hc[e] : PF_INF;
-            if (e < A.E) sI[e] = A.inv2N[e];
-        }
-    __syncthreads();
-    long long r = (long long)blockIdx.x * PF_BS + threadIdx.x;
-    if (r >= nrep) return;
-    const int n = A.n;
-    Lane ln = make_lane(A, m, rep0 + r);
-    ln.seed = seed;
-    ln.stream = 2;
-    ln.ebuf = -dlog(uni(ln));
-    int root = 0;
-    for (int i = 1; i < n; ++i) {
-        int ni = i - 1;
-        double tc = coalesce_up(ln, [&](int k) { return LS(ln, k); }, ni, i, 0.0);
-        int pr = -1, ps = 0;
-        int k = lineages_at(ln, ni, tc, -1, &pr, &ps);
-        bool above_root = (ni == 0) || (tc >= LS(ln, ni - 1));
-        int kk = above_root ? 1 : k;
-        double u = uni(ln);
-        int idx = min((int)(u * (double)kk), kk - 1);
-        if (above_root) insert_node(ln, ni, tc, i, -1, 0, root);
-        else { lineages_at(ln, ni, tc, idx, &pr, &ps); insert_node(ln, ni, tc, i, pr, ps, root); }
-        root = n + ni;
-    }
-    ln.Ltree = tree_length(ln, n);
-    // original internal-node heights live in the t0 scratch column of this lane
-    double* orig = m.t0 + threadIdx.x;
-    int alive = n - 1;
-    for (int j = 0; j < n - 1; ++j) {
-        orig[j * PF_BS] = LS(ln, j);
-        out_epoch[r * (n - 1) + j] = epoch_of(ln, LS(ln, j));
-        out_dist[r * (n - 1) + j] = -1.0;
-    }
-    unsigned alive_mask = (1u << (n - 1)) - 1u;
-    double next = sample_next_base(ln, 0.0);
-    const double stop = A.L * 0.6;
-    if constexpr (NM > 0) {
-        RTree<NM> t;
-#pragma unroll
-        for (int rr = 0; rr < RTree<NM>::NI; ++rr) {
-            t.S[rr] = 0.0; t.C0[rr] = 0; t.C1[rr] = 0;
-            if (rr < n - 1) { t.S[rr] = LS(ln, rr); t.C0[rr] = LC(ln, rr, 0); t.C1[rr] = LC(ln, rr, 1); }
-        }
-        RCtx cx;
-        cx.T = sT; cx.I = sI; cx.H = sH; cx.E = A.E; cx.n = n; cx.L = A.L; cx.mu = A.mu; cx.rho = A.rho;
-        cx.seed = seed; cx.slot = ln.slot; cx.stream = 2; cx.ctr = ln.ctr; cx.ebuf = ln.ebuf; cx.Ltree = ln.Ltree;
-        cx.nb = 1; cx.bH = nullptr; cx.bS = nullptr; cx.last_iw = 1.0; cx.want_desc = false; cx.want_desc_new = false; cx.last_desc = 0; cx.last_desc_new = 0;
-        cx.vbc = nullptr; cx.upd_fac = 1.0;
-        cx.gK = 0; cx.gpos = nullptr; cx.grho = nullptr; cx.gleaf = nullptr; cx.last_rbiw = 1.0; cx.ridx = 0; cx.g_rp = 0; cx.g_sb = 0;
-        while (alive > 0 && next < stop) {
-            const double x = next;
-            double h, tc, sp;
-            bool changed;
-            r_genealogy_update<NM, false>(cx, t, &h, &tc, &sp, &changed);
-            if (changed) {
-                for (int j = 0; j < n - 1; ++j)
-                    if (((alive_mask >> j) & 1u) && orig[j * PF_BS] == sp) {
-                        out_dist[r * (n - 1) + j] = x;
-                        alive_mask &= ~(1u << j);
-                        --alive;
-                        break;
-                    }
-            }
-            next = r_sample_next_base<true>(cx, x);
-        }
-        return;
-    }
-    while (alive > 0 && next < stop) {
-        double x = next;
-        double h, tc, sp;
-        bool changed;
-        genealogy_update(ln, &h, &tc, &sp, &changed);
-        if (changed) {
-            for (int j = 0; j < n - 1; ++j)
-                if (((alive_mask >> j) & 1u) && orig[j * PF_BS] == sp) {
-                    out_dist[r * (n - 1) + j] = x;
-                    alive_mask &= ~(1u << j);
-                    --alive;
-                    break;
-                }
-        }
-        next = sample_next_base(ln, x);
-        ln.uqn = 0;
-    }
+    calibrate_lds_body<NM>(A, seed, rep0, nrep, out_epoch, out_dist, smem);
 }
 
 // ------------------------------------------------------------------ k_lookahead
@@ -2927,74 +2548,11 @@ __global__ void k_test_uniform(unsigned long long seed, unsigned slot, unsigned 
     if (i < n) o[i] = philox_uniform(seed, slot, stream, first + (unsigned long long)i);
 }
 
-// ------------------------------------------------------------------ k_simulate: synthetic data on the device
-// The `.seg` producer next to the path (the reference shells out to scrm and converts its
-// output, populationmodels.py:440-577).  One lane = one independent chromosome chunk: a prior tree, then along the
-// sequence the same SMC' transition the filter simulates (genealogy_update), and between recombinations mutations
-// dropped as a Poisson process of rate mu * tree length, each on a branch drawn in proportion to its length
-// (sample_point) -- the carriers are the samples below it.  Output per chunk: site positions (continuous, ascending)
-// and carrier masks; the host rounds them to bases and writes rows.  Its own Philox stream (3).
+// ------------------------------------------------------------------ k_simulate (body in pf_lds_body.h)
 __global__ __launch_bounds__(PF_BS) void k_simulate(KArgs A, unsigned long long seed, int nchunks, long long max_sites,
                                                     double* pos_out, unsigned* mask_out, long long* n_out) {
     extern __shared__ double smem[];
-    Smem m = carve(smem, A.n, A.E);
-    load_model(A, m);
-    __syncthreads();
-    const long long r = (long long)blockIdx.x * PF_BS + threadIdx.x;
-    if (r >= nchunks) return;
-    const int n = A.n;
-    Lane ln = make_lane(A, m, r);
-    ln.seed = seed;
-    ln.stream = 3;
-    ln.ebuf = -dlog(uni(ln));
-    int root = 0;
-    for (int i = 1; i < n; ++i) {            // Forest::buildInitialTree: the leaves join one at a time (as k_calibrate)
-        int ni = i - 1;
-        double tc = coalesce_up(ln, [&](int k) { return LS(ln, k); }, ni, i, 0.0);
-        int pr = -1, ps = 0;
-        int k = lineages_at(ln, ni, tc, -1, &pr, &ps);
-        bool above_root = (ni == 0) || (tc >= LS(ln, ni - 1));
-        int kk = above_root ? 1 : k;
-        double u = uni(ln);
-        int idx = min((int)(u * (double)kk), kk - 1);
-        if (above_root) insert_node(ln, ni, tc, i, -1, 0, root);
-        else { lineages_at(ln, ni, tc, idx, &pr, &ps); insert_node(ln, ni, tc, i, pr, ps, root); }
-        root = n + ni;
-    }
-    ln.Ltree = tree_length(ln, n);
-    double* tmp = m.t0 + threadIdx.x;        // per-lane LDS column for the descendant masks
-    double* pos = pos_out + (size_t)r * max_sites;
-    unsigned* msk = mask_out + (size_t)r * max_sites;
-    long long ns = 0;
-    double x = 0.0;
-    double next_rec = sample_next_base(ln, 0.0);
-    double next_mut = x + (-dlog(uni(ln))) / (A.mu * ln.Ltree);
-    bool overflow = false;
-    while (x < A.L) {
-        if (next_mut < next_rec && next_mut < A.L) {
-            // a mutation on the current tree: a uniform point of the tree picks the branch
-            int rp = 0, sb = 0;
-            double h;
-            ln.uqn = 0;
-            sample_point(ln, &rp, &sb, &h);
-            const unsigned carriers = lane_desc_mask(ln, LC(ln, rp, sb), tmp);
-            if (ns < max_sites) { pos[ns] = next_mut; msk[ns] = carriers; }
-            else overflow = true;
-            ++ns;
-            x = next_mut;
-            next_mut = x + (-dlog(uni(ln))) / (A.mu * ln.Ltree);
-            continue;
-        }
-        x = next_rec;
-        if (!(x < A.L)) break;
-        double h, tc, sp;
-        bool changed;
-        genealogy_update(ln, &h, &tc, &sp, &changed);
-        ln.uqn = 0;                           // what is left of the update's uniforms is not reused
-        next_rec = sample_next_base(ln, x);
-        next_mut = x + (-dlog(uni(ln))) / (A.mu * ln.Ltree);     // memoryless: redrawn under the new tree length
-    }
-    n_out[r] = overflow ? -ns : ns;
+    simulate_lds_body(A, seed, nchunks, max_sites, pos_out, mask_out, n_out, smem);
 }
 
 // ------------------------------------------------------------------ host side
@@ -3033,6 +2591,7 @@ struct pf_handle {
     bool fin_pending = false;     // k_count partials not yet folded into the totals
     Windows step_windows;         // windows of the step being processed
     bool force_lds = false;       // pf_params.debug & PF_DEBUG_FORCE_LDS: use the LDS-tree kernel for every n (testing)
+    bool wide = false;            // one population on the wide kernels of pf_wide.hip: nsam > PF_NMAX, or PF_DEBUG_FORCE_WIDE (testing)
     bool no_fuse = false;         // PF_DEBUG_NO_FUSE: always run k_resample as its own kernel (testing)
     bool no_count = false;        // PF_DEBUG_NO_COUNT: no lagged counting, no ledger upkeep (profiling)
     bool two_launch_rows = false; // PF_DEBUG_TWO_LAUNCH: the round-1 row pipeline (k_row + k_decide_ledger) instead of k_pipe
@@ -3222,7 +2781,11 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     if (ndev <= 0) return fail("pf_create: no HIP device available (there is no CPU fallback)");
     if (device < 0 || device >= ndev) return fail("pf_create: device index out of range");
     if (m->n_pops < 1 || m->n_pops > PF_PMAX) return fail("pf_create: n_pops must be in 1..4");
-    if (m->nsam < 2 || m->nsam > PF_NMAX) return fail("pf_create: nsam must be in 2..16");
+    if (m->nsam < 2 || m->nsam > PF_NMAX_WIDE) return fail("pf_create: nsam must be in 2..64");
+    const bool wide = m->n_pops == 1 && (m->nsam > PF_NMAX || (p->debug & PF_DEBUG_FORCE_WIDE));
+    if (m->nsam > PF_NMAX && m->n_pops > 1) return fail("pf_create: more than 16 haplotypes need one population (structured models take nsam <= 16)");
+    if ((p->debug & PF_DEBUG_FORCE_WIDE) && m->n_pops > 1) return fail("pf_create: PF_DEBUG_FORCE_WIDE applies to one population only");
+    if (wide && (p->flags & 2)) return fail("pf_create: tree recording (-arg) needs nsam <= 16 (its descendant masks are 32 bits wide)");
     if (m->n_epochs < 1 || m->n_epochs > PF_EMAX) return fail("pf_create: n_epochs must be in 1..64");
     if (p->np < 1 || p->np > 262144) return fail("pf_create: np must be in 1..262144");
     if (m->n_bias_heights < 0 || m->n_bias_heights > PF_BIAS_MAX) return fail("pf_create: at most 8 bias heights are supported");
@@ -3265,10 +2828,11 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     const long long Np = p->np;
     const int P = m->n_pops;
     h->E = E; h->n = n; h->Np = Np; h->P = P;
+    h->wide = wide;
     h->nblocks = (int)((Np + PF_BS - 1) / PF_BS);
     const int mcap = p->mig_cap > 0 ? p->mig_cap : PF_MMAX;
     if (mcap > 4096) { delete h; return fail("pf_create: mig_cap out of range"); }
-    h->smem = P > 1 ? pf_mp_smem_bytes(n, E, P, mcap) : smem_bytes(n, E);
+    h->smem = P > 1 ? pf_mp_smem_bytes(n, E, P, mcap) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
     h->max_trace_events = std::max(0, p->max_trace_events);
     if (p->flags & 2) {
         // -arg: the parent table of every resampling is kept (it is the ancestry the tree dump walks back through)
@@ -3373,7 +2937,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
         hipStreamSynchronize(h->stream);
         A.app_delays = dad;
     }
-    h->pipe = P == 1 && n <= 8 && Np <= 131072;      // beyond that the decision tables outgrow the default dynamic LDS
+    h->pipe = P == 1 && n <= 8 && Np <= 131072 && !wide;      // beyond that the decision tables outgrow the default dynamic LDS
     // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_mp)
     h->pipe_mp = P > 1 && n <= 8 && Np <= 131072 && !(p->flags & 2) && !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE));
     A.blk_gran = h->pipe_mp ? 4 : 1;
@@ -3438,7 +3002,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     rc |= dalloc(h, &A.widx, Np);
     A.cap = (unsigned)log_cap;
     A.rec_trees = (p->flags & 2) ? 1 : 0;
-    A.RS = 5 + (n - 1);
+    A.RS = 5 + (n - 1) + (wide ? 1 : 0);          // the wide kernels' records: the cut branch's samples in a 64-bit word behind the heights
     A.Gcap = (int)gen_cap;
     rc |= dalloc(h, &A.log, (size_t)Np * A.cap * A.RS);
     if (P > 1) {
@@ -3520,7 +3084,11 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     rc |= dalloc(h, &A.ev_parents, (size_t)std::max(1, h->max_trace_events) * Np);
     rc |= dalloc(h, &A.ctrl, 1);
     if (rc) { pf_destroy(h); return nullptr; }
-    if (P == 1 && h->smem > 64 * 1024) {
+    if (wide && pf_wide_prepare(h->smem)) {
+        pf_destroy(h);
+        return fail("pf_create: the local-tree state does not fit the LDS of one workgroup");
+    }
+    if (P == 1 && !wide && h->smem > 64 * 1024) {
         hipFuncSetAttribute((const void*)k_extend, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem);
         hipFuncSetAttribute((const void*)k_init, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem);
     }
@@ -3556,7 +3124,15 @@ pf_handle* pf_create(const pf_model* m, const pf_params* p, int device) {
         g_err = "pf_create: gen_cap must be at least 20 when the extend role runs ahead of the counts (structured models, PF_DEBUG_SPLIT_ROLES)";
         return nullptr;
     }
-    return create_impl(m, p, device, p->log_cap > 0 ? p->log_cap : (trees ? 131072 : 16384),
+    // (more than 16 haplotypes: a record is 8 (n + 5) bytes, 552 at n = 64; the default ring then holds as many bytes per particle as
+    // the 16 384 records of n = 16 do, rounded down to a power of two: 8192 records up to n = 35, 4096 up to n = 64)
+    long long log_def = trees ? 131072 : 16384;
+    if (!trees && m->nsam > PF_NMAX) {
+        const long long fit = 16384LL * (5 + PF_NMAX - 1) / (5 + m->nsam);
+        log_def = 1;
+        while (log_def * 2 <= fit) log_def *= 2;
+    }
+    return create_impl(m, p, device, p->log_cap > 0 ? p->log_cap : log_def,
                        p->gen_cap > 0 ? p->gen_cap : (trees ? 131072 : 8192));
 }
 
@@ -3652,6 +3228,8 @@ int pf_init_prior(pf_handle* h, double initial_position) {
     HIPCHK(hipSetDevice(h->device));
     if (h->P > 1)
         pf_mp_launch_init(h->A, initial_position, h->smem, h->stream);
+    else if (h->wide)
+        pf_wide_launch_init(h->A, initial_position, h->smem, h->stream);
     else
         hipLaunchKernelGGL(k_init, dim3(h->nblocks), dim3(PF_BS), h->smem, h->stream, h->A, initial_position);
     if (check_launch("k_init")) return -1;
@@ -3725,7 +3303,7 @@ static Windows no_windows(pf_handle* h) {
 
 // the register-tree kernels can complete the previous row while loading the particle (fused k_resample)
 static bool extend_can_fuse(const pf_handle* h) {
-    return h->P == 1 && h->n <= 8 && !h->force_lds && !h->no_fuse && h->A.apf == 0;
+    return h->P == 1 && h->n <= 8 && !h->force_lds && !h->wide && !h->no_fuse && h->A.apf == 0;
 }
 
 static int launch_extend(pf_handle* h, long long s, int fuse = 0) {
@@ -3736,6 +3314,8 @@ static int launch_extend(pf_handle* h, long long s, int fuse = 0) {
         const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
         if (h->P > 1)
             pf_mp_launch_extend(h->A, s, h->smem, h->stream, h->force_lds, fuse);
+        else if (h->wide)
+            pf_wide_launch_extend(h->A, s, h->smem, h->stream);
         else if (h->n <= 4 && biased && !h->force_lds)
         {
             if (h->A.rec_trees) hipLaunchKernelGGL((k_extend_reg<4, true, true>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
@@ -3797,7 +3377,9 @@ static int launch_count(pf_handle* h, long long s, const Windows& W) {
         const dim3 grid(h->nblocks, h->E - first), blk(PF_BS);
 #define PF_LAUNCH_COUNT(NMV, PV) hipLaunchKernelGGL((k_count<NMV, PV>), grid, blk, 0, h->cstream, h->A, first, W)
         const int P = h->P;
-        if (P == 1) {
+        if (P == 1 && h->wide) {
+            PF_LAUNCH_COUNT(PF_NMAX_WIDE, 1);                  // the wide records (descendants in their own word)
+        } else if (P == 1) {
             if (h->n <= 4) PF_LAUNCH_COUNT(4, 1);
             else if (h->n <= 8) PF_LAUNCH_COUNT(8, 1);
             else PF_LAUNCH_COUNT(PF_NMAX, 1);
@@ -5071,6 +4653,7 @@ int pf_load_lookahead(pf_handle* h, const pf_lookahead* la) {
     if (la->level < 0 || la->level > 4) { g_err = "-apf must be in 0..4"; return -1; }
     if (la->n != h->n_segs) { g_err = "pf_load_lookahead: one look-ahead record per segment expected"; return -1; }
     if (la->level == 0) { h->A.apf = 0; return 0; }
+    if (h->wide) { g_err = "-apf (the auxiliary particle filter) needs nsam <= 16"; return -1; }
     const long long S = la->n;
     const int n = h->n, D = la->max_doubletons, Q = la->n_quantiles;
     KArgs& A = h->A;
@@ -5176,13 +4759,16 @@ int pf_terminal_branch_quantiles(const pf_model* m, uint64_t seed, int64_t n_tre
 // then the same median / fallback rules are applied (smcsmc.cpp:235-262).
 #define PF_CAL_BATCH 16384
 
-int pf_median_survival(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
-                       int64_t* trees_used, int device) {
+static int median_survival_impl(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
+                                int64_t* trees_used, int32_t debug, int device) {
     if (test_setup(device)) return -1;
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX) {
-        g_err = "pf_median_survival: unsupported model";
+    if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > (m->n_pops == 1 ? PF_NMAX_WIDE : PF_NMAX) || m->n_epochs < 1 ||
+        m->n_epochs > PF_EMAX) {
+        g_err = "pf_median_survival: unsupported model (nsam 2..64 with one population, 2..16 with several)";
         return -1;
     }
+    // one population beyond 16 haplotypes (or PF_DEBUG_FORCE_WIDE): the wide kernel, same trees and walk
+    const bool wide = m->n_pops == 1 && (m->nsam > PF_NMAX || (debug & PF_DEBUG_FORCE_WIDE));
     const int E = m->n_epochs, n = m->nsam, P = m->n_pops;
     KArgs A;
     memset(&A, 0, sizeof(A));
@@ -5218,10 +4804,11 @@ int pf_median_survival(const pf_model* m, uint64_t seed, int32_t min_events, int
     std::vector<int> hep(PF_CAL_GROUP * per_batch);
     std::vector<double> hdist(PF_CAL_GROUP * per_batch);
     long long trees = 0;
-    const size_t smem = P > 1 ? pf_mp_smem_bytes(n, E, P, PF_MMAX) : smem_bytes(n, E);
+    const size_t smem = P > 1 ? pf_mp_smem_bytes(n, E, P, PF_MMAX) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
     if (P > 1 && pf_mp_prepare(smem, PF_MMAX)) { g_err = "pf_median_survival: the local-tree state does not fit the LDS"; return -1; }
+    if (wide && pf_wide_prepare(smem)) { g_err = "pf_median_survival: the local-tree state does not fit the LDS"; return -1; }
     const size_t smem_cal = smem + (size_t)(2 * PF_EPAD + E) * 8;          // + the padded epoch tables of the register path
-    if (P == 1 && smem_cal > 64 * 1024) {
+    if (P == 1 && !wide && smem_cal > 64 * 1024) {
         hipFuncSetAttribute((const void*)k_calibrate<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_cal);
         hipFuncSetAttribute((const void*)k_calibrate<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_cal);
         hipFuncSetAttribute((const void*)k_calibrate<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_cal);
@@ -5236,6 +4823,8 @@ int pf_median_survival(const pf_model* m, uint64_t seed, int32_t min_events, int
         const long long nrep = (long long)PF_CAL_GROUP * PF_CAL_BATCH;
         if (P > 1)
             pf_mp_launch_calibrate(A, (unsigned long long)seed, trees, nrep, dep, ddist, derr, smem, 0);
+        else if (wide)
+            pf_wide_launch_calibrate(A, (unsigned long long)seed, trees, nrep, dep, ddist, smem, 0);
         else
         {
             const dim3 grid((unsigned)(nrep / PF_BS)), blk(PF_BS);
@@ -5275,6 +4864,59 @@ int pf_median_survival(const pf_model* m, uint64_t seed, int32_t min_events, int
     }
     for (int e = 0; e < E; ++e)
         if (median_out[e] < 0) median_out[e] = e > 0 ? median_out[e - 1] : earliest;
+    return 0;
+}
+
+int pf_median_survival(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
+                       int64_t* trees_used, int device) {
+    return median_survival_impl(m, seed, min_events, max_trees, median_out, trees_used, 0, device);
+}
+
+int pf_median_survival_opts(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
+                            int64_t* trees_used, int32_t debug, int device) {
+    return median_survival_impl(m, seed, min_events, max_trees, median_out, trees_used, debug, device);
+}
+
+// One population, 2..64 haplotypes, 64-bit carrier masks: the wide kernel (k_simulate_wide, the body of k_simulate).
+int pf_simulate_sites_wide(const pf_model* m, uint64_t seed, int32_t nchunks, int64_t max_sites, double* pos, uint64_t* masks,
+                        int64_t* n_sites, int device) {
+    if (test_setup(device)) return -1;
+    if (m->n_pops != 1 || m->nsam < 2 || m->nsam > PF_NMAX_WIDE || m->n_epochs < 1 || m->n_epochs > PF_EMAX || nchunks < 1 || max_sites < 1) {
+        g_err = "pf_simulate_sites_wide: one population, 2..64 haplotypes, 1..64 epochs";
+        return -1;
+    }
+    const int E = m->n_epochs, n = m->nsam;
+    KArgs A;
+    memset(&A, 0, sizeof(A));
+    A.E = E; A.n = n; A.P = 1; A.L = m->loci_length; A.mu = m->mutation_rate; A.rho = m->recombination_rate; A.mcap = PF_MMAX;
+    struct Bufs { std::vector<void*> v; ~Bufs() { for (void* q : v) hipFree(q); } } bufs;
+    auto dmalloc = [&](auto** q, size_t bytes) { void* r = nullptr; hipError_t e = hipMalloc(&r, bytes); if (e == hipSuccess) bufs.v.push_back(r); *q = (std::remove_reference_t<decltype(**q)>*)r; return e; };
+    double *dT, *dI, *dHc, *dpos; int* dRF; unsigned long long* dmask; long long* dn;
+    HIPCHK(dmalloc(&dT, E * 8)); HIPCHK(dmalloc(&dI, E * 8)); HIPCHK(dmalloc(&dHc, E * 8)); HIPCHK(dmalloc(&dRF, E * 4));
+    HIPCHK(dmalloc(&dpos, (size_t)nchunks * max_sites * 8)); HIPCHK(dmalloc(&dmask, (size_t)nchunks * max_sites * 8));
+    HIPCHK(dmalloc(&dn, (size_t)nchunks * 8));
+    std::vector<double> inv2N(E);
+    for (int e = 0; e < E; ++e) inv2N[e] = 1.0 / (2.0 * m->pop_sizes[e]);
+    std::vector<int> rf(E, 3);
+    const std::vector<double> Hc = cumulative_intensity(m->change_times, inv2N, E);
+    HIPCHK(hipMemcpy(dT, m->change_times, E * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dI, inv2N.data(), E * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dHc, Hc.data(), E * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dRF, rf.data(), E * 4, hipMemcpyHostToDevice));
+    A.T = dT; A.inv2N = dI; A.Hc = dHc; A.recflags = dRF;
+    const size_t smem = pf_wide_smem_bytes(n, E);
+    if (pf_wide_prepare(smem)) { g_err = "pf_simulate_sites_wide: the local-tree state does not fit the LDS"; return -1; }
+    pf_wide_launch_simulate(A, (unsigned long long)seed, (int)nchunks, (long long)max_sites, dpos, dmask, dn, smem, 0);
+    if (check_launch("k_simulate_wide")) return -1;
+    if (hipDeviceSynchronize() != hipSuccess) { g_err = "k_simulate_wide failed"; return -1; }
+    std::vector<long long> hn(nchunks);
+    HIPCHK(hipMemcpy(hn.data(), dn, (size_t)nchunks * 8, hipMemcpyDeviceToHost));
+    for (int c = 0; c < nchunks; ++c) {
+        n_sites[c] = hn[c];
+        const long long k = std::min<long long>(std::llabs(hn[c]), max_sites);
+        HIPCHK(hipMemcpy(pos + (size_t)c * max_sites, dpos + (size_t)c * max_sites, (size_t)k * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(masks + (size_t)c * max_sites, dmask + (size_t)c * max_sites, (size_t)k * 8, hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

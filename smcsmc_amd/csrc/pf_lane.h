@@ -7,6 +7,16 @@
 
 using namespace pf;
 
+// Descendant and allele masks of the LDS-tree body: bit i = sample i.  32 bits for the kernels of nsam <= PF_NMAX; the
+// wide translation unit (pf_wide.hip, nsam <= PF_NMAX_WIDE) defines PF_WIDE 1 and PF_MASK_T as a 64-bit type.
+#ifndef PF_WIDE
+#define PF_WIDE 0
+#endif
+#ifndef PF_MASK_T
+#define PF_MASK_T unsigned
+#endif
+typedef PF_MASK_T pf_mask_t;
+
 // delayed importance weights: adjustWeightsWithDelay / applyDelayedAdjustment (particle.hpp:185-209)
 struct DStore {
     double* pos; double* fac; double* delta; int* k;   // column of this particle: element i at [i * Np]
@@ -292,14 +302,14 @@ __device__ __forceinline__ double sample_next_base_guided(Lane& ln, double x, in
 }
 
 // get_descendants (descendants.hpp:22-33): samples below node `id`; `tmp` = per-lane LDS scratch of n-1 doubles
-__device__ __forceinline__ unsigned lane_desc_mask(const Lane& ln, int id, double* tmp) {
+__device__ __forceinline__ pf_mask_t lane_desc_mask(const Lane& ln, int id, double* tmp) {
     const int n = ln.n;
-    if (id < n) return 1u << id;
-    unsigned res = 0;
+    if (id < n) return (pf_mask_t)1 << id;
+    pf_mask_t res = 0;
     for (int r = 0; r <= id - n; ++r) {
         int c0 = LC(ln, r, 0), c1 = LC(ln, r, 1);
-        unsigned m0 = c0 < n ? (1u << c0) : (unsigned)__double_as_longlong(tmp[(c0 - n) * PF_BS]);
-        unsigned m1 = c1 < n ? (1u << c1) : (unsigned)__double_as_longlong(tmp[(c1 - n) * PF_BS]);
+        pf_mask_t m0 = c0 < n ? ((pf_mask_t)1 << c0) : (pf_mask_t)__double_as_longlong(tmp[(c0 - n) * PF_BS]);
+        pf_mask_t m1 = c1 < n ? ((pf_mask_t)1 << c1) : (pf_mask_t)__double_as_longlong(tmp[(c1 - n) * PF_BS]);
         res = m0 | m1;
         tmp[r * PF_BS] = __longlong_as_double((long long)res);
     }
@@ -309,10 +319,10 @@ __device__ __forceinline__ unsigned lane_desc_mask(const Lane& ln, int id, doubl
 // With bH != nullptr the cut point is drawn with height-band weights (focused sampling) and *iw_out receives the
 // importance weight of the draw.
 __device__ __forceinline__ void genealogy_update(Lane& ln, double* h_out, double* tc_out, double* sp_out, bool* changed_out,
-                                                 unsigned* desc_out = nullptr, double* tmp = nullptr,
+                                                 pf_mask_t* desc_out = nullptr, double* tmp = nullptr,
                                                  const double* bH = nullptr, const double* bS = nullptr, int nb = 1,
                                                  double* iw_out = nullptr, const double* lr = nullptr, double rho_ratio = 1.0,
-                                                 double* rbiw_out = nullptr, unsigned* desc_new_out = nullptr) {
+                                                 double* rbiw_out = nullptr, pf_mask_t* desc_new_out = nullptr) {
     const int n = ln.n;
     int rp = 0, sb = 0;
     double h;
@@ -358,9 +368,9 @@ __device__ __forceinline__ void genealogy_update(Lane& ln, double* h_out, double
     }
     if (desc_new_out && desc_out) {
         // samples below the node this update creates (masks taken on the pruned tree, before the insertion)
-        unsigned dn = *desc_out;
+        pf_mask_t dn = *desc_out;
         if (idx < nslots) dn |= lane_desc_mask(ln, LC(ln, pr_ins, ps_ins), tmp);
-        else if (has_root && idx == nslots) dn = (1u << n) - 1u;
+        else if (has_root && idx == nslots) dn = ((pf_mask_t)2 << (n - 1)) - 1u;     // all n samples (no shift by the mask width at n = 64)
         *desc_new_out = dn;
     }
     insert_node(ln, ni, h_ins, b_id, pr_ins, ps_ins, troot);
@@ -387,7 +397,7 @@ __device__ __forceinline__ double tracked_len_lane(const Lane& ln, const int8_t*
     return total;
 }
 
-__device__ __forceinline__ double site_lik_lane(const Lane& ln, unsigned one_mask, unsigned zero_mask, bool anc,
+__device__ __forceinline__ double site_lik_lane(const Lane& ln, pf_mask_t one_mask, pf_mask_t zero_mask, bool anc,
                                                 double* t0, double* t1) {
     // particle.cpp:625-680.  Leaf i: L0 = (state==1 ? 0 : 1), L1 = (state==0 ? 0 : 1);
     // one_mask bit i <=> state==1, zero_mask bit i <=> state==0 (missing: neither).

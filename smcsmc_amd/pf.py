@@ -54,6 +54,8 @@ class _Params(C.Structure):
 
 
 DEBUG_FORCE_LDS, DEBUG_NO_FUSE, DEBUG_NO_COUNT, DEBUG_TWO_LAUNCH = 1, 2, 4, 8
+DEBUG_FORCE_WIDE = 2048      # one population: the wide kernels of nsam > 16 at any nsam (pins that path against the oracle)
+NSAM_MAX, NSAM_MAX_WIDE = 16, 64     # haplotypes: several populations / one population
 
 
 class _Segments(C.Structure):
@@ -96,7 +98,7 @@ EXPORTS = [
     "pf_update_segment", "pf_count", "pf_resample", "pf_run", "pf_run_many", "pf_can_run_many", "pf_finish", "pf_sync",
     "pf_num_segments_done", "pf_logl", "pf_get_counts", "pf_get_trace", "pf_get_resample_events",
     "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
-    "pf_median_survival", "pf_test_math", "pf_test_div", "pf_test_uniform", "pf_test_reduce", "pf_test_systematic",
+    "pf_simulate_sites_wide", "pf_median_survival", "pf_median_survival_opts", "pf_test_math", "pf_test_div", "pf_test_uniform", "pf_test_reduce", "pf_test_systematic",
 ]
 
 
@@ -151,6 +153,9 @@ def load_library(path=None):
     L.pf_get_wg_trace.argtypes = [vp, vp, C.c_int64, vp]
     L.pf_get_wg_trace.restype = C.c_int64
     L.pf_median_survival.argtypes = [C.POINTER(_Model), C.c_uint64, C.c_int32, C.c_int64, vp, vp, C.c_int]
+    L.pf_median_survival_opts.argtypes = [C.POINTER(_Model), C.c_uint64, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int]
+    L.pf_simulate_sites_wide.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.pf_simulate_sites_wide.restype = C.c_int
     L.pf_test_math.argtypes = [vp, C.c_int64, vp, vp, vp, C.c_int]
     L.pf_test_div.argtypes = [vp, vp, C.c_int64, vp, C.c_int]
     L.pf_test_uniform.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int64, vp, C.c_int]
@@ -488,21 +493,23 @@ def _pack_model(m):
     return pm.model, pm
 
 
-def median_survival(model, seed=1, min_events=200, max_trees=1000000, device=0):
-    """calculate_median_survival_distances (smcsmc.cpp:169-263) on the device; returns (medians[E], trees)."""
+def median_survival(model, seed=1, min_events=200, max_trees=1000000, device=0, debug=0):
+    """calculate_median_survival_distances (smcsmc.cpp:169-263) on the device; returns (medians[E], trees).
+    `debug`: pf_params.debug switches (DEBUG_FORCE_WIDE: the kernel of nsam > 16 at any nsam)."""
     L = load_library()
     mod, keep = _pack_model(model)
     out = np.zeros(mod.n_epochs)
     trees = C.c_int64()
-    if L.pf_median_survival(C.byref(mod), int(seed), int(min_events), int(max_trees), out.ctypes.data,
-                            C.byref(trees), int(device)) < 0:
+    if L.pf_median_survival_opts(C.byref(mod), int(seed), int(min_events), int(max_trees), out.ctypes.data,
+                                 C.byref(trees), int(debug), int(device)) < 0:
         raise PfError(_err(L))
     return out, trees.value
 
 
 def simulate_sites(model, seed=1, nchunks=1, max_sites=None, device=0):
     """Synthetic data on the device (k_simulate): for each of `nchunks` independent chunks of the model's length the
-    ascending site positions and carrier masks.  Returns a list of (positions, masks)."""
+    ascending site positions and carrier masks.  Returns a list of (positions, masks): uint32 masks up to 16 haplotypes,
+    uint64 beyond (one population, the wide kernel)."""
     L = load_library()
     L.pf_simulate_sites.argtypes = [C.c_void_p, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.pf_simulate_sites.restype = C.c_int
@@ -516,10 +523,12 @@ def simulate_sites(model, seed=1, nchunks=1, max_sites=None, device=0):
         deep = float(np.max(np.asarray(model["change_times"], float))) if int(model.get("n_pops", 1)) > 1 else 0.0
         max_sites = int(2.0 * (4.0 * nmax * harmonic + n * deep) * model["mutation_rate"] * model["loci_length"]) + 4096
     pos = np.zeros((nchunks, max_sites))
-    masks = np.zeros((nchunks, max_sites), np.uint32)
+    wide = n > NSAM_MAX
+    masks = np.zeros((nchunks, max_sites), np.uint64 if wide else np.uint32)
     cnt = np.zeros(nchunks, np.int64)
-    if L.pf_simulate_sites(C.byref(mod), int(seed), int(nchunks), int(max_sites), pos.ctypes.data, masks.ctypes.data,
-                           cnt.ctypes.data, int(device)) < 0:
+    sim = L.pf_simulate_sites_wide if wide else L.pf_simulate_sites
+    if sim(C.byref(mod), int(seed), int(nchunks), int(max_sites), pos.ctypes.data, masks.ctypes.data,
+           cnt.ctypes.data, int(device)) < 0:
         raise PfError(_err(L))
     if (cnt < 0).any():
         raise PfError("pf_simulate_sites: more than max_sites sites in a chunk")
@@ -541,9 +550,9 @@ def terminal_branch_quantiles(model, seed=1, n_trees=1000000, quantiles=None, de
     return out, mean.value
 
 
-def calibrated_lags(model, lag_fraction=2.0, seed=1, device=0):
+def calibrated_lags(model, lag_fraction=2.0, seed=1, device=0, debug=0):
     """CountModel::reset_lag (count.cpp:261-265) with the calibrated survival distances."""
-    med, _ = median_survival(model, seed=seed, device=device)
+    med, _ = median_survival(model, seed=seed, device=device, debug=debug)
     return med * lag_fraction
 
 

@@ -218,7 +218,7 @@ def simulate_seg_device(n, L, mu, rho, change_times, pop_sizes, seed=1, nchunks=
         model.update({k: structure[k] for k in ("n_pops", "pop_sizes", "mig_rates", "single_mig", "sample_pops") if k in structure})
     out = []
     for pos, masks in pf.simulate_sites(model, seed=seed, nchunks=nchunks, device=device):
-        pats = ((masks[:, None] >> np.arange(n)[None, :]) & 1).astype(np.int8)
+        pats = ((masks[:, None] >> np.arange(n, dtype=masks.dtype)[None, :]) & 1).astype(np.int8)     # (uint64 masks beyond 16 samples)
         out.append(sites_to_seg(pos, pats, n, L, missing))
     return out
 
