@@ -3,10 +3,11 @@ import ctypes as C, os, sys, numpy as np, argparse
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from smcsmc_amd import pf, build as _build
-pf.LIB_PATH = _build.build_stamps_lib()          # the -DPF_STAMPS build of the library (smcsmc_amd/build.py)
-import bench
 ap = argparse.ArgumentParser(); ap.add_argument("--rows", type=int, default=6000); ap.add_argument("--debug", type=int, default=0)
+ap.add_argument("--lib", default=None, help="a -DPF_STAMPS library built beforehand (default: build it, smcsmc_amd/build.py)")
 a = ap.parse_args()
+pf.LIB_PATH = a.lib or _build.build_stamps_lib()          # the -DPF_STAMPS build of the library
+import bench
 args = argparse.Namespace(nsam=4, length=1e7, epochs=32, pops=1)
 model, segs = bench.build_workload(args, seed=1)
 f = pf.ParticleFilter(model, 10000, seed=1, max_trace_events=0, local_recomb=True, debug=a.debug)
@@ -73,3 +74,20 @@ tot = acc[:, :, :5].sum(axis=(0, 1)) * 10.0 / 1000.0
 names2 = ["no-mutation weight (all iterations)", "record head stores", "genealogy update", "record tail + tracked length", "next recombination position"]
 for nm, v in zip(names2, tot):
     print("   %-40s %.3f us per trip" % (nm, v / max(1.0, trips.sum())))
+# the finer split (words 21-28: PF_ACC2 in extend_reg_body, PF_GTICK in r_genealogy_update)
+acc2 = out[5:, :, 21:29].astype(np.int64)
+tot2 = acc2.sum(axis=(0, 1)) * 10.0 / 1000.0
+names3 = ["no-mutation weight: up to the factor (fastexp)", "no-mutation weight: the two products, loop control",
+          "update: the four draws (table or Philox), next request", "update: cut point (slice, division, lineage)",
+          "update: descendant mask", "update: node searches and intensities", "update: walk, inverse search, division",
+          "update: tree edit (remove, slots, insert)"]
+if tot2.sum() > 0:
+    for nm, v in zip(names3, tot2):
+        print("      %-52s %.3f us per trip" % (nm, v / max(1.0, trips.sum())))
+    print("      %-52s %.3f us per trip" % ("update: tree length (rest of the slot)", (tot[2] - tot2[2:].sum()) / max(1.0, trips.sum())))
+# the critical wavefront's own loop: trips and time of the wavefront that ends the launch
+st_all = out[5:, :, :9].astype(np.int64) * 10.0 / 1000.0
+ci = st_all[:, :, 8].argmax(axis=1)
+ct = trips[np.arange(len(ci)), ci]
+cl = (st_all[:, :, 5] - st_all[:, :, 4])[np.arange(len(ci)), ci]
+print("wavefront that ends the launch: %.2f trips, %.2f us in the loop; wavefront with most trips: %.2f" % (ct.mean(), cl.mean(), trips.max(axis=1).mean()))

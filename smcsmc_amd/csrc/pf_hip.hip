@@ -64,14 +64,20 @@ __device__ __forceinline__ void pf_acc_trip(unsigned long long* a) { a[5] += 1; 
         A.stamps[((size_t)s * A.nc + (size_t)(((long long)pf_bx() * PF_BS + threadIdx.x) >> 6)) * PF_STAMP_W + (k)] = wall_clock64(); } while (0)
 #define PF_TICK(var) unsigned long long var = wall_clock64()
 #define PF_ACC(slot, t0, t1) pf_acc[slot] += (t1) - (t0)
-#define PF_ACC_DECL unsigned long long pf_acc[6] = {0, 0, 0, 0, 0, 0}
-#define PF_ACC_STORE do { if (A.stamps && (threadIdx.x & 63) == 0 && s < A.stamp_rows)                                  \
+#define PF_ACC_DECL unsigned long long pf_acc[6] = {0, 0, 0, 0, 0, 0}, pf_acc2[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+// the finer split of a trip (words 21-28): [0] no-mutation weight up to the factor, [1] its two products, [2..7] the genealogy update
+// between the marks of PF_GTICK (pf_tree_reg.h): draws, cut point, descendant mask, node searches, walk and inverse, tree edit
+#define PF_ACC2(slot, t0, t1) pf_acc2[slot] += (t1) - (t0)
+#define PF_ACC_STORE do { if (A.stamps && (threadIdx.x & 63) == 0 && s < A.stamp_rows) {                                \
         for (int k_ = 0; k_ < 6; ++k_)                                                                                  \
-            A.stamps[((size_t)s * A.nc + (size_t)(((long long)pf_bx() * PF_BS + threadIdx.x) >> 6)) * PF_STAMP_W + 9 + k_] = pf_acc[k_]; } while (0)
+            A.stamps[((size_t)s * A.nc + (size_t)(((long long)pf_bx() * PF_BS + threadIdx.x) >> 6)) * PF_STAMP_W + 9 + k_] = pf_acc[k_]; \
+        for (int k_ = 0; k_ < 8; ++k_)                                                                                  \
+            A.stamps[((size_t)s * A.nc + (size_t)(((long long)pf_bx() * PF_BS + threadIdx.x) >> 6)) * PF_STAMP_W + 21 + k_] = pf_acc2[k_]; } } while (0)
 #else
 #define PF_STAMP(k) do {} while (0)
 #define PF_TICK(var) do {} while (0)
 #define PF_ACC(slot, t0, t1) do {} while (0)
+#define PF_ACC2(slot, t0, t1) do {} while (0)
 #define PF_ACC_DECL do {} while (0)
 #define PF_ACC_STORE do {} while (0)
 #endif
@@ -119,6 +125,23 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
     long long o_nres = 0; int o_bflag = 0, o_bgen = 0;
     double spec_sm[PF_PIPE_STAGE * 64 / PF_BS];
     int spec_lo = 0;
+    // PIPE: the row's own segment (end, mutation limit, state, alleles) depends on nothing but s.  Read where it is used -- behind
+    // the prologue, the end before the limit before the alleles, the state after the update loop -- it was four dependent memory
+    // round trips of every wavefront of every row; here they ride along with the first loads of the launch.
+    double sg_start = 0.0, sg_len = 0.0;
+    int sg_limit = 0, sg_state = 1;
+    int sg_allele[NM];
+#pragma unroll
+    for (int i = 0; i < NM; ++i) sg_allele[i] = 0;
+    if constexpr (PIPE) {
+        if (PR.extend) {
+            sg_start = A.seg_start[s]; sg_len = A.seg_len[s];
+            sg_limit = A.seg_limit[s]; sg_state = A.seg_state[s];
+            const int8_t* al = A.seg_alleles + (size_t)s * n;
+#pragma unroll
+            for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = al[i];
+        }
+    }
     if constexpr (PIPE) {
         const int fs = __builtin_amdgcn_readfirstlane(PR.slot_prev >= 0 ? PR.slot_prev : c->cur);
         if (PR.complete) {
@@ -444,14 +467,17 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         PF_STAMP(4);
         const bool do_extend = !PIPE || PR.extend != 0;
         const int8_t* data = A.seg_alleles + (size_t)s * n;
-        const double seg_end = do_extend ? A.seg_start[s] + A.seg_len[s] : 0.0;
+        double seg_end = 0.0;
+        int limit = 0;
+        if constexpr (PIPE) { if (do_extend) { seg_end = sg_start + sg_len; limit = sg_limit; } }
+        else { if (do_extend) { seg_end = A.seg_start[s] + A.seg_len[s]; limit = A.seg_limit[s]; } }
         const double extend_to = seg_end < v_L ? seg_end : v_L;
-        const int limit = do_extend ? A.seg_limit[s] : 0;
         unsigned one_mask = 0, zero_mask = 0, present_mask = 0, two_mask = 0;
         int missing = 0;
         if (do_extend)
-            for (int i = 0; i < n; ++i) {
-                int d = data[i];
+#pragma unroll
+            for (int i = 0; i < NM; ++i) if (i < n) {
+                int d = PIPE ? sg_allele[i] : (int)data[i];
                 missing += d == -1;
                 if (d == 1) one_mask |= 1u << i;
                 if (d == 0) zero_mask |= 1u << i;
@@ -474,6 +500,8 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             PF_TICK(tk0);
             double new_to = extend_to < next_base ? extend_to : next_base;
             double f = fastexp(-v_mu * B * (new_to - updated_to));
+            PF_TICK(tk0a);
+            PF_ACC2(0, tk0, tk0a);
             w_post *= f;
             w_pilot *= f;
             if (BIASED && cx.gK > 0) {
@@ -497,6 +525,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             }
             PF_TICK(tk1);
             PF_ACC(0, tk0, tk1);
+            PF_ACC2(1, tk0a, tk1);
             if (updated_to < extend_to) {
                 double* rec = rec_ptr(A, p, widx);
                 rec[0] = x_mark;
@@ -509,6 +538,10 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
                 r_genealogy_update<NM, BIASED, PIPE>(cx, t, &h, &tc);
                 PF_TICK(tk3);
                 PF_ACC(2, tk2, tk3);
+#ifdef PF_STAMPS
+                PF_ACC2(2, tk2, cx.gt[0]);
+                for (int k_ = 0; k_ < 5; ++k_) PF_ACC2(3 + k_, cx.gt[k_], cx.gt[k_ + 1]);
+#endif
                 if (cx.vbc) { w_post *= cx.upd_fac; w_pilot *= cx.upd_fac; cx.upd_fac = 1.0; }
                 rec[2] = h;
                 rec[3] = tc;
@@ -559,7 +592,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             if (cx.gK > 0) st1.ridx[p] = cx.ridx;
             has_pending = ds.count > 0;
         }
-        if (do_extend && A1.seg_state[s] == 0) {
+        if (do_extend && (PIPE ? sg_state : (int)A1.seg_state[s]) == 0) {
             const bool dephase = A1.flags & 2;
             const bool anc = A1.flags & 1;
             unsigned het_pairs = 0;

@@ -99,7 +99,16 @@ struct RCtx {
     // bucket tables of the two searches of an update (r_search_lut): 256 bytes each in LDS, or null
     const unsigned char* lutT; const unsigned char* lutH;
     int kbT, kbH;
+#ifdef PF_STAMPS
+    unsigned long long gt[6];     // profiling builds: marks inside the genealogy update (PF_GTICK)
+#endif
 };
+
+#ifdef PF_STAMPS
+#define PF_GTICK(k) cx.gt[k] = wall_clock64()
+#else
+#define PF_GTICK(k) do {} while (0)
+#endif
 
 #define PF_DRAW_RING 32        // blocks per slot kept in the draw table (sixteen genealogy updates)
 
@@ -308,6 +317,7 @@ __device__ __forceinline__ double r_coalesce_up(RCtx& cx, const RTree<NM>& t, in
         hh[0] = hh[NI]; tt[0] = tt[NI]; ii[0] = ii[NI];
         Hn_h = hh[0] + (h - tt[0]) * ii[0];
     }
+    PF_GTICK(3);
     double Hc = Hn_h;
     double lower = h, kd = 1.0, sn = PF_INF;
     bool stopped = false;
@@ -557,6 +567,7 @@ __device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, doubl
     }
     cx.ctr += 2;
     if constexpr (TAB) r_draws_prefetch(cx);
+    PF_GTICK(0);
     if (BIASED && cx.gK > 0 && cx.stream == 0) {
         r_sample_point_guided(cx, t, cx.nb > 1, u_point, &h);
         guided_pt = true;
@@ -597,6 +608,7 @@ __device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, doubl
     if (guided_pt) { rp = cx.g_rp; sb = cx.g_sb; }
     else r_lineages_at(t, n, n - 1, h, lin, &rp, &sb);
     *h_out = h;
+    PF_GTICK(1);
     unsigned tmask[RTree<NM>::NI + NM];          // -arg only: samples below every node id of the tree before the cut
     if (TAB || cx.want_desc) {
         // (on the rows of k_sweep always: a dozen selects that the scheduler can place beside the search that follows, where
@@ -623,7 +635,9 @@ __device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, doubl
             for (int r = 0; r < RTree<NM>::NI; ++r) tmask[r] = below[r];
         }
     }
+    PF_GTICK(2);
     double tc = r_coalesce_up<NM, TAB>(cx, t, n - 1, n, h, u_refresh);
+    PF_GTICK(4);
     *tc_out = tc;
     double Sp = t.getS(rp);
     int b_id = t.getC(rp, sb), s_id = t.getC(rp, 1 - sb);
@@ -684,6 +698,7 @@ __device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, doubl
         cx.last_desc_new = dn;
     }
     r_insert_node(t, n, ni, h_ins, b_id, pr_ins, ps_ins, troot);
+    PF_GTICK(5);
     cx.Ltree = r_tree_length(t, n);
 }
 
