@@ -54,7 +54,10 @@ namespace smco {
 
 static thread_local std::string g_err;
 
-enum { NMAX = 16 };
+enum { NMAX = 64 };         /* haplotypes of a one-population run: the capacity of the device path (PF_NMAX_WIDE) */
+enum { NMAX_NARROW = 16 };  /* structured models, tree recording and the look-ahead stay at 16, as on the device (PF_NMAX): their
+                             * sample masks (TreeEv::desc, desc_mask, tree_fl_desc / tree_rt_desc) are 32 bits wide and the create /
+                             * enable / load calls below refuse what would reach them with more */
 enum { MMAX = 256 };  /* storage for migration events per local tree (multi-population models); the limit in force is
                        * Filter::mig_cap (smco_params.mig_cap, default 96, as pf_params.mig_cap of the device path) */
 enum { DCAP_DEFAULT = 128 };   /* default capacity of the per-particle delayed-factor store: the capacity of the device path
@@ -1574,6 +1577,8 @@ struct Filter {
             for (int i = 0; i < n; ++i) hap[i] = data[i];
             for (int i = 0; i + 1 < n; i += 2) {
                 bool het = (data[i] == 2) || (M.dephase && data[i] + data[i + 1] == 1);
+                /* 32 pairs at n = 64: the count of phasings is an int here and on the device, and 2^31 of them are out of reach anyway */
+                if (het && ncfg >= (1 << 30)) throw std::runtime_error("oracle: more than 30 unphased pairs at one site");
                 if (het) { ncfg *= 2; hap[i] = 0; hap[i + 1] = 1; }
             }
             double norm = 1.0 / ncfg;
@@ -1910,7 +1915,9 @@ const char* smco_last_error(void) { return g_err.c_str(); }
 
 static void fill_model(Model& M, const smco_model* m) {
     if (m->n_pops < 1 || m->n_pops > 8) throw std::runtime_error("oracle: n_pops out of range");
-    if (m->nsam < 2 || m->nsam > NMAX) throw std::runtime_error("oracle: nsam out of range");
+    if (m->nsam < 2 || m->nsam > NMAX) throw std::runtime_error("oracle: nsam out of range (2..64 haplotypes)");
+    if (m->nsam > NMAX_NARROW && m->n_pops > 1)
+        throw std::runtime_error("oracle: more than 16 haplotypes need one population (structured models take nsam <= 16)");
     M.E = m->n_epochs; M.P = m->n_pops; M.n = m->nsam;
     const int E = M.E, P = M.P;
     M.ancestral_aware = m->flags & 1; M.dephase = m->flags & 2;
@@ -2027,6 +2034,7 @@ int smco_load_lookahead(void* h, const smco_lookahead* la) {
         Filter* f = (Filter*)h;
         const int n = f->M.n;
         const int64_t S = la->n;
+        if (n > NMAX_NARROW) throw std::runtime_error("oracle: the look-ahead (-apf) takes nsam <= 16");
         if (la->level < 0 || la->level > 4) throw std::runtime_error("-apf must be 0..4");
         f->apf = la->level; f->la_D = la->max_doubletons; f->la_Q = la->n_quantiles;
         f->la_fsd.assign(la->first_singleton_distance, la->first_singleton_distance + S * n);
@@ -2181,9 +2189,11 @@ int smco_enable_local_recomb(void* h) { ((Filter*)h)->local_map = true; return 0
 
 /* -arg: call before smco_init_prior */
 int smco_enable_tree_recording(void* h) {
-    Filter* f = (Filter*)h;
-    f->record_trees = true;
-    return 0;
+    GUARD(
+        Filter* f = (Filter*)h;
+        if (f->M.n > NMAX_NARROW) throw std::runtime_error("oracle: tree recording (-arg) takes nsam <= 16");
+        f->record_trees = true;
+    )
 }
 
 /* ParticleContainer::printTrees (pc.cpp:515-555) after resample(..., NULL, 1) (smcsmc.cpp:395): the particle whose

@@ -31,7 +31,8 @@ extern "C" {
 typedef struct smco_model {
     int32_t n_epochs;            /* E */
     int32_t n_pops;              /* P (1..8) */
-    int32_t nsam;                /* number of haplotypes n (2..16) */
+    int32_t nsam;                /* number of haplotypes n: 2..64 with one population, 2..16 with several populations, with tree
+                                  * recording and with the look-ahead (the limits of the device path; the calls say which) */
     int32_t flags;               /* bit0 ancestral_aware, bit1 dephase */
     double loci_length;          /* L, bp */
     double mutation_rate;        /* per bp per generation */

@@ -49,6 +49,37 @@ def nodata_segments(model, seglen=1000.0):
                 max_record_epoch=np.full(S, -1, np.int32) * 0 + (len(model["lags"]) - 1))
 
 
+def guide(model, K, spread, seed):
+    """A recombination guide (-guide): K segments with sampling rates and per-sample relative rates within `spread` of the
+    model's rate."""
+    rng = np.random.default_rng(seed)
+    L, n = model["loci_length"], model["nsam"]
+    pos = np.floor(np.arange(K) * L / K)
+    rates = model["recombination_rate"] * rng.uniform(1.0 / spread, spread, K)
+    leaf = rng.uniform(1.0 / spread, spread, (K, n))
+    leaf /= leaf.sum(1, keepdims=True)
+    return dict(positions=pos, rates=rates, leaf_rates=leaf)
+
+
+def fastexp(x):
+    """the filter's approximation of exp (particle.cpp's fastexp: a Pade form near zero), in numpy"""
+    xx = x * x
+    return np.where(xx < 0.516167859, 1 + 2 * x / (2 - x + xx / (6 + xx * 0.1)), np.exp(x))
+
+
+def site_lik(heights, children, alleles, mu, n):
+    """particle.cpp:625-680 on one rank-sorted tree, in numpy: leaf L0 = (allele != 1), L1 = (allele != 0); missing leaves both 1"""
+    t0 = np.zeros(2 * n - 1); t1 = np.zeros(2 * n - 1)
+    t0[:n] = alleles != 1; t1[:n] = alleles != 0
+    h = np.concatenate([np.zeros(n), heights])
+    for r in range(n - 1):
+        c0, c1 = children[2 * r], children[2 * r + 1]
+        pl = fastexp(-(h[n + r] - h[c0]) * mu); pr = fastexp(-(h[n + r] - h[c1]) * mu)
+        t0[n + r] = (t0[c0] * pl + t1[c0] * (1 - pl)) * (t0[c1] * pr + t1[c1] * (1 - pr))
+        t1[n + r] = (t1[c0] * pl + t0[c0] * (1 - pl)) * (t1[c1] * pr + t0[c1] * (1 - pr))
+    return 0.5 * t0[2 * n - 2] + 0.5 * t1[2 * n - 2]
+
+
 def make_structured(model, P=2, split_epoch=None, mig=1.0, N0=1e4, sample_pops=None, sizes=None):
     """Turns a single-population model into an isolation-with-migration model with P populations:
     symmetric migration 4*N0*m = `mig` between all pairs until the epoch `split_epoch`, at whose start every

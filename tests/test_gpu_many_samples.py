@@ -1,19 +1,31 @@
 """More than 16 haplotypes with one population: the wide kernels (pf_wide.hip: one wavefront per workgroup, 64-bit masks, the
-records' extra descendant word, k_count<64, 1>).  At n <= 16 PF_DEBUG_FORCE_WIDE runs the same kernels, which pins them bit for
-bit against the oracle; beyond 16, where there is no oracle, the tests check what the model implies (Kingman's coalescent for the
-prior, the site likelihood restated in numpy, the frequency spectrum of the simulator) and that the binary runs.
+records' extra descendant word, k_count<64, 1>), held to the CPU oracle bit for bit where they are wide.
 
-Sizes (Np, sequence length): parity 300 / 256 / 200 particles over 120 kb; prior 4096 particles over 100 kb at n = 32 and 64; local
-map 1024 particles over 60 kb at n = 64; emission 512 particles, one site; simulator 4 chunks of 3 Mb at n = 32; binary 300
-particles over 200 kb at n = 32; two sweeps 256 particles over 100 kb at n = 12 and 32."""
+(1) PF_DEBUG_FORCE_WIDE runs the wide kernels at n = 9, 12, 16 against the oracle and against the 256-lane kernels.
+(1b) Without the switch, at n = 17, 24, 32, 33, 48, 63, 64 (tests/wide_cases.py: plain, biased with delays, local map, unphased
+    with a missing block, recombination guide, odd n, the unphased pair (62, 63), 32 epochs with a partly filled last wavefront):
+    log-likelihood, trace, resampling slots and parents, final particles bit for bit, the six count arrays within 1e-9, the local
+    map's per-sample rows at n = 32, 33 and 64.  Lag calibration, the step API, rows without data and rows past the end at
+    n = 40, a re-initialised handle at n = 32: against the oracle as well.  The oracle itself is judged at these sizes, without
+    a device, in tests/test_oracle_wide_cpu.py.
+(2..6) What the model implies, independent of the oracle: Kingman's coalescent for the prior, the site likelihood restated in
+    numpy, the frequency spectrum of the simulator; and the binary runs.
+
+Sizes (Np, sequence length): forced-wide parity 300 / 256 / 200 particles over 120 kb; wide parity 100..300 particles over
+12..100 kb and 1000 particles over 40 kb at 32 epochs (tests/wide_cases.py); calibration one batch of 16384 trees over 300 kb at
+n = 40; prior 4096 particles over 100 kb at n = 32 and 64; local map 1024 particles over 60 kb at n = 64; emission 512 particles,
+one site; simulator 4 chunks of 3 Mb at n = 32; binary 300 particles over 200 kb at n = 32; two sweeps 256 particles over 100 kb
+at n = 12 and 32."""
 import gzip
 import os
 import subprocess
+import time
 
 import numpy as np
 import pytest
 
 import cases
+import wide_cases
 from smcsmc_amd import ParticleFilter, pf, simulate
 
 pytestmark = pytest.mark.gpu
@@ -56,6 +68,36 @@ def _same_run(a, b, counts_rtol=None, counts_a=None):
     assert ca["resample_count"] == cb["resample_count"]
 
 
+def _device_equals_oracle(o, g, model, local_map=False, min_resampling=1):
+    """log-likelihood, trace, resampled flags, resampling slots and parents, final particles bit for bit; the six count arrays at
+    rtol 1e-9 (the project's bound for the lagged sums); with local_map the 100-bp map, every per-sample row compared"""
+    n = model["nsam"]
+    assert _bits([o.logl()])[0] == _bits([g.logl()])[0]
+    to, tg = o.trace(), g.trace()
+    assert len(to["T"]) == len(tg["T"])
+    for k in ("T", "ess", "logl"):
+        assert (_bits(to[k]) == _bits(tg[k])).all(), k
+    assert (to["resampled"] == tg["resampled"]).all() and to["resampled"].sum() >= min_resampling
+    so, po = o.resample_events(); sg, pg = g.resample_events()
+    assert (so == sg).all() and (po == pg).all()
+    wo, wg = o.particles(), g.particles()
+    assert (wo["children"] == wg["children"]).all()
+    for k in ("heights", "w_post", "w_pilot", "next_base"):
+        assert (_bits(wo[k]) == _bits(wg[k])).all(), k
+    co, cg = o.counts(), g.counts()
+    for k in COUNT_KEYS:
+        np.testing.assert_allclose(cg[k], co[k], rtol=1e-9, atol=1e-300, err_msg=k)
+    assert cg["resample_count"] == co["resample_count"]
+    if local_map:
+        lo, lg = o.local_recomb(model["loci_length"]), g.local_recomb()
+        cum_o, cum_g = np.cumsum(lo["opp_diff"]), np.cumsum(lg["opp_diff"])
+        np.testing.assert_allclose(cum_g, cum_o, rtol=1e-7, atol=1e-7 * cum_o.max())
+        assert lo["counts"][:n].sum() > 0
+        assert lg["counts"].shape == lo["counts"].shape == (n + 2, len(lo["opp_diff"]))
+        np.testing.assert_allclose(lg["counts"], lo["counts"], rtol=1e-9, atol=1e-12 * max(1.0, lo["counts"].max()))
+        assert lg["counts"][:n].sum() == pytest.approx(cg["rec_count"].sum(), rel=1e-9)
+
+
 # ---------------------------------------------------------------- 1. the wide path against the oracle at n <= 16
 @pytest.mark.parametrize("n,Np,kind", [(9, 300, "local_recomb"), (12, 256, "biased"), (16, 200, "plain")])
 def test_force_wide_equals_oracle(oracle, hiplib, n, Np, kind):
@@ -69,29 +111,7 @@ def test_force_wide_equals_oracle(oracle, hiplib, n, Np, kind):
     o.init_prior(segs["start"][0])
     o.run(o.pack_segments(model, segs))
     g = _sweep(model, segs, Np, n, debug=FORCE_WIDE, local_recomb=kind == "local_recomb")
-    assert _bits([o.logl()])[0] == _bits([g.logl()])[0]
-    to, tg = o.trace(), g.trace()
-    assert len(to["T"]) == len(tg["T"])
-    for k in ("T", "ess", "logl"):
-        assert (_bits(to[k]) == _bits(tg[k])).all(), k
-    assert (to["resampled"] == tg["resampled"]).all() and to["resampled"].sum() > 0
-    so, po = o.resample_events(); sg, pg = g.resample_events()
-    assert (so == sg).all() and (po == pg).all()
-    wo, wg = o.particles(), g.particles()
-    assert (wo["children"] == wg["children"]).all()
-    for k in ("heights", "w_post", "w_pilot", "next_base"):
-        assert (_bits(wo[k]) == _bits(wg[k])).all(), k
-    co, cg = o.counts(), g.counts()
-    for k in COUNT_KEYS:
-        np.testing.assert_allclose(cg[k], co[k], rtol=1e-9, atol=1e-300, err_msg=k)
-    assert cg["resample_count"] == co["resample_count"]
-    if kind == "local_recomb":
-        lo, lg = o.local_recomb(model["loci_length"]), g.local_recomb()
-        cum_o, cum_g = np.cumsum(lo["opp_diff"]), np.cumsum(lg["opp_diff"])
-        np.testing.assert_allclose(cum_g, cum_o, rtol=1e-7, atol=1e-7 * cum_o.max())
-        assert lo["counts"][:n].sum() > 0
-        np.testing.assert_allclose(lg["counts"], lo["counts"], rtol=1e-9, atol=1e-12 * max(1.0, lo["counts"].max()))
-        assert lg["counts"][:n].sum() == pytest.approx(cg["rec_count"].sum(), rel=1e-9)
+    _device_equals_oracle(o, g, model, local_map=kind == "local_recomb")
 
 
 def test_force_wide_equals_default_path_at_12(hiplib):
@@ -108,6 +128,84 @@ def test_wide_calibration_equals_oracle(oracle, hiplib):
     om, ot = oracle.median_survival(model, seed=1, min_events=50, max_trees=32768)
     assert dt == ot
     assert (_bits(dm) == _bits(om)).all()
+
+
+# ---------------------------------------------------------------- 1b. the wide path against the oracle where it is wide
+@pytest.mark.parametrize("case_id", [c["id"] for c in wide_cases.PARITY])
+def test_wide_equals_oracle(oracle, hiplib, case_id):
+    """No debug switch: n > 16 takes the wide kernels by itself, with mask bits, child ids, LDS strides and record words at
+    their real size.  The oracle's and the device's seconds are printed for the budget of the suite."""
+    case = wide_cases.by_id(case_id)
+    model, segs = wide_cases.inputs(case)
+    n, lmap = case["n"], bool(case.get("local_map"))
+    al = segs["alleles"].reshape(len(segs["start"]), n)
+    if case["kind"] == "unphased" and n >= 63:
+        last = n - 2 if n % 2 == 0 else n - 3                                  # n = 64: pair (62, 63); n = 63: (60, 61), 62 alone
+        assert (al[:, last] == 2).any() and (al[:, last + 1] == 2).any() and (n % 2 == 0 or not (al[:, n - 1] == 2).any())
+    if case.get("missing"):
+        assert ((al[:, 20:33] == -1).all(axis=1) & (al[:, :20] >= 0).all(axis=1)).sum() >= 3
+    t0 = time.time()
+    o = wide_cases.run_oracle(oracle, case, model, segs)
+    t1 = time.time()
+    g = _sweep(model, segs, case["Np"], n, local_recomb=lmap)
+    t2 = time.time()
+    print("%s: %d rows, %d resamplings, oracle %.2f s, device %.2f s" % (case_id, len(segs["start"]), o.trace()["resampled"].sum(),
+                                                                        t1 - t0, t2 - t1))
+    _device_equals_oracle(o, g, model, local_map=lmap, min_resampling=3)
+    if case["E"] == 32:
+        assert case["Np"] % 64 != 0 and (o.counts()["coal_count"] > 0).all()  # every epoch column of k_count carries events
+    g.close(); o.close()
+
+
+def test_wide_calibration_equals_oracle_at_40(oracle, hiplib):
+    """lag calibration (calculate_median_survival_distances) at n = 40: the oracle's medians, bit for bit"""
+    model = cases.make_model(n=40, E=8, L=3e5)
+    dm, dt = pf.median_survival(model, seed=1, min_events=50, max_trees=16384)
+    om, ot = oracle.median_survival(model, seed=1, min_events=50, max_trees=16384)
+    assert dt == ot == 16384
+    assert (_bits(dm) == _bits(om)).all()
+    assert (om > 0).all() and len(np.unique(om)) == len(om)                  # every epoch has a median of its own
+
+
+def test_stepwise_api_matches_run_at_40(oracle, hiplib):
+    """update_segment / count / resample row by row equal run(), and both equal the oracle, at n = 40"""
+    n, Np = 40, 130
+    model = cases.make_model(n=n, E=8, L=5e4)
+    segs = cases.make_segments(model, seed=90, max_seg_len=5000)
+    a = _sweep(model, segs, Np, 5)
+    b = ParticleFilter(model, Np, seed=5, max_trace_events=64); b.init_prior(segs["start"][0]); b.load_segments(segs)
+    for s in range(len(segs["start"])):
+        b.update_segment(s); b.count(s); b.resample(s)
+    b.finish()
+    assert _bits([a.logl()])[0] == _bits([b.logl()])[0]
+    ca, cb = a.counts(), b.counts()
+    for k in ("coal_count", "coal_opp", "rec_count", "rec_opp"):
+        assert (_bits(ca[k]) == _bits(cb[k])).all()
+    o = oracle.Oracle(model, Np, seed=5, max_trace_events=64)
+    o.init_prior(segs["start"][0]); o.run(o.pack_segments(model, segs))
+    _device_equals_oracle(o, a, model, min_resampling=3)
+    _device_equals_oracle(o, b, model, min_resampling=3)
+
+
+def test_rows_without_data_and_rows_past_the_end_at_40(oracle, hiplib):
+    """the rows of tests/test_gpu_row_chain.py at n = 40: a block in which every sample is missing (no update of the weights,
+    no site), a block in which one is, and a last row without data that ends past the sequence"""
+    n, Np, L = 40, 130, 6e4
+    model = cases.make_model(n=n, E=8, L=L)
+    segs = cases.make_segments(model, seed=91, max_seg_len=3000, missing_block=(1.5e4, 2.5e4, list(range(n))))
+    al = segs["alleles"]
+    part = (segs["start"] >= 3.5e4) & (segs["start"] < 4.0e4)
+    al[part, 39] = -1
+    assert int((al == -1).all(axis=1).sum()) >= 3 and part.sum() >= 3
+    segs["length"][-1] += 7000.0
+    al[-1, :] = -1
+    assert segs["start"][-1] + segs["length"][-1] > L
+    o = oracle.Oracle(model, Np, seed=4, max_trace_events=64)
+    o.enable_local_recomb()
+    o.init_prior(segs["start"][0]); o.run(o.pack_segments(model, segs))
+    g = _sweep(model, segs, Np, 4, local_recomb=True)
+    assert g.segments_done() == len(segs["start"]) == len(o.trace()["T"])
+    _device_equals_oracle(o, g, model, local_map=True, min_resampling=3)
 
 
 # ---------------------------------------------------------------- 2. the prior beyond 16 haplotypes: Kingman's coalescent
@@ -144,22 +242,7 @@ def test_local_map_at_64(hiplib):
 
 
 # ---------------------------------------------------------------- 4. the site likelihood at high sample indices
-def _fastexp(x):
-    xx = x * x
-    return np.where(xx < 0.516167859, 1 + 2 * x / (2 - x + xx / (6 + xx * 0.1)), np.exp(x))
-
-
-def _site_lik(heights, children, alleles, mu, n):
-    """particle.cpp:625-680 on one rank-sorted tree: leaf L0 = (allele != 1), L1 = (allele != 0); missing leaves both 1"""
-    t0 = np.zeros(2 * n - 1); t1 = np.zeros(2 * n - 1)
-    t0[:n] = alleles != 1; t1[:n] = alleles != 0
-    h = np.concatenate([np.zeros(n), heights])
-    for r in range(n - 1):
-        c0, c1 = children[2 * r], children[2 * r + 1]
-        pl = _fastexp(-(h[n + r] - h[c0]) * mu); pr = _fastexp(-(h[n + r] - h[c1]) * mu)
-        t0[n + r] = (t0[c0] * pl + t1[c0] * (1 - pl)) * (t0[c1] * pr + t1[c1] * (1 - pr))
-        t1[n + r] = (t1[c0] * pl + t0[c0] * (1 - pl)) * (t1[c1] * pr + t0[c1] * (1 - pr))
-    return 0.5 * t0[2 * n - 2] + 0.5 * t1[2 * n - 2]
+_site_lik = cases.site_lik
 
 
 def test_emission_at_high_sample_indices(hiplib):
@@ -229,7 +312,7 @@ def test_binary_at_32(hiplib, tmp_path):
 
 # ---------------------------------------------------------------- 7. a re-initialised handle equals a fresh one
 @pytest.mark.parametrize("n", [12, 32])
-def test_second_sweep_equals_fresh_handle(hiplib, n):
+def test_second_sweep_equals_fresh_handle(oracle, hiplib, n):
     """The sweep after pf_init_prior on a used handle is that of a fresh handle, bit for bit.  The count totals are the one thing
     a handle keeps across pf_init_prior (they add up over its sweeps, as before): what the second sweep added to them is the
     fresh handle's counts, up to the rounding of the running sums."""
@@ -245,3 +328,9 @@ def test_second_sweep_equals_fresh_handle(hiplib, n):
     for k in COUNT_KEYS:
         added[k] = both[k] - first[k]
     _same_run(a, b, counts_rtol=1e-9, counts_a=added)
+    if n == 32:
+        # ... and the fresh handle's sweep, hence the second sweep of the used one, is the oracle's
+        o = oracle.Oracle(model, 256, seed=8, max_trace_events=64)
+        o.init_prior(segs["start"][0]); o.run(o.pack_segments(model, segs))
+        _device_equals_oracle(o, b, model, min_resampling=3)
+        assert _bits([a.logl()])[0] == _bits([o.logl()])[0]

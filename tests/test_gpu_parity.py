@@ -526,14 +526,7 @@ def test_device_exp_digamma(oracle, hiplib):
 
 # ---------------------------------------------------------------- recombination guide (-guide)
 
-def _guide(model, K, spread, seed):
-    rng = np.random.default_rng(seed)
-    L, n = model["loci_length"], model["nsam"]
-    pos = np.floor(np.arange(K) * L / K)
-    rates = model["recombination_rate"] * rng.uniform(1.0 / spread, spread, K)
-    leaf = rng.uniform(1.0 / spread, spread, (K, n))
-    leaf /= leaf.sum(1, keepdims=True)
-    return dict(positions=pos, rates=rates, leaf_rates=leaf)
+_guide = cases.guide
 
 
 @pytest.mark.parametrize("n,bias", [(4, False), (4, True), (7, True), (2, False), (10, True), (12, False)])

@@ -4,6 +4,7 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,3 +43,37 @@ def test_header_declares_the_wide_path():
     assert len(bits) == len(set(bits)), "two debug switches share a bit"
     from smcsmc_amd import pf
     assert pf.DEBUG_FORCE_WIDE == 2048 and pf.NSAM_MAX_WIDE == 64
+
+
+# ---------------------------------------------------------------- the oracle states the same limits as the device path
+def test_oracle_accepts_64_haplotypes_with_one_population(oracle):
+    import cases
+    model = cases.make_model(n=64, E=4, L=1e4)
+    o = oracle.Oracle(model, 8, seed=1)
+    o.init_prior(0.0)
+    p = o.particles()
+    assert p["children"].shape == (8, 63, 2) and p["children"].max() == 2 * 64 - 3 and (p["heights"] > 0).all()
+    o.close()
+    with pytest.raises(RuntimeError, match="nsam out of range"):
+        oracle.Oracle(cases.make_model(n=65, E=4, L=1e4), 8, seed=1)
+
+
+def test_oracle_refuses_what_the_wide_path_does_not_cover(oracle):
+    import cases
+    from smcsmc_amd import segments as segmod
+    model = cases.make_model(n=17, E=4, L=1e4)
+    with pytest.raises(RuntimeError, match="more than 16 haplotypes need one population"):
+        oracle.Oracle(cases.make_structured(model, P=2, split_epoch=2), 8, seed=1)
+    o = oracle.Oracle(model, 8, seed=1)
+    with pytest.raises(RuntimeError, match=r"tree recording \(-arg\) takes nsam <= 16"):
+        o.enable_tree_recording()
+    segs = cases.make_segments(model, seed=1)
+    rows = [(int(s) + 1, int(l), int(st), list(map(int, a)))
+            for s, l, st, a in zip(segs["start"], segs["length"], segs["state"], segs["alleles"].reshape(-1, 17))]
+    with pytest.raises(RuntimeError, match=r"look-ahead \(-apf\) takes nsam <= 16"):
+        o.load_lookahead(segmod.pack_lookahead(rows, 17), 1, (np.ones((17, len(segmod.TBL_QUANTILES))), 1.0))
+    o.close()
+    # all three are accepted at 16
+    m16 = cases.make_model(n=16, E=4, L=1e4)
+    oracle.Oracle(cases.make_structured(m16, P=2, split_epoch=2), 8, seed=1).close()
+    o = oracle.Oracle(m16, 8, seed=1); o.enable_tree_recording(); o.close()
