@@ -113,8 +113,6 @@ typedef struct pf_params {
 #define PF_DEBUG_NO_FUSE   2     /* complete every row with the stand-alone k_resample (two-stream pipeline) */
 #define PF_DEBUG_NO_COUNT  4     /* profiling: skip the lagged counting and the ledger upkeep */
 #define PF_DEBUG_TWO_LAUNCH 8    /* rows as two launches (extend + decide) instead of the single-launch pipeline */
-#define PF_DEBUG_SPLIT_ROLES 64  /* one population: the extend role and the bookkeeping / ledger / count roles of a step as two launches on
-                                  * two streams, as the structured models run them (A/B against the single launch) */
 #define PF_DEBUG_NO_SPEC_STAGE 32 /* row pipeline: stage the pilot scans for the parent search only once the range is known (A/B) */
 #define PF_DEBUG_K_PIPE   16     /* the round-2 row paths: k_pipe (argument block passed by value, windows from the host) instead of k_sweep;
                                   * structured models: k_extend_mpr + k_decide with the counts on a second stream instead of the row pipeline */
@@ -124,18 +122,10 @@ typedef struct pf_params {
 
 #define PF_DEBUG_NO_SEARCH_LUT 256 /* k_sweep: the epoch searches of an update by the four-way search instead of the bucket tables (A/B) */
 
-#define PF_DEBUG_COUNT_YOUNG_FIRST 512 /* row pipeline: count workgroups in ascending epoch order, as before round 3 (A/B) */
-
-#define PF_DEBUG_FLAG_HANDOFF 8192 /* one population: a row as two launches (extend + draw roles; bookkeeping + ledger + counts) that no longer wait
-                                  * for each other's END: the extend launches alternate between two streams and hand the row over through
-                                  * arrival counters in memory, the other launches wait the same way (run_sweep_flags; same bits) */
-
 #define PF_DEBUG_ONE_LAUNCH (1 << 23) /* one population, at most four haplotypes, no focused sampling: every role of a step in ONE launch (k_sweep4 with the
                                   * ledger and count workgroups riding along: the form of rounds 3 and 4) instead of two -- the extend, bookkeeping
                                   * and draw roles; the ledger and count roles on the counting stream, four workgroups to a compute unit
                                   * (run_sweep_split).  A/B, same bits */
-
-#define PF_DEBUG_CU_MASK 1024     /* with PF_DEBUG_SPLIT_ROLES: the two streams on disjoint sets of compute units (experiment) */
 
 #define PF_DEBUG_FORCE_WIDE 2048  /* one population: run the wide kernels of nsam > 16 (64-lane workgroups, 64-bit masks, the records' extra
                                    * descendant word, k_count<64>) whatever nsam is -- how that path is pinned against the oracle at n <= 16 */

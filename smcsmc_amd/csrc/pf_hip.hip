@@ -1904,6 +1904,9 @@ __device__ __forceinline__ void pipe_count_item(const KA& A, const PipeLaunch& P
     // the columns of the oldest epochs first: their lags are the shortest, their windows sit right behind the front where
     // nearly every particle is still its own ancestor, and their workgroups are the long ones -- dispatched last they were
     // what a launch ended with
+    // (bit 512 of KArgs::flags is set by nobody any more -- it chose the ascending order until that lost its A/B.  Its two tests stay for
+    // k_pipe's sake, the comparator of the sweep tests: without them the register allocation of five k_pipe instances comes out with 36 to
+    // 68 bytes of scratch memory where it had none -- profiles/round6/r6_kernel_meta.md)
     int e, cbx, cnb;
     if (A.cw_off && !(A.flags & 512)) {
         int j = 0, hi = A.E;                       // the column of workgroup idx: last j with cw_off[j] <= idx
@@ -1939,7 +1942,7 @@ __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeL
             return;
         }
         if (bx == nb) {
-            if (PL.b_slot < 0 || PL.nL == -2) return;          // nL = -2: the extend launch of a split step (-3: one that keeps the bookkeeping)
+            if (PL.b_slot < 0) return;
             extern __shared__ double smem[];
             PipeLds q = pipe_carve(smem + (2 * PF_EPAD + A.E + 2 * PF_BIAS_MAX + 3), A.nc);
             pipe_bookkeeping<BIASED>(A, q, PL, Wb);
@@ -1952,7 +1955,7 @@ __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeL
     } else {
         if (bx <= nb) return;
     }
-    if (PL.lc_slot < 0 || PL.nL < -1) return;
+    if (PL.lc_slot < 0 || PL.nL < -1) return;          // nL = -3: the extend launch of a split step (run_sweep_split)
     const Ctrl* c = A.ctrl;
     const Ctrl::RowInfo& r = c->ri[PL.lc_slot];
     const int lb = bx - (nb + 1) - PL.nT;
@@ -2043,14 +2046,13 @@ __device__ __forceinline__ unsigned long long* wg_trace_slot(SweepChunkC& ch, lo
     return ch.trace + ((size_t)(t - ch.trace_t0) * (size_t)ch.trace_stride + lin) * 4;
 }
 
-template <int NM, bool BIASED, bool EXACT, bool TREES, bool HANDOFF = false, bool TRACE = false, bool QUEUE = false>
+template <int NM, bool BIASED, bool EXACT, bool TREES, bool TRACE = false, bool QUEUE = false>
 __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long long t, int nb) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[pf_chunk()];
     KArgsC& A = ch.A;
     const long long s = ch.s_begin + t;
     __shared__ Windows W;           // written and read by the bookkeeping workgroup only
-    bool ok = true;
     if constexpr (TRACE) {
         if (threadIdx.x == 0) {
             if (unsigned long long* w = wg_trace_slot(ch, t)) {
@@ -2060,24 +2062,12 @@ __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long 
             }
         }
     }
-    if constexpr (HANDOFF) {
-        // this launch was enqueued without waiting for the one of step t - 1 to end: its workgroups wait for that launch's workgroups
-        // to have arrived (state, scans, partials and draw table of row s - 1 are then visible), and -- ring reuse -- for the
-        // bookkeeping / ledger / count launch of step t - 14 to have ended
-        Ctrl* c = A.ctrl;
-        if (t >= PF_RING - 2) ok = sweep_wait_ge(c, (const unsigned*)&c->blc_step, (unsigned)(t - (PF_RING - 3)));      // (nothing is read from that launch)
-        if (ok && t > 0) { ok = sweep_wait_ge(c, &c->xt_done[(t - 1) & (PF_RING - 1)], (unsigned)((t - 1) / PF_RING + 1) * (unsigned)ch.xt_wgs); sweep_acquire(); }
-    }
     PipeLaunch PL;
-    if (ok && sweep_plan(ch, s, nb, PL)) {
-        if (ch.split == 1) PL.nL = -2;                     // extend and draw roles only: the other roles are k_sweep_blc's
-        else {
-            if (ch.split == 2) PL.nL = -3;                 // ... the bookkeeping too: only ledger and counts are k_sweep_blc's (run_sweep_split)
-            if (pf_bx() == nb && PL.b_slot >= 0) sweep_windows(A, A.ctrl, PL.b_pos, W);
-        }
+    if (sweep_plan(ch, s, nb, PL)) {
+        if (ch.split == 2) PL.nL = -3;                     // extend, bookkeeping and draw roles only: ledger and counts are k_sweep_blc's (run_sweep_split)
+        if (pf_bx() == nb && PL.b_slot >= 0) sweep_windows(A, A.ctrl, PL.b_pos, W);
         pipe_roles<NM, BIASED, EXACT, TREES, 1, false, QUEUE>(A, s, PL, W);
     }
-    if constexpr (HANDOFF) sweep_arrive(&A.ctrl->xt_done[t & (PF_RING - 1)]);
     if constexpr (TRACE) {
         __syncthreads();
         if (threadIdx.x == 0) if (unsigned long long* w = wg_trace_slot(ch, t)) w[1] = wall_clock64();
@@ -2096,22 +2086,15 @@ template <bool EXACT, bool TREES>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_sweep4(const SweepChunk* tab_g, long long t, int nb) {
     sweep_kernel_body<4, false, EXACT, TREES>(tab_g, t, nb);
 }
-// the extend / draw launch of run_sweep_flags: the same body behind a wait for the previous step's arrivals (a kernel of its own:
-// the few values the wait keeps alive would tip k_sweep4 into scratch memory)
-template <bool EXACT>
-__global__ __launch_bounds__(PF_BS) void k_sweep4h(const SweepChunk* tab_g, long long t, int nb) {
-    sweep_kernel_body<4, false, EXACT, false, true>(tab_g, t, nb);
-}
-
 // the headline instance with the ledger and count work of a step taken off a queue (pf_params.count_workers; the traced form too)
 template <bool EXACT, bool TRACE>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_sweep4q(const SweepChunk* tab_g, long long t, int nb) {
-    sweep_kernel_body<4, false, EXACT, false, false, TRACE, true>(tab_g, t, nb);
+    sweep_kernel_body<4, false, EXACT, false, TRACE, true>(tab_g, t, nb);
 }
 // the headline instance with a time stamp at either end of every workgroup (pf_set_wg_trace: where do the slots of a step go?)
 template <bool EXACT>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_sweep4t(const SweepChunk* tab_g, long long t, int nb) {
-    sweep_kernel_body<4, false, EXACT, false, false, true>(tab_g, t, nb);
+    sweep_kernel_body<4, false, EXACT, false, true>(tab_g, t, nb);
 }
 
 // The bookkeeping, ledger and count roles of a step as a launch of their own: what the structured models run on the counting
@@ -2132,19 +2115,6 @@ __device__ __forceinline__ void sweep_blc_body(const SweepChunk* tab_g, long lon
         if (ch.split == 2) PL.b_slot = -1;                 // ... and so does the bookkeeping (run_sweep_split)
         if (pf_bx() == 0 && PL.b_slot >= 0) sweep_windows(A, c, PL.b_pos, W);
         pipe_roles<NM, BIASED, EXACT, false, P, true, QUEUE, LEAN>(A, s, PL, W);
-    }
-    if (ch.handoff) {
-        // run_sweep_flags: the extend launch of step t + 14 overwrites ring slots this launch read; it polls Ctrl::blc_step, which the
-        // last workgroup of this launch to finish advances (launches of this kind run one after the other; nothing they WRITE is read
-        // by an extend launch, so no release is needed -- a release per workgroup would write the L2 back a thousand times a step)
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned before = __hip_atomic_fetch_add(&c->blc_arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (before + 1 == gridDim.x) {
-                __hip_atomic_store(&c->blc_arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&c->blc_step, (int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
     }
 }
 
@@ -2179,8 +2149,7 @@ __global__ void k_sweep_seed(const SweepChunk* tab_g) {
         c->xr[slot].n_res = c->n_resample; c->xr[slot].gen = c->gen; c->xr[slot].flag = 0;
     }
     if ((int)threadIdx.x < A.E) c->counted_to[threadIdx.x] = ch.counted_to[threadIdx.x];
-    if ((int)threadIdx.x < PF_RING) { c->xt_done[threadIdx.x] = 0; c->wq[threadIdx.x] = 0; }
-    if (threadIdx.x == 0) { c->blc_arrive = 0; c->blc_step = 0; }
+    if ((int)threadIdx.x < PF_RING) c->wq[threadIdx.x] = 0;
     if (ch.nT > 0) {
         // the draw table starts every call empty, from the counters the slots have now
         const size_t par = (size_t)((ch.s_begin + 1) & 1);          // parity of row s_begin - 1
@@ -2634,17 +2603,11 @@ struct pf_handle {
     int ledger_wgs = 192;         // workgroups per step that re-base the older generations' run lists after a resampling (beside one per particle block)
     int workers = 0;              // pf_params.count_workers: workgroups per step that take the ledger and count items off a queue (0: one workgroup per item)
     std::vector<int> cw_off;      // [E + 1] first count workgroup of the j-th column, oldest epoch first (KArgs::cw_off)
-    bool flag_handoff = false;    // PF_DEBUG_FLAG_HANDOFF: one population, rows as extend / draw launches that alternate between two streams and
-                                  // bookkeeping / ledger / count launches on the counting stream, ordered by counters in memory instead of events
-    hipStream_t stream2 = nullptr;
-    bool sweep_handoff = false;   // (argument of sweep_table: the table it builds is for run_sweep_flags)
-    bool sweep_split2 = false;    // (argument of sweep_table: ... for run_sweep_split)
     bool split_many = false;      // a step as two launches (run_sweep_split; not with PF_DEBUG_ONE_LAUNCH)
     int split_batch = 0;          // ... the second launches enqueued in batches of this many steps behind one completion signal (0: chosen by the runner)
     unsigned long long* d_trace = nullptr;   // pf_set_wg_trace (leader of a pf_run_many call): four words per workgroup and step
     size_t trace_words = 0;
     int trace_t0 = 0, trace_n = 0, trace_stride = 0, trace_grid[3] = {0, 0, 0};
-    bool split_roles = false;     // PF_DEBUG_SPLIT_ROLES: one population too runs the extend role and the other roles as two launches on two streams
     bool pipe_mp = false;         // structured models on the row pipeline: extend launches on the filter stream, the other roles on the counting stream
     size_t smem_sweep_x = 0;
     std::vector<hipEvent_t> ev_x, ev_blc;   // completion of the last 16 extend / bookkeeping-ledger-count launches
@@ -2840,21 +2803,8 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     if (hipSetDevice(device) != hipSuccess) { delete h; return fail("hipSetDevice failed"); }
     // (no stream priorities: a high-priority filter stream per handle gains nothing for one chunk and costs 30 % of the
     // throughput when several chunks share the device -- priority streams share fewer hardware queues)
-    if ((p->debug & PF_DEBUG_SPLIT_ROLES) && (p->debug & PF_DEBUG_CU_MASK) && m->n_pops == 1) {
-        // the extend launches on compute units of their own: the count workgroups of the other stream, which wait on memory
-        // most of the time but share issue slots, LDS and the vector memory path with whatever sits beside them, stay off them
-        int ncu = 0;
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device);
-        const int words = (ncu + 31) / 32;
-        const int nx = std::min(ncu / 2, (int)((p->np + PF_BS - 1) / PF_BS) * 2 + 8);       // extend + draw workgroups
-        std::vector<uint32_t> mx((size_t)words, 0u), mc((size_t)words, 0u);
-        for (int i = 0; i < ncu; ++i) (i < nx ? mx : mc)[(size_t)(i >> 5)] |= 1u << (i & 31);
-        if (hipExtStreamCreateWithCUMask(&h->stream, (uint32_t)words, mx.data()) != hipSuccess ||
-            hipExtStreamCreateWithCUMask(&h->cstream, (uint32_t)words, mc.data()) != hipSuccess) { delete h; return fail("hipExtStreamCreateWithCUMask failed"); }
-    } else {
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail("hipStreamCreate failed"); }
     if (hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail("hipStreamCreate failed"); }
-    }
     h->sync_ev.resize(512);
     for (auto& e : h->sync_ev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { delete h; return fail("hipEventCreate failed"); }
     const int E = m->n_epochs, n = m->nsam;
@@ -2882,23 +2832,19 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     h->two_launch_rows = (p->debug & PF_DEBUG_TWO_LAUNCH) != 0;
     h->use_k_pipe = (p->debug & PF_DEBUG_K_PIPE) != 0;
     h->no_spec_stage = (p->debug & PF_DEBUG_NO_SPEC_STAGE) != 0;
-    h->split_roles = (p->debug & PF_DEBUG_SPLIT_ROLES) != 0;
     h->split_batch = (p->debug >> 16) & 15;       // (bits 16-19 of debug: tuning experiments; 0 = four with several chunks, one with one)
     // one population, at most four haplotypes, no focused sampling, no -arg: a step is two launches (run_sweep_split) unless the switch says one
     h->split_many = !(p->debug & PF_DEBUG_ONE_LAUNCH) && P == 1 && n <= 4 && m->n_bias_heights == 0 && m->n_rate_segments == 0 && !(p->flags & 2) &&
-                    !(p->debug & (PF_DEBUG_SPLIT_ROLES | PF_DEBUG_FLAG_HANDOFF | PF_DEBUG_K_PIPE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_NO_FUSE));
+                    !(p->debug & (PF_DEBUG_K_PIPE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_NO_FUSE));
     // (several chunks per GPU -- the caller set count_wgs -- : on the rows that do not resample, nine in ten, these workgroups find nothing to do and
     // leave after 2 us of a slot each; with 32 instead of 192 eight chunks gain 3 %, one chunk is the same either way: 28.7 us per row)
     h->ledger_wgs = p->count_wgs > 0 ? 32 : std::max(16, std::min(PF_LEDGER_BLOCKS, 192));
-    // (instantiated for the headline shape only: at most four haplotypes, no focused sampling or guide, no tree dump)
-    h->flag_handoff = (p->debug & PF_DEBUG_FLAG_HANDOFF) != 0 && P == 1 && n <= 4 && m->n_bias_heights == 0 && m->n_rate_segments == 0 && !(p->flags & 2);
-    if (h->flag_handoff && hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking) != hipSuccess) { delete h; return fail("hipStreamCreate failed"); }
     h->h_lags.assign(m->lags, m->lags + E);
     h->h_counted_to.assign(E, 0.0);
     h->h_L = m->loci_length;
     KArgs& A = h->A;
     memset(&A, 0, sizeof(A));
-    A.E = E; A.n = n; A.flags = m->flags | (h->no_spec_stage ? 256 : 0) | ((p->debug & PF_DEBUG_COUNT_YOUNG_FIRST) ? 512 : 0);
+    A.E = E; A.n = n; A.flags = m->flags | (h->no_spec_stage ? 256 : 0);
     A.flags |= p->debug & (7 << 20);        // profiling probes of the count role (bits 20, 21: the sums are then wrong on purpose)
     A.L = m->loci_length; A.mu = m->mutation_rate; A.rho = m->recombination_rate;
     A.Np = Np;
@@ -3084,8 +3030,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     // workgroups 32.9 us per row, 16: 38.7, 8: 53.7, 4: 91.4, 2: 168 -- profiles/round3/count_wgs.md)
     h->ncw = p->count_wgs > 0 ? std::min<int>(p->count_wgs, h->nblocks) : h->nblocks;
     // (the queue has one kernel instance so far: one population, at most four haplotypes, no focused sampling, no -arg, single launch per step)
-    h->workers = (h->pipe && !h->use_k_pipe && P == 1 && n <= 4 && !(m->n_bias_heights > 0 || m->n_rate_segments > 0) && !(p->flags & 2) &&
-                  !(p->debug & (PF_DEBUG_SPLIT_ROLES | PF_DEBUG_FLAG_HANDOFF))) ? std::max(0, std::min(p->count_workers, 4096)) : 0;
+    h->workers = (h->pipe && !h->use_k_pipe && P == 1 && n <= 4 && !(m->n_bias_heights > 0 || m->n_rate_segments > 0) && !(p->flags & 2)) ? std::max(0, std::min(p->count_workers, 4096)) : 0;
     {
         // count workgroups per epoch column of the row pipeline: the tasks of an epoch are the live ancestors of the generations in its
         // window, about Np / (1 + depth), depth = generations between window and front, i.e. in proportion to its lag: a column whose
@@ -3099,7 +3044,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
             w = std::max(std::min(2, h->ncw), std::min(w, h->ncw));
             // (only when the caller set count_wgs, i.e. runs several chunks side by side and wants fewer workgroups: a single chunk
             // leaves most of the chip idle, and there every column is shortest with all the workgroups it can get)
-            if ((p->debug & PF_DEBUG_COUNT_YOUNG_FIRST) || p->count_wgs <= 0) w = h->ncw;
+            if (p->count_wgs <= 0) w = h->ncw;
             h->cw_off[j + 1] = h->cw_off[j] + w;
         }
         int* dcw = nullptr;
@@ -3107,7 +3052,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
             rc |= dalloc(h, &dcw, E + 1);
             if (!rc) { hipMemcpyAsync(dcw, h->cw_off.data(), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, h->stream); hipStreamSynchronize(h->stream); }
             // (with every column at full width the kernels compute column and workgroup from the index: no table)
-            A.cw_off = ((p->debug & PF_DEBUG_COUNT_YOUNG_FIRST) || p->count_wgs <= 0) ? nullptr : dcw;
+            A.cw_off = p->count_wgs <= 0 ? nullptr : dcw;
         }
     }
     rc |= dalloc(h, &A.totals, (size_t)A.ncol * E);
@@ -3145,6 +3090,12 @@ pf_handle* pf_create(const pf_model* m, const pf_params* p, int device) {
     // with -arg (flags bit 1) nothing may be overwritten: rings sized for a whole chunk by default
     const bool trees = p && (p->flags & 2);
     if (!m || !p) { g_err = "pf_create: null model or parameters"; return nullptr; }
+    // switches of launch arrangements that were removed: a stale caller is told so, it does not silently get the default
+    static const struct { int bit; const char* what; } removed[] = {
+        {64, "one population as two launches on two streams"}, {512, "count workgroups in ascending epoch order"},
+        {1024, "the two streams on disjoint compute units"}, {8192, "hand-off between launches through counters in memory"}};
+    for (const auto& r : removed)
+        if (p->debug & r.bit) { g_err = "pf_create: pf_params.debug bit " + std::to_string(r.bit) + " (" + r.what + ") selected a launch arrangement that has been removed"; return nullptr; }
     if (p->log_cap < 0 || p->gen_cap < 0 || p->piece_cap < 0 || p->log_cap > 0x7fffffffLL || p->piece_cap > 0x7fffffffLL) {
         g_err = "pf_create: ring capacities out of range";
         return nullptr;
@@ -3153,8 +3104,8 @@ pf_handle* pf_create(const pf_model* m, const pf_params* p, int device) {
         g_err = "pf_create: log_cap and gen_cap must be at least 4";
         return nullptr;
     }
-    if (p->gen_cap > 0 && p->gen_cap < PF_RING + 4 && (m->n_pops > 1 || (p->debug & PF_DEBUG_SPLIT_ROLES))) {
-        g_err = "pf_create: gen_cap must be at least 20 when the extend role runs ahead of the counts (structured models, PF_DEBUG_SPLIT_ROLES)";
+    if (p->gen_cap > 0 && p->gen_cap < PF_RING + 4 && m->n_pops > 1) {
+        g_err = "pf_create: gen_cap must be at least 20 when the extend role runs ahead of the counts (structured models)";
         return nullptr;
     }
     // (more than 16 haplotypes: a record is 8 (n + 5) bytes, 552 at n = 64; the default ring then holds as many bytes per particle as
@@ -3181,7 +3132,6 @@ void pf_destroy(pf_handle* h) {
     for (auto e : h->ev_x) if (e) hipEventDestroy(e);
     for (auto e : h->ev_blc) if (e) hipEventDestroy(e);
     if (h->cstream) hipStreamDestroy(h->cstream);
-    if (h->stream2) { hipStreamSynchronize(h->stream2); hipStreamDestroy(h->stream2); }
     for (auto& sp : h->spans) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
     for (auto e : h->ev_pool) hipEventDestroy(e);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -3676,7 +3626,8 @@ static bool sweep_compatible(const pf_handle* a, const pf_handle* b) {
 }
 
 // the per-chunk table of a k_sweep call in the leader's device buffer; returns the number of steps (0: nothing to do)
-static long long sweep_table(pf_handle* const* hs, int nh, long long s_begin, long long s_end, int nL_full, bool* failed) {
+// (split: SweepChunk::split of every chunk)
+static long long sweep_table(pf_handle* const* hs, int nh, long long s_begin, long long s_end, int nL_full, int split, bool* failed) {
     pf_handle* h = hs[0];
     const int E = h->E;
     *failed = true;
@@ -3704,12 +3655,8 @@ static long long sweep_table(pf_handle* const* hs, int nh, long long s_begin, lo
         ch.ncw = g->ncw;
         ch.nblk = g->nblocks;
         ch.nT = (g->A.dt_tab && g->P == 1) ? g->nblocks : 0;
-        ch.split = (g->P == 1 && g->split_roles && !g->A.rec_trees) ? 1 : 0;
+        ch.split = split;
         ch.workers = g->workers;
-        ch.handoff = h->sweep_handoff ? 1 : 0;
-        ch.xt_wgs = h->sweep_handoff ? g->nblocks + (ch.nT > 0 ? 1 + ch.nT : 0) : 0;
-        if (h->sweep_handoff) ch.split = 1;
-        if (h->sweep_split2) ch.split = 2;
         ch.trace = h->d_trace; ch.trace_t0 = h->trace_t0; ch.trace_n = h->d_trace ? h->trace_n : 0; ch.trace_stride = h->trace_stride;
         if (last >= s_begin) steps = std::max(steps, last - s_begin + 3);
     }
@@ -3722,13 +3669,10 @@ static long long sweep_table(pf_handle* const* hs, int nh, long long s_begin, lo
     return steps;
 }
 
-static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
+// What the sweep runners share.  A sweep runs on the leader's streams (hs[0]); the other handles' streams, and anything they still have
+// in flight, come first ...
+static void sweep_join(pf_handle* const* hs, int nh) {
     pf_handle* h = hs[0];
-    if (s_begin >= s_end) return 0;
-    const int nb = h->nblocks, E = h->E;
-    const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
-    const int nL_full = nb + h->ledger_wgs;
-    // the other handles' streams (anything they still have in flight) come first, then the table
     for (int k = 0; k < nh; ++k) {
         pf_handle* g = hs[k];
         if (g->ev_cnt) { hipStreamWaitEvent(h->stream, g->ev_cnt, 0); g->ev_cnt = nullptr; }
@@ -3738,6 +3682,75 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
             hipStreamWaitEvent(h->stream, ev, 0);
         }
     }
+}
+
+// ... and each chunk's own stream continues after the sweep
+static void sweep_leave(pf_handle* const* hs, int nh, long long s_begin) {
+    pf_handle* h = hs[0];
+    for (int k = 0; k < nh; ++k) {
+        pf_handle* g = hs[k];
+        const long long last = h->h_sweep[k].s_last;
+        if (last >= s_begin) g->seg_done = last + 1;
+        if (k > 0) {
+            hipEvent_t ev = next_sync_event(h);
+            hipEventRecord(ev, h->stream);
+            hipStreamWaitEvent(g->stream, ev, 0);
+        }
+    }
+}
+
+// completion events of the last sixteen extend launches (ev_x) and of the last sixteen launches of the other roles (ev_blc)
+static int sweep_event_ring(pf_handle* h) {
+    if (!h->ev_x.empty()) return 0;
+    // all thirty-two or none: a vector left half filled would pass for complete on the next call, and launches with null
+    // completion events lose the ordering between the two streams without a word
+    std::vector<hipEvent_t> ev(32, nullptr);
+    bool ok = true;
+    for (auto& e : ev) if (ok && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { e = nullptr; ok = false; }
+    if (!ok) {
+        for (auto e : ev) if (e) hipEventDestroy(e);
+        g_err = "hipEventCreate failed";
+        return -1;
+    }
+    h->ev_x.assign(ev.begin(), ev.begin() + 16); h->ev_blc.assign(ev.begin() + 16, ev.end());
+    return 0;
+}
+
+// Ledger and count workgroups per chunk in the step of row s.  They belong to row s - 2, whose windows (W2) the host knows as well as the
+// device does: the grid ends with the last epoch column any chunk needs (epochs before a chunk's first moving one are not launched at all)
+static int sweep_lc_wgs(pf_handle* const* hs, int nh, long long s_begin, long long s, const Windows* W2, int nL_full) {
+    pf_handle* h = hs[0];
+    int columns = 0;
+    bool any_lc = false;
+    for (int k = 0; k < nh; ++k)
+        if (s >= s_begin + 2 && s - 2 <= h->h_sweep[k].s_last && !hs[k]->no_count) { any_lc = true; columns = std::max(columns, h->E - W2[k].first); }
+    const int workers = h->h_sweep[0].workers;
+    return workers > 0 ? (any_lc ? workers : 0) : nL_full + h->cw_off[columns];
+}
+
+// after the step of row s: W1 / W2 become the windows of rows s and s - 1 of every chunk
+static void sweep_advance_windows(pf_handle* const* hs, int nh, long long s, Windows* W1, Windows* W2) {
+    pf_handle* h = hs[0];
+    for (int k = 0; k < nh; ++k) {
+        pf_handle* g = hs[k];
+        W2[k] = W1[k];
+        if (s <= h->h_sweep[k].s_last) {
+            W1[k] = host_windows(g, seg_pos(g, s), false);
+            g->step_windows = W1[k];
+            if (W1[k].first < g->E && !g->no_count) g->fin_pending = true;
+        } else {
+            W1[k] = no_windows(g);
+        }
+    }
+}
+
+static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
+    pf_handle* h = hs[0];
+    if (s_begin >= s_end) return 0;
+    const int nb = h->nblocks, E = h->E;
+    const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
+    const int nL_full = nb + h->ledger_wgs;
+    sweep_join(hs, nh);
     if (h->trace_n > 0 && !h->d_trace) {
         // pf_set_wg_trace: room for the largest grid a step of these chunks can have
         const int nT = (h->A.dt_tab && h->P == 1) ? nb : 0;
@@ -3747,22 +3760,14 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
         hipMemsetAsync(h->d_trace, 0, h->trace_words * 8, h->stream);
     }
     bool failed = false;
-    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, &failed);
+    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, 0, &failed);
     if (failed) return -1;
     if (steps == 0) return 0;
-    // the count workgroups of a step belong to row s - 2, whose windows the host knows as well as the device does: the grid
-    // ends with the last epoch column any chunk needs (epochs before a chunk's first moving one are not launched at all)
     std::vector<Windows> W1((size_t)nh), W2((size_t)nh);
     for (int k = 0; k < nh; ++k) { W1[k] = no_windows(hs[k]); W2[k] = W1[k]; }
     for (long long t = 0; t < steps; ++t) {
         const long long s = s_begin + t;
-        int columns = 0;
-        for (int k = 0; k < nh; ++k)
-            if (s >= s_begin + 2 && s - 2 <= h->h_sweep[k].s_last && !hs[k]->no_count) columns = std::max(columns, E - W2[k].first);
-        const int ncount = h->cw_off[columns];
-        bool any_lc = false;
-        for (int k = 0; k < nh; ++k) any_lc = any_lc || (s >= s_begin + 2 && s - 2 <= h->h_sweep[k].s_last && !hs[k]->no_count);
-        const unsigned per_chunk = (unsigned)(nb + 1 + h->h_sweep[0].nT + (h->h_sweep[0].workers > 0 ? (any_lc ? h->h_sweep[0].workers : 0) : nL_full + ncount));
+        const unsigned per_chunk = (unsigned)(nb + 1 + h->h_sweep[0].nT + sweep_lc_wgs(hs, nh, s_begin, s, W2.data(), nL_full));
         const dim3 grid(per_chunk, (unsigned)nh);          // (pf_bx() / pf_chunk(), pf_device.h)
         const bool tm_on = timing_on(h, s);
         {
@@ -3774,29 +3779,10 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
         }
         if (check_launch("k_sweep")) return -1;
         if ((t & 1023) == 1023) trim_spans(h);
-        for (int k = 0; k < nh; ++k) {
-            pf_handle* g = hs[k];
-            W2[k] = W1[k];
-            if (s <= h->h_sweep[k].s_last) {
-                W1[k] = host_windows(g, seg_pos(g, s), false);
-                g->step_windows = W1[k];
-                if (W1[k].first < E && !g->no_count) g->fin_pending = true;
-            } else {
-                W1[k] = no_windows(g);
-            }
-        }
+        sweep_advance_windows(hs, nh, s, W1.data(), W2.data());
     }
     h->k_launches[0] -= 2;                                      // flush steps are not rows
-    for (int k = 0; k < nh; ++k) {
-        pf_handle* g = hs[k];
-        const long long last = h->h_sweep[k].s_last;
-        if (last >= s_begin) g->seg_done = last + 1;
-        if (k > 0) {                                            // the chunk's own stream continues after the sweep
-            hipEvent_t ev = next_sync_event(h);
-            hipEventRecord(ev, h->stream);
-            hipStreamWaitEvent(g->stream, ev, 0);
-        }
-    }
+    sweep_leave(hs, nh, s_begin);
     return 0;
 }
 
@@ -3810,28 +3796,12 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
 static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
     pf_handle* h = hs[0];
     if (s_begin >= s_end) return 0;
-    const int nb = h->nblocks, E = h->E;
+    const int nb = h->nblocks;
     const int nL_full = nb + h->ledger_wgs;
-    for (int k = 0; k < nh; ++k) {
-        pf_handle* g = hs[k];
-        if (g->ev_cnt) { hipStreamWaitEvent(h->stream, g->ev_cnt, 0); g->ev_cnt = nullptr; }
-        if (k > 0) {
-            hipEvent_t ev = next_sync_event(g);
-            hipEventRecord(ev, g->stream);
-            hipStreamWaitEvent(h->stream, ev, 0);
-        }
-    }
-    if (h->ev_x.empty()) {
-        std::vector<hipEvent_t> ev(32, nullptr);
-        bool ok = true;
-        for (auto& e : ev) if (ok && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { e = nullptr; ok = false; }
-        if (!ok) { for (auto e : ev) if (e) hipEventDestroy(e); g_err = "hipEventCreate failed"; return -1; }
-        h->ev_x.assign(ev.begin(), ev.begin() + 16); h->ev_blc.assign(ev.begin() + 16, ev.end());
-    }
+    sweep_join(hs, nh);
+    if (sweep_event_ring(h)) return -1;
     bool failed = false;
-    h->sweep_split2 = true;
-    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, &failed);
-    h->sweep_split2 = false;
+    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, 2, &failed);
     if (failed) return -1;
     if (steps == 0) return 0;
     hipEvent_t seeded = next_sync_event(h);
@@ -3864,13 +3834,8 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
             }
         }
         if (check_launch("k_sweep4 (extend, bookkeeping and draw roles)")) return -1;
-        int columns = 0;
-        for (int k = 0; k < nh; ++k)
-            if (s >= s_begin + 2 && s - 2 <= h->h_sweep[k].s_last && !hs[k]->no_count) columns = std::max(columns, E - W2[k].first);
-        bool any_lc = false;
-        for (int k = 0; k < nh; ++k) any_lc = any_lc || (s >= s_begin + 2 && s - 2 <= h->h_sweep[k].s_last && !hs[k]->no_count);
         const int W = h->h_sweep[0].workers;
-        pending_grid[(size_t)(t % batch)] = (unsigned)(1 + (W > 0 ? (any_lc ? W : 0) : nL_full + h->cw_off[columns]));
+        pending_grid[(size_t)(t % batch)] = (unsigned)(1 + sweep_lc_wgs(hs, nh, s_begin, s, W2.data(), nL_full));
         if (batch_end) {
             hipStreamWaitEvent(h->cstream, h->ev_x[(size_t)(t & 15)], 0);
             for (long long u = t - (t % batch); u <= t; ++u) {
@@ -3887,31 +3852,12 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
             if (check_launch("k_sweep_blc (ledger and count roles)")) return -1;
         }
         if ((t & 1023) == 1023) trim_spans(h);
-        for (int k = 0; k < nh; ++k) {
-            pf_handle* g = hs[k];
-            W2[k] = W1[k];
-            if (s <= h->h_sweep[k].s_last) {
-                W1[k] = host_windows(g, seg_pos(g, s), false);
-                g->step_windows = W1[k];
-                if (W1[k].first < E && !g->no_count) g->fin_pending = true;
-            } else {
-                W1[k] = no_windows(g);
-            }
-        }
+        sweep_advance_windows(hs, nh, s, W1.data(), W2.data());
     }
     h->k_launches[0] -= 2;                                      // flush steps are not rows
     // what follows on any chunk's stream waits for the last launch of the other roles
     hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((steps - 1) & 15)], 0);
-    for (int k = 0; k < nh; ++k) {
-        pf_handle* g = hs[k];
-        const long long last = h->h_sweep[k].s_last;
-        if (last >= s_begin) g->seg_done = last + 1;
-        if (k > 0) {
-            hipEvent_t ev = next_sync_event(h);
-            hipEventRecord(ev, h->stream);
-            hipStreamWaitEvent(g->stream, ev, 0);
-        }
-    }
+    sweep_leave(hs, nh, s_begin);
     return 0;
 }
 
@@ -3925,26 +3871,14 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
 // next row on the previous row's ledger upkeep are gone from the critical stream.
 static int run_sweep_mp(pf_handle* h, long long s_begin, long long s_end) {
     if (s_begin >= s_end) return 0;
-    const int nb = h->nblocks, E = h->E;
+    const int nb = h->nblocks;
     const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
     const int nL_full = nb + h->ledger_wgs;
-    if (h->ev_cnt) { hipStreamWaitEvent(h->stream, h->ev_cnt, 0); h->ev_cnt = nullptr; }
-    if (h->ev_x.empty()) {
-        // all thirty-two or none: a vector left half filled would pass for complete on the next call, and launches with null
-        // completion events lose the ordering between the two streams without a word
-        std::vector<hipEvent_t> ev(32, nullptr);
-        bool ok = true;
-        for (auto& e : ev) if (ok && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { e = nullptr; ok = false; }
-        if (!ok) {
-            for (auto e : ev) if (e) hipEventDestroy(e);
-            g_err = "hipEventCreate failed";
-            return -1;
-        }
-        h->ev_x.assign(ev.begin(), ev.begin() + 16); h->ev_blc.assign(ev.begin() + 16, ev.end());
-    }
     pf_handle* one[1] = {h};
+    sweep_join(one, 1);
+    if (sweep_event_ring(h)) return -1;
     bool failed = false;
-    const long long steps = sweep_table(one, 1, s_begin, s_end, nL_full, &failed);
+    const long long steps = sweep_table(one, 1, s_begin, s_end, nL_full, 0, &failed);
     if (failed) return -1;
     if (steps == 0) return 0;
     // the counting stream starts behind the table and the seed
@@ -3961,118 +3895,22 @@ static int run_sweep_mp(pf_handle* h, long long s_begin, long long s_end) {
         if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);
         {
             Timed tm(h, 0, timing_on(h, s));
-            if (h->P > 1) pf_mp_launch_sweep_x(h->A, h->d_sweep, t, h->smem_sweep_x, h->stream, h->ev_x[(size_t)(t & 15)]);
-            else {
-                // one population (PF_DEBUG_SPLIT_ROLES): k_sweep with a grid of the extend workgroups only
-                const dim3 gx((unsigned)(nb + (h->h_sweep[0].nT > 0 ? 1 + h->h_sweep[0].nT : 0)), 1u), bx(PF_BS);
-                hipEvent_t xdone = h->ev_x[(size_t)(t & 15)];
-#define PF_LAUNCH_X(NMV, BV, EV) hipExtLaunchKernelGGL((k_sweep<NMV, BV, EV, false>), gx, bx, h->smem_pipe, h->stream, nullptr, xdone, 0, h->d_sweep, t, nb)
-                if (h->n <= 4) { if (biased) { if (h->n == 4) PF_LAUNCH_X(4, true, true); else PF_LAUNCH_X(4, true, false); } else { if (h->n == 4) PF_LAUNCH_X(4, false, true); else PF_LAUNCH_X(4, false, false); } }
-                else { if (biased) { if (h->n == 8) PF_LAUNCH_X(8, true, true); else PF_LAUNCH_X(8, true, false); } else { if (h->n == 8) PF_LAUNCH_X(8, false, true); else PF_LAUNCH_X(8, false, false); } }
-#undef PF_LAUNCH_X
-            }
+            pf_mp_launch_sweep_x(h->A, h->d_sweep, t, h->smem_sweep_x, h->stream, h->ev_x[(size_t)(t & 15)]);
         }
-        if (check_launch("k_sweep (extend role)")) return -1;
+        if (check_launch("k_sweep_xmp")) return -1;
         hipStreamWaitEvent(h->cstream, t >= 1 ? h->ev_x[(size_t)((t - 1) & 15)] : seeded, 0);
-        const int columns = (s >= s_begin + 2 && s - 2 <= last && !h->no_count) ? E - W2.first : 0;
-        const int ncount = h->cw_off[columns];
-        const dim3 grid((unsigned)(1 + (h->h_sweep[0].workers > 0 ? ((s >= s_begin + 2 && s - 2 <= last && !h->no_count) ? h->h_sweep[0].workers : 0) : nL_full + ncount)), 1u), blk(PF_BS);
+        const dim3 grid((unsigned)(1 + sweep_lc_wgs(one, 1, s_begin, s, &W2, nL_full)), 1u), blk(PF_BS);
         hipEvent_t done = h->ev_blc[(size_t)(t & 15)];
 #define PF_LAUNCH_BLC(NMV, PV, BV) hipExtLaunchKernelGGL((k_sweep_blc<NMV, PV, BV>), grid, blk, h->smem_pipe, h->cstream, nullptr, done, 0, h->d_sweep, t)
-        if (h->P == 1) { if (h->n <= 4) { if (biased) PF_LAUNCH_BLC(4, 1, true); else PF_LAUNCH_BLC(4, 1, false); } else { if (biased) PF_LAUNCH_BLC(8, 1, true); else PF_LAUNCH_BLC(8, 1, false); } }
-        else if (h->P == 2) { if (biased) PF_LAUNCH_BLC(8, 2, true); else PF_LAUNCH_BLC(8, 2, false); }
+        if (h->P == 2) { if (biased) PF_LAUNCH_BLC(8, 2, true); else PF_LAUNCH_BLC(8, 2, false); }
         else { if (biased) PF_LAUNCH_BLC(8, PF_PMAX, true); else PF_LAUNCH_BLC(8, PF_PMAX, false); }
 #undef PF_LAUNCH_BLC
         if (check_launch("k_sweep_blc")) return -1;
         if ((t & 1023) == 1023) trim_spans(h);
-        W2 = W1;
-        if (s <= last) {
-            W1 = host_windows(h, seg_pos(h, s), false);
-            h->step_windows = W1;
-            if (W1.first < E && !h->no_count) h->fin_pending = true;
-        } else {
-            W1 = no_windows(h);
-        }
+        sweep_advance_windows(one, 1, s, &W1, &W2);
     }
     h->k_launches[0] -= 2;                                      // flush steps are not rows
     h->ev_cnt = h->ev_blc[(size_t)((steps - 1) & 15)];       // what follows on the filter stream waits for the last counts
-    if (last >= s_begin) h->seg_done = last + 1;
-    return 0;
-}
-
-// One population, rows handed over through memory (PF_DEBUG_FLAG_HANDOFF).  A row is two launches, as in the split arrangement of
-// run_sweep_mp -- k_sweep with the extend and draw roles, k_sweep_blc with bookkeeping, ledger and counts -- but no launch waits for
-// another launch to END: the extend / draw launches alternate between two streams, so that step t + 1 is dispatched while step t
-// still runs, and its workgroups wait in the kernel for the arrivals of step t's workgroups (Ctrl::xt_done; sweep_wait_ge); the
-// launches of the other roles follow one another on the counting stream and wait the same way for the extend launch they read
-// from; ring reuse (the extend launch of step t overwrites what the counts of step t - 14 read) is a wait on Ctrl::blc_step.  What
-// a row pays for the hand-off is then a release, an arrival and a poll (3.8 us for 157 wavefronts, pf_probe_handoff) instead of a
-// kernel boundary (5.4 us), and the count workgroups no longer share the launch of the extend workgroups.
-static int run_sweep_flags(pf_handle* h, long long s_begin, long long s_end) {
-    if (s_begin >= s_end) return 0;
-    const int nb = h->nblocks, E = h->E;
-    const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
-    const int nL_full = nb + h->ledger_wgs;
-    if (h->ev_cnt) { hipStreamWaitEvent(h->stream, h->ev_cnt, 0); h->ev_cnt = nullptr; }
-    pf_handle* one[1] = {h};
-    bool failed = false;
-    // (sweep_table uploads the chunk table and runs the seed on h->stream; the hand-off fields are set in the host copy first)
-    h->sweep_handoff = true;
-    const long long steps = sweep_table(one, 1, s_begin, s_end, nL_full, &failed);
-    h->sweep_handoff = false;
-    if (failed) return -1;
-    if (steps == 0) return 0;
-    if (h->ev_x.empty()) {
-        std::vector<hipEvent_t> ev(32, nullptr);
-        bool ok = true;
-        for (auto& e : ev) if (ok && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { e = nullptr; ok = false; }
-        if (!ok) { for (auto e : ev) if (e) hipEventDestroy(e); g_err = "hipEventCreate failed"; return -1; }
-        h->ev_x.assign(ev.begin(), ev.begin() + 16); h->ev_blc.assign(ev.begin() + 16, ev.end());
-    }
-    hipEvent_t seeded = next_sync_event(h);
-    hipEventRecord(seeded, h->stream);
-    hipStreamWaitEvent(h->stream2, seeded, 0);
-    hipStreamWaitEvent(h->cstream, seeded, 0);
-    const int nT = h->h_sweep[0].nT;
-    const dim3 gx((unsigned)(nb + (nT > 0 ? 1 + nT : 0)), 1u), bx(PF_BS);
-    Windows W1 = no_windows(h), W2 = W1;
-    const long long last = h->h_sweep[0].s_last;
-    for (long long t = 0; t < steps; ++t) {
-        const long long s = s_begin + t;
-        hipStream_t xs = (t & 1) ? h->stream2 : h->stream;
-        hipEvent_t xdone = h->ev_x[(size_t)(t & 15)];
-        {
-            Timed tm(h, 0, timing_on(h, s) && !(t & 1));
-#define PF_LAUNCH_XF(KERN) hipExtLaunchKernelGGL((KERN), gx, bx, h->smem_pipe, xs, nullptr, xdone, 0, h->d_sweep, t, nb)
-            if (h->n == 4) PF_LAUNCH_XF((k_sweep4h<true>)); else PF_LAUNCH_XF((k_sweep4h<false>));
-#undef PF_LAUNCH_XF
-        }
-        if (check_launch("k_sweep (extend role, flag hand-off)")) return -1;
-        // the other roles' launch of step t reads what the extend launch of step t - 1 wrote: ordered by that launch's completion
-        // signal on the counting stream (a queue-level wait: nothing spins; this stream is not the critical one)
-        if (t >= 1) hipStreamWaitEvent(h->cstream, h->ev_x[(size_t)((t - 1) & 15)], 0);
-        const int columns = (s >= s_begin + 2 && s - 2 <= last && !h->no_count) ? E - W2.first : 0;
-        const int ncount = h->cw_off[columns];
-        const dim3 grid((unsigned)(1 + (h->h_sweep[0].workers > 0 ? ((s >= s_begin + 2 && s - 2 <= last && !h->no_count) ? h->h_sweep[0].workers : 0) : nL_full + ncount)), 1u), blk(PF_BS);
-#define PF_LAUNCH_BLCF(NMV, BV) hipLaunchKernelGGL((k_sweep_blc<NMV, 1, BV>), grid, blk, h->smem_pipe, h->cstream, h->d_sweep, t)
-        if (h->n <= 4) { if (biased) PF_LAUNCH_BLCF(4, true); else PF_LAUNCH_BLCF(4, false); } else { if (biased) PF_LAUNCH_BLCF(8, true); else PF_LAUNCH_BLCF(8, false); }
-#undef PF_LAUNCH_BLCF
-        if (check_launch("k_sweep_blc (flag hand-off)")) return -1;
-        if ((t & 1023) == 1023) trim_spans(h);
-        W2 = W1;
-        if (s <= last) {
-            W1 = host_windows(h, seg_pos(h, s), false);
-            h->step_windows = W1;
-            if (W1.first < E && !h->no_count) h->fin_pending = true;
-        } else {
-            W1 = no_windows(h);
-        }
-    }
-    h->k_launches[0] -= 2;                                      // flush steps are not rows
-    // what follows on the filter stream waits for all three
-    hipEvent_t e2 = next_sync_event(h), ec = next_sync_event(h);
-    hipEventRecord(e2, h->stream2); hipEventRecord(ec, h->cstream);
-    hipStreamWaitEvent(h->stream, e2, 0); hipStreamWaitEvent(h->stream, ec, 0);
     if (last >= s_begin) h->seg_done = last + 1;
     return 0;
 }
@@ -4111,8 +3949,6 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end) {
     if (extend_can_fuse(h)) {
         if (!h->pipe || h->two_launch_rows) return run_single_stream(h, s_begin, s_end);
         if (h->use_k_pipe) return run_pipeline(h, s_begin, s_end);
-        if (h->flag_handoff) return run_sweep_flags(h, s_begin, s_end);
-        if (h->split_roles && !h->A.rec_trees) return run_sweep_mp(h, s_begin, s_end);
         pf_handle* one[1] = {h};
         if (h->split_many && !h->A.rec_trees) return run_sweep_split(one, 1, s_begin, s_end);
         return run_sweep(one, 1, s_begin, s_end);

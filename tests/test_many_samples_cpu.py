@@ -45,6 +45,31 @@ def test_header_declares_the_wide_path():
     assert pf.DEBUG_FORCE_WIDE == 2048 and pf.NSAM_MAX_WIDE == 64
 
 
+REMOVED_DEBUG_BITS = {"SPLIT_ROLES": 64, "COUNT_YOUNG_FIRST": 512, "CU_MASK": 1024, "FLAG_HANDOFF": 8192}
+
+
+def test_removed_launch_arrangements_are_gone_and_refused_by_name():
+    """The switches of the three launch arrangements that lost their A/B are neither declared nor used, and pf_create -- before it
+    touches a device -- refuses a debug value that still sets one of their bits, naming the bit."""
+    import ctypes as C
+    from smcsmc_amd import pf
+    sources = [os.path.join(ROOT, "include", "smcsmc_pf.h")]
+    for d, _, files in os.walk(os.path.join(ROOT, "smcsmc_amd")):
+        sources += [os.path.join(d, f) for f in files if f.endswith((".h", ".hpp", ".hip", ".cpp", ".py", "Makefile"))]
+    assert len(sources) > 20
+    for path in sources:
+        text = open(path, errors="replace").read()
+        for name in REMOVED_DEBUG_BITS:
+            assert name not in text, "%s still names %s" % (path, name)
+    L = pf.load_library()
+    model = pf._Model()
+    for bit in REMOVED_DEBUG_BITS.values():
+        for debug in (bit, bit | pf.DEBUG_NO_COUNT):
+            params = pf._Params(np=100, ess_fraction=0.5, seed=1, debug=debug)
+            assert L.pf_create(C.byref(model), C.byref(params), 0) is None
+            assert "debug bit %d " % bit in pf._err(L) and "removed" in pf._err(L), pf._err(L)
+
+
 # ---------------------------------------------------------------- the oracle states the same limits as the device path
 def test_oracle_accepts_64_haplotypes_with_one_population(oracle):
     import cases
