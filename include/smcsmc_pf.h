@@ -210,14 +210,20 @@ int pf_resample(pf_handle* h, int64_t s);
 /* the hot loop over segments [s_begin, s_end): update -> count -> resample per segment */
 int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
 /* the same loop for several chunks at once: rows [s_begin, s_end) of n_handles independent filters (one per chromosome
- * chunk; same device, particle count, haplotypes, epochs and options) step in lockstep through the same kernel launches, whose
+ * chunk; same device, particle count, haplotypes, epochs, populations and options) step in lockstep through the same kernel launches, whose
  * grids cover all of them (two per row for at most four haplotypes without focused sampling -- the extend roles; the ledger and
- * count roles on the counting stream -- one otherwise).  The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
- * every chunk's results are bit-identical to its own pf_run.  A chunk that runs out of rows simply stops. */
+ * count roles on the counting stream -- one otherwise).  Structured models with the tree in registers (two to four populations, at
+ * most 8 haplotypes, no look-ahead, no -arg) are taken too: one extend launch (k_sweep_xmp, grid = particle blocks x chunks) and one
+ * launch of the bookkeeping, ledger and count roles (k_sweep_blc) per row for all chunks; such chunks must also share mig_cap,
+ * piece_cap, delay_cap and the number of bias bands, and cannot be mixed with one-population chunks.
+ * The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
+ * every chunk's results are bit-identical to its own pf_run.  A chunk that runs out of rows simply stops and sits later calls out.
+ * Afterwards every handle's own stream continues behind the call: pf_run, pf_finish, pf_get_counts and the step API mix freely with it. */
 int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, int64_t s_end);
 /* 1 when pf_run_many would take these handles, 0 when the caller has to run them one after the other with pf_run (the row
- * pipeline does not apply to one of them -- several populations, more than 8 haplotypes, look-ahead, more than 131 072
- * particles -- or they differ in shape) */
+ * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure,
+ * more than 8 haplotypes, look-ahead, more than 131 072 particles, a debug path -- or they differ in shape or mix structured and
+ * one-population chunks) */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 int pf_finish(pf_handle* h);
 int pf_sync(pf_handle* h);

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -596,8 +597,12 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
     std::vector<std::vector<double>> mine(R, std::vector<double>((size_t)slots * LEN, 0.0));
     std::vector<std::vector<double>> all(R, std::vector<double>((size_t)R * slots * LEN, 0.0));
     std::vector<std::string> failure(R);
-    // the chunks of a rank go through one launch per row when the row pipeline applies to them (include/smcsmc_pf.h, pf_run_many)
+    // the chunks of a rank go through the same launches, row by row, when the row pipeline applies to them (include/smcsmc_pf.h, pf_run_many):
+    // one population, at most 8 haplotypes, no look-ahead (-arg never gets here: plan_chunks).  pf_can_run_many decides.  The library takes
+    // the chunks of a structured model too (pf_run_many), but this binary keeps filtering those one after the other
+    // until lockstep has been measured not slower than that at four chunks (section 7: not measured yet) -- npop == 1 below is the switch
     const bool lockstep = P.model.npop == 1 && P.model.nsam <= 8 && P.apf_level == 0;
+    std::mutex notes_lock;
     auto rank_main = [&](int r) {
         bool entered = false;
         try {
@@ -647,7 +652,16 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
                 }
                 std::vector<pf_handle*> hs;
                 for (ChunkFilter* F : group) hs.push_back(F->h);
-                if (group.size() > 1 && pf_can_run_many(hs.data(), (int32_t)hs.size())) {
+                const bool together = group.size() > 1 && pf_can_run_many(hs.data(), (int32_t)hs.size());
+                {
+                    std::ostringstream note;
+                    note << " rank " << r << ": chunks " << my_chunks[k0] << " to " << my_chunks[k1 - 1] << ": " << group.size()
+                         << (together ? " chunk(s) ran side by side" : " chunk(s) ran one after the other");
+                    std::lock_guard<std::mutex> hold(notes_lock);
+                    clog << note.str() << endl;
+                    P.chunk_notes.push_back(note.str());
+                }
+                if (together) {
                     run_filters(group, r == 0);
                 } else {
                     for (ChunkFilter* F : group) { std::vector<ChunkFilter*> one{F}; run_filters(one, r == 0); }

@@ -606,6 +606,7 @@ int PfParam::log() {   // pfparam.cpp:392-400
     if (write_log_file) {
         ofstream f(log_path.c_str(), ios::out | ios::app | ios::binary);
         write_log_text(&f);
+        for (const std::string& ln : chunk_notes) f << ln << "\n";
     }
     write_log_text(&std::cout);
     return 0;

@@ -209,6 +209,7 @@ class PfParam {
     bool record_all = false;                         // -record_all: no recording limit far from data
     int mig_cap = 0;                                 // -migcap: pf_params.mig_cap (0 = the library's default)
     int delay_cap = 0;                               // -delaycap: pf_params.delay_cap (0 = the library's default)
+    std::vector<std::string> chunk_notes;            // -chunks: one line per group of a rank's chunks, how they ran (written to the .log)
     long long log_cap = 0;                           // -log_cap: pf_params.log_cap (0 = the library's default; -arg sizes its own)
     int count_wgs = 0;                               // -count_wgs: pf_params.count_wgs (0 = chosen here: the library's default, or tapered columns with six or more chunks per device)
     bool delay_evict = false;                        // -delay_evict: pf_params.flags bit 2

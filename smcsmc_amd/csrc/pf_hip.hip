@@ -3622,7 +3622,10 @@ static bool sweep_compatible(const pf_handle* a, const pf_handle* b) {
     const bool ba = a->A.n_bias > 0 || a->A.g_K > 0, bb = b->A.n_bias > 0 || b->A.g_K > 0;
     return a->device == b->device && a->Np == b->Np && a->n == b->n && a->E == b->E && a->P == b->P && ba == bb &&
            a->A.rec_trees == b->A.rec_trees && a->ncw == b->ncw && a->workers == b->workers && a->ledger_wgs == b->ledger_wgs && a->split_many == b->split_many && a->cw_off == b->cw_off && a->smem_pipe == b->smem_pipe && a->no_count == b->no_count &&
-           (a->A.dt_tab != nullptr) == (b->A.dt_tab != nullptr);
+           (a->A.dt_tab != nullptr) == (b->A.dt_tab != nullptr) &&
+           // structured models: what the two launches of a step take from the leader (the extend launch's LDS and, through it, the capacities)
+           a->pipe_mp == b->pipe_mp &&
+           (!a->pipe_mp || (a->smem_sweep_x == b->smem_sweep_x && a->A.mcap == b->A.mcap && a->A.pcap == b->A.pcap && a->A.dcap == b->A.dcap && a->A.n_bias == b->A.n_bias));
 }
 
 // the per-chunk table of a k_sweep call in the leader's device buffer; returns the number of steps (0: nothing to do)
@@ -3861,31 +3864,34 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
     return 0;
 }
 
-// Structured models (register-tree kernel) on the row pipeline.  Per step two launches: the extend role (k_sweep_xmp, with the
-// decision on the previous row in its prologue) on the filter stream, the bookkeeping / ledger / count roles (k_sweep_blc) on
-// the counting stream -- separate launches because the extend workgroups' LDS (their trees' migration events) would be
+// Structured models (register-tree kernel) on the row pipeline, one chunk or several in lockstep.  Per step two launches for all
+// of them: the extend role (k_sweep_xmp, with the decision on the previous row in its prologue; grid = particle blocks x chunks) on
+// the leader's filter stream, the bookkeeping / ledger / count roles (k_sweep_blc, grid = workgroups per chunk x chunks) on the
+// leader's counting stream -- separate launches because the extend workgroups' LDS (their trees' migration events) would be
 // allocated to every count workgroup too.  Step t's second launch needs the extend launch of step t - 1 (partials, offspring
 // table, records), the extend launch of step t must not overwrite ring slot t & (PF_RING - 1) before the counts of step t - 2 are done:
 // one wait each way per step, on the kernels' own completion signals; the extend role does not read anything the other
 // launch writes (it keeps its own note of n_resample / generation, Ctrl::xr).  k_decide, its boundary and the wait of the
-// next row on the previous row's ledger upkeep are gone from the critical stream.
-static int run_sweep_mp(pf_handle* h, long long s_begin, long long s_end) {
+// next row on the previous row's ledger upkeep are gone from the critical stream.  A chunk never reads another chunk's memory and
+// takes nothing from the launch geometry but its own blockIdx.x: every chunk is bit-identical to its own pf_run
+// (tests/test_gpu_sweep_structured.py).
+static int run_sweep_mp(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
+    pf_handle* h = hs[0];
     if (s_begin >= s_end) return 0;
     const int nb = h->nblocks;
     const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
     const int nL_full = nb + h->ledger_wgs;
-    pf_handle* one[1] = {h};
-    sweep_join(one, 1);
+    sweep_join(hs, nh);
     if (sweep_event_ring(h)) return -1;
     bool failed = false;
-    const long long steps = sweep_table(one, 1, s_begin, s_end, nL_full, 0, &failed);
+    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, 0, &failed);
     if (failed) return -1;
     if (steps == 0) return 0;
     // the counting stream starts behind the table and the seed
     hipEvent_t seeded = next_sync_event(h);
     hipEventRecord(seeded, h->stream);
-    Windows W1 = no_windows(h), W2 = W1;
-    const long long last = h->h_sweep[0].s_last;
+    std::vector<Windows> W1((size_t)nh), W2((size_t)nh);
+    for (int k = 0; k < nh; ++k) { W1[k] = no_windows(hs[k]); W2[k] = W1[k]; }
     for (long long t = 0; t < steps; ++t) {
         const long long s = s_begin + t;
         // ring slot reuse: the extend launch of step t overwrites the slot of row t - PF_RING, which the counts read in step
@@ -3895,11 +3901,11 @@ static int run_sweep_mp(pf_handle* h, long long s_begin, long long s_end) {
         if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);
         {
             Timed tm(h, 0, timing_on(h, s));
-            pf_mp_launch_sweep_x(h->A, h->d_sweep, t, h->smem_sweep_x, h->stream, h->ev_x[(size_t)(t & 15)]);
+            pf_mp_launch_sweep_x(h->A, h->d_sweep, nh, t, h->smem_sweep_x, h->stream, h->ev_x[(size_t)(t & 15)]);
         }
         if (check_launch("k_sweep_xmp")) return -1;
         hipStreamWaitEvent(h->cstream, t >= 1 ? h->ev_x[(size_t)((t - 1) & 15)] : seeded, 0);
-        const dim3 grid((unsigned)(1 + sweep_lc_wgs(one, 1, s_begin, s, &W2, nL_full)), 1u), blk(PF_BS);
+        const dim3 grid((unsigned)(1 + sweep_lc_wgs(hs, nh, s_begin, s, W2.data(), nL_full)), (unsigned)nh), blk(PF_BS);
         hipEvent_t done = h->ev_blc[(size_t)(t & 15)];
 #define PF_LAUNCH_BLC(NMV, PV, BV) hipExtLaunchKernelGGL((k_sweep_blc<NMV, PV, BV>), grid, blk, h->smem_pipe, h->cstream, nullptr, done, 0, h->d_sweep, t)
         if (h->P == 2) { if (biased) PF_LAUNCH_BLC(8, 2, true); else PF_LAUNCH_BLC(8, 2, false); }
@@ -3907,11 +3913,12 @@ static int run_sweep_mp(pf_handle* h, long long s_begin, long long s_end) {
 #undef PF_LAUNCH_BLC
         if (check_launch("k_sweep_blc")) return -1;
         if ((t & 1023) == 1023) trim_spans(h);
-        sweep_advance_windows(one, 1, s, &W1, &W2);
+        sweep_advance_windows(hs, nh, s, W1.data(), W2.data());
     }
     h->k_launches[0] -= 2;                                      // flush steps are not rows
-    h->ev_cnt = h->ev_blc[(size_t)((steps - 1) & 15)];       // what follows on the filter stream waits for the last counts
-    if (last >= s_begin) h->seg_done = last + 1;
+    // what follows on any chunk's stream waits for the last launch of the other roles
+    hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((steps - 1) & 15)], 0);
+    sweep_leave(hs, nh, s_begin);
     return 0;
 }
 
@@ -3922,8 +3929,11 @@ static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles
     for (int k = 0; k < n_handles; ++k) {
         pf_handle* g = handles[k];
         if (!g) return "pf_run_many: null handle";
-        if (!(extend_can_fuse(g) && g->pipe && !g->two_launch_rows))
-            return "pf_run_many: the chunks must run on the single-launch row pipeline (one population, at most 8 haplotypes, no look-ahead)";
+        const bool one_pop = extend_can_fuse(g) && g->pipe && !g->two_launch_rows;
+        const bool structured = g->pipe_mp && g->A.apf == 0 && !g->force_lds && !g->no_fuse;
+        if (!one_pop && !structured)
+            return "pf_run_many: the chunks must run on the row pipeline (one population, or a structured model of two to four populations with "
+                   "the tree in registers; at most 8 haplotypes, no look-ahead, no -arg)";
         if (!sweep_compatible(h, g)) return "pf_run_many: the chunks must share device, particle count, haplotypes, epochs and options";
         for (int j = 0; j < k; ++j) if (handles[j] == g) return "pf_run_many: a handle appears twice";
     }
@@ -3939,6 +3949,7 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
     pf_handle* h = handles[0];
     HIPCHK(hipSetDevice(h->device));
     if (s_begin < 0) { g_err = "segment range out of bounds"; return -1; }        // a chunk with fewer rows sits the call out
+    if (h->pipe_mp) return run_sweep_mp(handles, n_handles, s_begin, s_end);
     if (h->split_many && !h->A.rec_trees) return run_sweep_split(handles, n_handles, s_begin, s_end);
     return run_sweep(handles, n_handles, s_begin, s_end);
 }
@@ -3953,7 +3964,7 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end) {
         if (h->split_many && !h->A.rec_trees) return run_sweep_split(one, 1, s_begin, s_end);
         return run_sweep(one, 1, s_begin, s_end);
     }
-    if (h->pipe_mp && h->A.apf == 0 && !h->force_lds && !h->no_fuse) return run_sweep_mp(h, s_begin, s_end);
+    if (h->pipe_mp && h->A.apf == 0 && !h->force_lds && !h->no_fuse) { pf_handle* one[1] = {h}; return run_sweep_mp(one, 1, s_begin, s_end); }
     // structured models on the register-tree kernel: the next row's extend completes this row while it loads (two
     // launches per row on the main stream instead of three); the last row of the call is completed by k_resample
     const bool mp_fuse = h->P > 1 && pf_mp_can_fuse(h->A, h->force_lds) && h->A.apf == 0 && !h->no_fuse;

@@ -1052,8 +1052,9 @@ __global__ __launch_bounds__(64 * (64 / LA)) void k_extend_mpr(KArgs A, long lon
     extend_mpr_body<NM, BIASED, LA, TREES, false>(A, s, fuse);
 }
 
-// the extend role of the row pipeline for structured models: step t of the chunk table (pf_pipe.h; one chunk per launch
-// for now), the bookkeeping / ledger / count roles of the step run as their own launch on the counting stream (pf_hip.hip)
+// the extend role of the row pipeline for structured models: step t of the chunk table (pf_pipe.h; blockIdx.y is the chunk,
+// a chunk that is finished or sits the call out leaves before it touches LDS or memory other than its table entry), the
+// bookkeeping / ledger / count roles of the step run as their own launch on the counting stream (pf_hip.hip)
 template <int NM, bool BIASED, int LA, bool TREES>
 __global__ __launch_bounds__(64 * (64 / LA)) void k_sweep_xmp(const SweepChunk* tab_g, long long t) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
@@ -1242,9 +1243,9 @@ int pf_mp_sweep_prepare(size_t smem) {
     if (hipFuncSetAttribute((const void*)k_sweep_xmp<8, true, PF_MPR_LANES_BIASED, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
     return 0;
 }
-void pf_mp_launch_sweep_x(const KArgs& A, const SweepChunk* tab, long long t, size_t smem, hipStream_t st, hipEvent_t done) {
+void pf_mp_launch_sweep_x(const KArgs& A, const SweepChunk* tab, int nchunks, long long t, size_t smem, hipStream_t st, hipEvent_t done) {
     const bool biased = A.n_bias > 0 || A.g_K > 0;
-    const dim3 grid(mp_blocks(A.Np)), blk(64 * (64 / (biased ? PF_MPR_LANES_BIASED : PF_MPR_LANES_PLAIN)));
+    const dim3 grid(mp_blocks(A.Np), (unsigned)nchunks), blk(64 * (64 / (biased ? PF_MPR_LANES_BIASED : PF_MPR_LANES_PLAIN)));
     if (biased) hipExtLaunchKernelGGL((k_sweep_xmp<8, true, PF_MPR_LANES_BIASED, false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
     else hipExtLaunchKernelGGL((k_sweep_xmp<8, false, PF_MPR_LANES_PLAIN, false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
 }

@@ -19,7 +19,7 @@ bool pf_mp_can_fuse(const KArgs& A, bool lds_tree);
 struct SweepChunk;
 size_t pf_mp_sweep_smem_bytes(int E, int P, int mcap, int nc);
 int pf_mp_sweep_prepare(size_t smem);
-void pf_mp_launch_sweep_x(const KArgs& A, const SweepChunk* tab, long long t, size_t smem, hipStream_t st, hipEvent_t done);
+void pf_mp_launch_sweep_x(const KArgs& A, const SweepChunk* tab, int nchunks, long long t, size_t smem, hipStream_t st, hipEvent_t done);
 void pf_mp_launch_calibrate(const KArgs& A, unsigned long long seed, long long rep0, long long nrep, int* out_epoch,
                             double* out_dist, int* out_err, size_t smem, hipStream_t st);
 void pf_mp_launch_tbl(const KArgs& A, unsigned long long seed, long long nrep, double* out_h, double* out_len, int* out_err,

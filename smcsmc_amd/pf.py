@@ -344,12 +344,23 @@ class ParticleFilter:
 
     @staticmethod
     def run_many(filters, s_begin=0, s_end=None):
-        """Rows [s_begin, s_end) of several chunks (filters on one device, same shape) in lockstep: one launch per row
-        covers all of them (pf_run_many).  A chunk with fewer rows stops at its end."""
+        """Rows [s_begin, s_end) of several chunks (filters on one device, same shape and options) in lockstep: the launches
+        of a row cover all of them (pf_run_many).  One-population chunks of at most 8 haplotypes, or chunks of a structured model
+        (two to four populations, at most 8 haplotypes: one extend launch and one launch of the other roles per row for all
+        chunks); no look-ahead, no tree recording with structure.  A chunk with fewer rows stops at its end and sits later
+        calls out.  Every chunk gets the bits of its own run().  Raises PfError for a group can_run_many() refuses."""
         if s_end is None:
             s_end = max(f.n_segs for f in filters)
         hs = (C.c_void_p * len(filters))(*[f.h for f in filters])
         filters[0]._chk(filters[0].L.pf_run_many(hs, len(filters), int(s_begin), int(s_end)))
+
+    @staticmethod
+    def can_run_many(filters):
+        """True when run_many would take these filters (pf_can_run_many); otherwise run them one after the other with run()."""
+        if not filters:
+            return False
+        hs = (C.c_void_p * len(filters))(*[f.h for f in filters])
+        return bool(filters[0].L.pf_can_run_many(hs, len(filters)))
 
     def update_segment(self, s):
         self._chk(self.L.pf_update_segment(self.h, int(s)))
