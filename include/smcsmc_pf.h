@@ -39,7 +39,7 @@ extern "C" {
 typedef struct pf_model {
     int32_t n_epochs;            /* E  (Model::change_times_.size()) */
     int32_t n_pops;              /* P  (1..4; scrm -I) */
-    int32_t nsam;                /* haplotypes n: 2..64 with one population (beyond 16 without -arg and -apf), 2..16 with several */
+    int32_t nsam;                /* haplotypes n: 2..64 with one population (beyond 16 without -arg and -apf), 2..16 with several (-arg included) */
     int32_t flags;               /* bit0 -ancestral_aware, bit1 -dephase (pfparam.cpp:143-146) */
     double loci_length;          /* Model::loci_length() */
     double mutation_rate;        /* per bp per generation */
@@ -192,7 +192,8 @@ int64_t pf_sample_tree_events(pf_handle* h, int32_t* kind, double* pos, double* 
  * -1 for R), to_pop = destination of a migration (M lines, kind 2; -1 otherwise).  With several populations an update
  * yields R, C and then the migrations of the two active lineages of the walk that led to the coalescence, latest first
  * (particle.cpp:292-298; samples: those of the floating lineage, or everything else for the root's own lineage).
- * Structured models need nsam <= 8 for -arg. */
+ * Structured models record trees at every nsam they take (2..16): on the register-tree row kernel up to 8 haplotypes, on the
+ * LDS-tree row kernel k_extend_mp<BIASED, TREES> from 9 to 16 (and below with PF_DEBUG_FORCE_LDS); the two give the same dump. */
 int64_t pf_sample_tree_events_pops(pf_handle* h, int32_t* kind, double* pos, double* height, uint32_t* desc, int32_t* from_pop,
                                    int32_t* to_pop, int64_t max_events, int64_t* particle_out);
 
@@ -221,7 +222,8 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * Afterwards every handle's own stream continues behind the call: pf_run, pf_finish, pf_get_counts and the step API mix freely with it. */
 int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, int64_t s_end);
 /* 1 when pf_run_many would take these handles, 0 when the caller has to run them one after the other with pf_run (the row
- * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure,
+ * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure
+ * (at any number of haplotypes: such handles run on the general path, row kernel -> k_decide -> k_resample),
  * more than 8 haplotypes, look-ahead, more than 131 072 particles, a debug path -- or they differ in shape or mix structured and
  * one-population chunks) */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);

@@ -269,7 +269,6 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
     pp.count_wgs = job ? job->count_wgs : P.count_wgs;
     if (P.delay_evict) pp.flags |= 4;
     if (P.record_trees) {
-        if (NP > 1 && M.nsam > 8) throw Unsupported("-arg with more than one population and more than 8 samples");
         pp.flags |= 2;     // -arg (pfparam.cpp:353-357)
         // nothing may be overwritten while the history is needed: a slot appends about 0.6 records per row for its
         // recombinations and up to one per resampling, and there are at most as many generations as rows
@@ -277,7 +276,9 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
         // (recombinations per row grow with the tree length: the figure above is for four samples)
         const long long log_cap = pow2_at_least(1.4 * (double)start.size() * std::max(1.0, (M.nsam - 1) / 3.0));
         const long long gen_cap = pow2_at_least((double)start.size() + 2.0);
-        const double gib = ((double)P.particles * (double)log_cap * (5.0 + M.nsam - 1) * 8.0 + (double)gen_cap * (double)P.particles * 20.0) / (1024.0 * 1024.0 * 1024.0);
+        // (structured models: plus the piece ring, four pieces of three words per record by default -- pf_params.piece_cap)
+        const double piece_bytes = NP > 1 ? (double)P.particles * 4.0 * (double)log_cap * 3.0 * 8.0 : 0.0;
+        const double gib = ((double)P.particles * (double)log_cap * (5.0 + M.nsam - 1) * 8.0 + piece_bytes + (double)gen_cap * (double)P.particles * 20.0) / (1024.0 * 1024.0 * 1024.0);
         clog << " -arg: event log of " << log_cap << " records per particle, " << gen_cap << " generations (" << fixed << setprecision(1)
              << gib << " GiB)" << setprecision(6) << scientific << endl;
         pp.log_cap = log_cap;

@@ -2818,11 +2818,9 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     h->smem = P > 1 ? pf_mp_smem_bytes(n, E, P, mcap) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
     h->max_trace_events = std::max(0, p->max_trace_events);
     if (p->flags & 2) {
-        // -arg: the parent table of every resampling is kept (it is the ancestry the tree dump walks back through)
-        if (P > 1 && (n > 8 || (p->debug & PF_DEBUG_FORCE_LDS))) {
-            delete h;
-            return fail("pf_create: tree recording (-arg) with several populations needs nsam <= 8 (register-tree kernel)");
-        }
+        // -arg: the parent table of every resampling is kept (it is the ancestry the tree dump walks back through).
+        // Structured models record trees on either row kernel: the register tree (nsam <= 8) or the LDS tree (any nsam
+        // they take, i.e. up to 16 -- the width of the descendant sets in a record -- and PF_DEBUG_FORCE_LDS).
         if (gen_cap > 0x7fffffffLL / 2) gen_cap = 0x7fffffffLL / 2;
         h->max_trace_events = (int)gen_cap;
     }

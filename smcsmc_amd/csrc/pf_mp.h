@@ -190,9 +190,10 @@ __device__ __forceinline__ void mp_insert_node(Lane& ln, MLane& ml, int ni, doub
 // Lineages in population `pop` crossing time tc, enumerated in the canonical order of the tree WITHOUT its node of
 // rank rp (rp < 0: nothing removed): rows ascending, child 0 then 1, the removed node's parent slot standing for
 // the sibling lineage (below the removed node) or the removed node's own branch (above it).  Populations are read
-// from Bp as the walk left them at tc.  Returns the count; the want-th slot is returned in pruned-tree coordinates.
+// from Bp as the walk left them at tc.  Returns the count; the want-th slot is returned in pruned-tree coordinates
+// (and, in *eff_out, the node id of its lineage in the tree as it stands, before the removal).
 __device__ __forceinline__ int mp_slots_at(const Lane& ln, const MLane& ml, int ni, int rp, double tc, int pop, int s_id,
-                                           double Sp, int want, int* pr, int* ps) {
+                                           double Sp, int want, int* pr, int* ps, int* eff_out = nullptr) {
     const int n = ln.n;
     const int pid = rp >= 0 ? n + rp : -1;
     int cnt = 0;
@@ -209,7 +210,7 @@ __device__ __forceinline__ int mp_slots_at(const Lane& ln, const MLane& ml, int 
                 crossing = node_h(ln, id) <= tc;
             }
             if (crossing && LBp(ml, eff) == pop) {
-                if (cnt == want) { *pr = r - ((rp >= 0 && r > rp) ? 1 : 0); *ps = s; }
+                if (cnt == want) { *pr = r - ((rp >= 0 && r > rp) ? 1 : 0); *ps = s; if (eff_out) *eff_out = eff; }
                 ++cnt;
             }
         }
@@ -512,10 +513,13 @@ __device__ __forceinline__ void mp_build_initial_tree(Lane& ln, MLane& ml, PLog&
 }
 
 // the part of a genealogy update after the recombination point (slot (rp,sb), height h) has been sampled
-template <bool LOG>
+// TREES (-arg): *span_out receives, instead of the epoch span of the pieces, the samples below the node the update
+// creates -- the cut samples `cut` plus those below the lineage it lands on (masks of the tree before the cut), all of
+// them above the root, its own only when it falls back into its branch; `tmp` = n-1 doubles of per-lane LDS scratch
+template <bool LOG, bool TREES = false>
 __device__ __forceinline__ void mp_genealogy_rest(Lane& ln, MLane& ml, PLog& pl, int limit, int rp, int sb, double h,
                                                   double* tc_out, double* sp_out, bool* changed_out, double* tfirst_out = nullptr,
-                                                  unsigned* span_out = nullptr) {
+                                                  unsigned* span_out = nullptr, unsigned cut = 0, double* tmp = nullptr) {
     const int n = ln.n;
     MP_TICK(tg0);
     int b_id = LC(ln, rp, sb), s_id = LC(ln, rp, 1 - sb);
@@ -528,7 +532,7 @@ __device__ __forceinline__ void mp_genealogy_rest(Lane& ln, MLane& ml, PLog& pl,
     const double tc = W.tc;
     *tc_out = tc;
     if (tfirst_out) *tfirst_out = W.tfirst;
-    if (span_out) *span_out = piece_span(W.e0, W.e1);
+    if (!TREES && span_out) *span_out = piece_span(W.e0, W.e1);
     const double Sp = LS(ln, rp);
     *sp_out = Sp;
     *changed_out = true;
@@ -546,7 +550,14 @@ __device__ __forceinline__ void mp_genealogy_rest(Lane& ln, MLane& ml, PLog& pl,
     if (k != W.weight || k < 1) { if (!ml.err) ml.err = 2; return; }
     const double u = uni(ln);
     const int idx = min((int)(u * (double)k), k - 1);
-    if (idx < nslots) mp_slots_at(ln, ml, n - 1, rp, tc, W.pf, s_id, Sp, idx, &pr, &ps);
+    int eff = 0;
+    if (idx < nslots) mp_slots_at(ln, ml, n - 1, rp, tc, W.pf, s_id, Sp, idx, &pr, &ps, TREES ? &eff : nullptr);
+    if (TREES) {
+        unsigned dn = cut;
+        if (idx < nslots) dn |= lane_desc_mask(ln, eff, tmp);
+        else if (has_root && idx == nslots) dn = (1u << n) - 1u;
+        *span_out = dn;
+    }
     *changed_out = !(has_stub && idx == k - 1);
     // ---- the edit.  Tree: remove p, insert the re-attachment node (one insertion for all three outcomes: slot,
     // root lineage, back into the stub).  Event list: everything that the separate steps (tag the stub, relabel for

@@ -140,7 +140,9 @@ __global__ __launch_bounds__(PF_BS) void k_init_mp(KArgs A, double initial_posit
 }
 
 // BIASED = false: no focused sampling and no guide; their code is compiled out
-template <bool BIASED>
+// TREES (-arg): every record carries the samples below the cut branch and below the node the update creates (where the
+// other instances store the epoch span of the record's pieces), and neither the record ring nor the piece ring may wrap
+template <bool BIASED, bool TREES = false>
 __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
     extern __shared__ double smem[];
     Smem m = carve(smem, A.n, A.E);
@@ -260,13 +262,13 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
                                         &iw, &rbiw, tmp0);
                 else if (biased) { sample_point_biased(ln, sBH, sBS, A.n_bias + 1, &rp, &sb, &h, &iw); rbiw = iw; }
                 else sample_point(ln, &rp, &sb, &h);
-                const unsigned desc = A.lmap_opp ? lane_desc_mask(ln, LC(ln, rp, sb), tmp0) : 0u;
+                const unsigned desc = (TREES || A.lmap_opp) ? lane_desc_mask(ln, LC(ln, rp, sb), tmp0) : 0u;
                 unsigned p0 = pl.idx;
                 double tfirst = 0.0;
                 MP_TICK(tu1);
                 MP_ACC(ml, 8, tu0, tu1);
                 unsigned span = 0;
-                mp_genealogy_rest<true>(ln, ml, pl, limit, rp, sb, h, &tc, &sp_removed, &changed, &tfirst, &span);
+                mp_genealogy_rest<true, TREES>(ln, ml, pl, limit, rp, sb, h, &tc, &sp_removed, &changed, &tfirst, &span, desc, tmp0);
                 if (ln.vbc) { w_post *= ln.upd_fac; w_pilot *= ln.upd_fac; ln.upd_fac = 1.0; }
                 rec[2] = h;
                 rec[3] = piece_ref(p0, pl.idx - p0);
@@ -373,6 +375,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
         A.ebuf[p] = ln.ebuf;
         A.widx[p] = widx;
         A.pidx[p] = pl.idx;
+        if (TREES && (widx >= A.cap || pl.idx >= A.pcap)) A.ctrl->err = ERR_LOG_OVERFLOW;       // -arg keeps every record and piece
         for (int r = 0; r < n - 1; ++r) A.snap_S[A.sp][(size_t)r * A.Np + p] = LS(ln, r);
         A.snap_w[A.sp][p] = w_post; A.snap_xm[A.sp][p] = x_mark; A.snap_ml[A.sp][p] = mark_limit; A.snap_widx[A.sp][p] = widx;
         MP_TICK(tk_stored);
@@ -1222,6 +1225,8 @@ int pf_mp_prepare(size_t smem, int mcap) {
     if (smem > 64 * 1024) {
         if (hipFuncSetAttribute((const void*)k_extend_mp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_extend_mp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_extend_mp<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_extend_mp<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_init_mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_calibrate_mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_tbl_mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
@@ -1265,10 +1270,12 @@ void pf_mp_launch_extend(const KArgs& A, long long s, size_t smem, hipStream_t s
         else hipLaunchKernelGGL((k_extend_mpr<8, false, PF_MPR_LANES_PLAIN, false>), grid, blk, sm, st, A, s, fuse);
         return;
     }
-    if (A.n_bias > 0 || A.g_K > 0)
-        hipLaunchKernelGGL(k_extend_mp<true>, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, s);
-    else
-        hipLaunchKernelGGL(k_extend_mp<false>, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, s);
+    const bool biased = A.n_bias > 0 || A.g_K > 0;
+    const dim3 grid(mp_blocks(A.Np)), blk(PF_BS);
+    if (biased && A.rec_trees) hipLaunchKernelGGL((k_extend_mp<true, true>), grid, blk, smem, st, A, s);
+    else if (biased) hipLaunchKernelGGL(k_extend_mp<true>, grid, blk, smem, st, A, s);
+    else if (A.rec_trees) hipLaunchKernelGGL((k_extend_mp<false, true>), grid, blk, smem, st, A, s);
+    else hipLaunchKernelGGL(k_extend_mp<false>, grid, blk, smem, st, A, s);
 }
 void pf_mp_launch_calibrate(const KArgs& A, unsigned long long seed, long long rep0, long long nrep, int* out_epoch,
                             double* out_dist, int* out_err, size_t smem, hipStream_t st) {
