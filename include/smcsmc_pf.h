@@ -97,7 +97,9 @@ typedef struct pf_params {
                                   * any tree is a reported error ("too many migration events on one local tree"). */
     int32_t count_wgs;           /* row pipeline: workgroups per epoch that share the lagged counting of a row (0 = one
                                   * per 256 particles, which is also the most).  The sums are grouped by workgroup, so the value is part
-                                  * of what makes two runs bit-identical. */
+                                  * of what makes two runs bit-identical.  One population with 9 to 16 haplotypes, where pf_run, pf_finish
+                                  * and the step API count on the general kernels and only pf_run_many on the row pipeline: a value > 0 sets
+                                  * the same column widths for both, so a chunk is grouped alike whichever call filters it. */
     int32_t delay_cap;           /* focused sampling / guide: delayed importance factors a particle may have pending (0 = 128).  The
                                   * reference keeps them in an unbounded heap (particle.hpp:59-101, 248); here the store is a column of
                                   * delay_cap entries per particle in device memory.  One factor too many is a reported error
@@ -217,6 +219,12 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * most 8 haplotypes, no look-ahead, no -arg) are taken too: one extend launch (k_sweep_xmp, grid = particle blocks x chunks) and one
  * launch of the bookkeeping, ledger and count roles (k_sweep_blc) per row for all chunks; such chunks must also share mig_cap,
  * piece_cap, delay_cap and the number of bias bands, and cannot be mixed with one-population chunks.
+ * One population with 9 to 16 haplotypes (the tree in per-lane LDS columns; no look-ahead, no -arg, at most 131 072 particles, no debug
+ * switch that selects a path) is taken the same way: one extend launch (k_sweep_xl, 256 particles per workgroup x chunks) and one
+ * launch of the other roles (k_sweep_blc<16, 1, *>) per row for all chunks.  Such chunks must have the same number of haplotypes (the
+ * width of the tree columns is the launch's LDS size: 12 does not run with 16, nor either with 8 or fewer), delay_cap and bias bands.
+ * pf_run on ONE such handle keeps the general kernels (k_extend -> k_decide -> k_resample); nobody has measured one chunk on the pipeline.
+ * Not taken: structured models above 8 haplotypes, -arg and the look-ahead above 8 haplotypes, more than 16 haplotypes (the wide kernels).
  * The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
  * every chunk's results are bit-identical to its own pf_run.  A chunk that runs out of rows simply stops and sits later calls out.
  * Afterwards every handle's own stream continues behind the call: pf_run, pf_finish, pf_get_counts and the step API mix freely with it. */
@@ -224,8 +232,8 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
 /* 1 when pf_run_many would take these handles, 0 when the caller has to run them one after the other with pf_run (the row
  * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure
  * (at any number of haplotypes: such handles run on the general path, row kernel -> k_decide -> k_resample),
- * more than 8 haplotypes, look-ahead, more than 131 072 particles, a debug path -- or they differ in shape or mix structured and
- * one-population chunks) */
+ * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path -- or they
+ * differ in shape: haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks) */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 int pf_finish(pf_handle* h);
 int pf_sync(pf_handle* h);

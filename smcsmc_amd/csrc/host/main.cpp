@@ -599,10 +599,11 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
     std::vector<std::vector<double>> all(R, std::vector<double>((size_t)R * slots * LEN, 0.0));
     std::vector<std::string> failure(R);
     // the chunks of a rank go through the same launches, row by row, when the row pipeline applies to them (include/smcsmc_pf.h, pf_run_many):
-    // one population, at most 8 haplotypes, no look-ahead (-arg never gets here: plan_chunks).  pf_can_run_many decides.  The library takes
+    // one population, at most 16 haplotypes (above 8 on the LDS tree: k_sweep_xl), no look-ahead (-arg never gets here: plan_chunks).
+    // pf_can_run_many decides.  The library takes
     // the chunks of a structured model too (pf_run_many), but this binary keeps filtering those one after the other
     // until lockstep has been measured not slower than that at four chunks (section 7: not measured yet) -- npop == 1 below is the switch
-    const bool lockstep = P.model.npop == 1 && P.model.nsam <= 8 && P.apf_level == 0;
+    const bool lockstep = P.model.npop == 1 && P.model.nsam <= 16 && P.apf_level == 0;
     std::mutex notes_lock;
     auto rank_main = [&](int r) {
         bool entered = false;
@@ -628,13 +629,14 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
                 // Six or more chunks side by side on a device: count_wgs set (to the most a column can have, one per 256 particles) makes
                 // the library taper the columns of the young epochs and trim its ledger workgroups (8 chunks of the C3 shape: 1.17e5
                 // segments/s against 1.09e5, 12 chunks 1.29e5 against 1.11e5; profiles/round4/wg_trace.md).  The sums of a chunk are grouped by workgroup: a run that must give the same bits
-                // whatever the number of ranks pins the width with -count_wgs.
+                // whatever the number of ranks pins the width with -count_wgs (from 9 haplotypes on a rank's only chunk goes to pf_run on the
+                // general kernels, which then count with the same column widths: k_count_cw).
                 jobs[k].count_wgs = P.count_wgs > 0 ? P.count_wgs : ((lockstep && my_chunks.size() >= 6) ? (int)((P.particles + 255) / 256) : 0);
             }
             // Side by side in groups: as many of the rank's chunks as the device has memory for are opened together (every
             // filter holds its own rings: the event log alone is Np x 16 384 records by default) and go through one launch per
             // row when the library says the group can (pf_can_run_many: the row pipeline applies to all of them -- one
-            // population, at most 8 haplotypes, no look-ahead, Np <= 131 072 -- and they share their shape); otherwise, and
+            // population, at most 16 haplotypes, no look-ahead, Np <= 131 072 -- and they share their shape); otherwise, and
             // whenever a group comes down to one chunk, one after the other.
             size_t k0 = 0;
             while (k0 < my_chunks.size()) {

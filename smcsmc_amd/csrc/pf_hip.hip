@@ -17,6 +17,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +34,7 @@
 #include "pf_mp_host.h"
 #include "pf_wide_host.h"
 #include "pf_pipe.h"
+#include "pf_lds_pipe.h"
 
 using namespace pf;
 
@@ -793,8 +795,9 @@ __device__ void window_generations(const KA& A, Ctrl* c, const Windows& W, int t
         for (int e = 1; e < E; ++e) gr = c->g_lo[e] < gr ? c->g_lo[e] : gr;
         c->g_retain = gr;
         c->delayed_opp += W.b[E - 1] - W.a[E - 1];
-        if (A.n_bias > 0) {
-            // update_delayed_weight_count (count.cpp:395-397): particles that carry pending factors
+        if (A.n_bias > 0 || A.g_K > 0) {
+            // update_delayed_weight_count (count.cpp:395-397): particles that carry pending factors (a guide alone delays its
+            // factors too: the extend kernels fill chunk_dpend whenever they run biased)
             long long npend = 0;
             const int ncq = (int)((A.Np + 63) / 64);
             for (int q = 0; q < ncq; ++q) npend += A.chunk_dpend[q];
@@ -1547,6 +1550,19 @@ __global__ __launch_bounds__(PF_BS) void k_count(KArgs A, int e0, Windows Wn) {
     count_body<NM, P>(A, count_src_parity(A, A.sp, e), e, Wn.a[e], Wn.b[e], (int)blockIdx.x, (int)gridDim.x);
 }
 
+// k_count with the column widths of the row pipeline (KArgs::cw_off: pf_params.count_wgs was set): grid = (widest column, epochs).
+// For the handles whose chunks pf_run_many takes through k_sweep_blc<16, 1, *> while pf_run, pf_finish and the step API count here:
+// a column's sums are grouped by its workgroups (count_body), so both have to give it the same number (pipe_count_item)
+template <int NM, int P>
+__global__ __launch_bounds__(PF_BS) void k_count_cw(KArgs A, int e0, Windows Wn) {
+    const int e = e0 + (int)blockIdx.y;
+    if (e < Wn.first || e >= A.E) return;
+    const int j = A.E - 1 - e;
+    const int cnb = A.cw_off[j + 1] - A.cw_off[j];
+    if ((int)blockIdx.x >= cnb) return;
+    count_body<NM, P>(A, count_src_parity(A, A.sp, e), e, Wn.a[e], Wn.b[e], (int)blockIdx.x, cnb);
+}
+
 // ------------------------------------------------------------------ k_row
 // One launch per row on a single stream: workgroups [0, nb) extend the particles over row s (and complete row s-1 on
 // load), the remaining workgroups evaluate the lagged counts of row s-1 (k_count's body).  The two halves touch
@@ -1938,7 +1954,7 @@ __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeL
     // are what would keep it from four workgroups per compute unit)
     if constexpr (!LEAN) {
         if (bx < nb) {
-            if constexpr (P == 1) { if (PL.row.extend || PL.row.complete) extend_reg_body<NM, BIASED, EXACT, TREES, true>(A, s, 0, PL.row); }
+            if constexpr (P == 1 && !BLC) { if (PL.row.extend || PL.row.complete) extend_reg_body<NM, BIASED, EXACT, TREES, true>(A, s, 0, PL.row); }
             return;
         }
         if (bx == nb) {
@@ -1949,7 +1965,7 @@ __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeL
             return;
         }
         if (bx - (nb + 1) < PL.nT) {
-            if constexpr (P == 1) draw_role(A, bx - (nb + 1), PL.nT, PL.row.draws - 1);
+            if constexpr (P == 1 && !BLC) draw_role(A, bx - (nb + 1), PL.nT, PL.row.draws - 1);
             return;
         }
     } else {
@@ -2132,6 +2148,24 @@ __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 template <bool EXACT>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_sweep_blc4q(const SweepChunk* tab_g, long long t) {
     sweep_blc_body<4, 1, false, EXACT, true, true>(tab_g, t);
+}
+
+// The extend role of the row pipeline on the per-lane LDS tree (one population, 9 to 16 haplotypes; extend_lds_pipe_body,
+// pf_lds_pipe.h): step t of the chunk table, blockIdx.y is the chunk, 256 particles per workgroup.  A chunk that is finished or
+// sits the call out leaves before it touches LDS or memory other than its table entry.  The bookkeeping, ledger and count
+// roles of the step are k_sweep_blc<16, 1, *> on the counting stream: in one launch every count workgroup would be given the
+// extend workgroups' tree columns (100 KB at 16 haplotypes) and one would fit a compute unit.
+template <bool BIASED>
+__global__ __launch_bounds__(PF_BS) void k_sweep_xl(const SweepChunk* tab_g, long long t) {
+    SweepChunkC* tab = (SweepChunkC*)tab_g;
+    SweepChunkC& ch = tab[pf_chunk()];
+    KArgsC& A = ch.A;
+    const long long s = ch.s_begin + t;
+    PipeLaunch PL;
+    if (!sweep_plan(ch, s, 0, PL)) return;
+    if (!(PL.row.extend || PL.row.complete)) return;
+    extern __shared__ double smem[];
+    extend_lds_pipe_body<BIASED>(A, s, PL.row, smem);
 }
 
 // first step of a call: the seed of k_pipe_seed, and the chunk's window state
@@ -2610,6 +2644,8 @@ struct pf_handle {
     int trace_t0 = 0, trace_n = 0, trace_stride = 0, trace_grid[3] = {0, 0, 0};
     bool pipe_mp = false;         // structured models on the row pipeline: extend launches on the filter stream, the other roles on the counting stream
     size_t smem_sweep_x = 0;
+    bool pipe_lds = false;        // one population, 9 to 16 haplotypes: pf_run_many takes the chunks on the row pipeline with the tree in LDS
+                                  // (k_sweep_xl + k_sweep_blc, run_sweep_x); pf_run on one handle keeps the general kernels
     std::vector<hipEvent_t> ev_x, ev_blc;   // completion of the last 16 extend / bookkeeping-ledger-count launches
     bool no_spec_stage = false;   // PF_DEBUG_NO_SPEC_STAGE
     bool use_k_pipe = false;      // PF_DEBUG_K_PIPE: rows through k_pipe (argument block by value, one chunk per launch) instead of k_sweep
@@ -2915,11 +2951,17 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
         A.app_delays = dad;
     }
     h->pipe = P == 1 && n <= 8 && Np <= 131072 && !wide;      // beyond that the decision tables outgrow the default dynamic LDS
-    // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_mp)
+    // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_x)
     h->pipe_mp = P > 1 && n <= 8 && Np <= 131072 && !(p->flags & 2) && !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE));
+    // one population on the LDS tree, several chunks in lockstep (pf_run_many): the same rings, the extend role k_sweep_xl.  Not with
+    // -arg, not with a debug switch that selects a path, and not with a generation ring too short for an extend role that runs
+    // ahead of the counts (what pf_create refuses for structured models; here the general kernels serve such a handle as before)
+    h->pipe_lds = P == 1 && n > 8 && n <= PF_NMAX && Np <= 131072 && !wide && !(p->flags & 2) && gen_cap >= PF_RING + 4 &&
+                  !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_FORCE_WIDE)) &&
+                  lds_pipe_tables_fit(n, (int)((Np + 63) / 64));
     A.blk_gran = h->pipe_mp ? 4 : 1;
     {
-        const size_t K = (h->pipe || h->pipe_mp) ? PF_RING : 2;               // copies of the particle state (KArgs::st0)
+        const size_t K = (h->pipe || h->pipe_mp || h->pipe_lds) ? PF_RING : 2;               // copies of the particle state (KArgs::st0)
         A.nslots = (int)K;
         DState& st = A.st0;
         rc |= dalloc(h, &st.S, K * (size_t)(n - 1) * Np);
@@ -2998,7 +3040,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     rc |= dalloc(h, &A.nruns, A.Gcap);
     const size_t nc = (size_t)((Np + 63) / 64);
     A.nc = (int)nc;
-    if (h->pipe || h->pipe_mp) {
+    if (h->pipe || h->pipe_mp || h->pipe_lds) {
         rc |= dalloc(h, &A.run_st2, (size_t)A.Gcap * Np);
         rc |= dalloc(h, &A.run_anc2, (size_t)A.Gcap * Np);
         rc |= dalloc(h, &A.nruns2, A.Gcap);
@@ -3046,7 +3088,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
             h->cw_off[j + 1] = h->cw_off[j] + w;
         }
         int* dcw = nullptr;
-        if (h->pipe || h->pipe_mp) {
+        if (h->pipe || h->pipe_mp || h->pipe_lds) {
             rc |= dalloc(h, &dcw, E + 1);
             if (!rc) { hipMemcpyAsync(dcw, h->cw_off.data(), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, h->stream); hipStreamSynchronize(h->stream); }
             // (with every column at full width the kernels compute column and workgroup from the index: no table)
@@ -3080,6 +3122,22 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     if (h->pipe_mp) {
         h->smem_sweep_x = pf_mp_sweep_smem_bytes(E, P, A.mcap, A.nc);
         if (pf_mp_sweep_prepare(h->smem_sweep_x)) h->pipe_mp = false;        // the event lists and the decision tables do not fit together: the two-stream path
+    }
+    if (h->pipe_lds) {
+        // k_sweep_xl: the LDS of k_extend (the decision tables lie in the tree columns); the rings stay, pf_run_many refuses
+        h->smem_sweep_x = h->smem;
+        // (the attribute belongs to the kernel, not to the handle: the largest any handle of the process has asked for, so that a
+        // handle of twelve haplotypes made after one of sixteen does not lower it)
+        static std::atomic<int> xl_smem{0};
+        int most = xl_smem.load();
+        while (most < (int)h->smem && !xl_smem.compare_exchange_weak(most, (int)h->smem)) {}
+        most = std::max(most, (int)h->smem);
+        if (most > 64 * 1024 &&
+            (hipFuncSetAttribute((const void*)k_sweep_xl<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+             hipFuncSetAttribute((const void*)k_sweep_xl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)) {
+            (void)hipGetLastError();
+            h->pipe_lds = false;
+        }
     }
     return h;
 }
@@ -3363,6 +3421,8 @@ static int launch_count(pf_handle* h, long long s, const Windows& W) {
         } else if (P == 1) {
             if (h->n <= 4) PF_LAUNCH_COUNT(4, 1);
             else if (h->n <= 8) PF_LAUNCH_COUNT(8, 1);
+            else if (h->pipe_lds && h->A.cw_off)               // count_wgs set: the columns as wide as pf_run_many makes them
+                hipLaunchKernelGGL((k_count_cw<PF_NMAX, 1>), dim3(h->ncw, h->E - first), blk, 0, h->cstream, h->A, first, W);
             else PF_LAUNCH_COUNT(PF_NMAX, 1);
         } else if (P == 2) {
             if (h->n <= 4) PF_LAUNCH_COUNT(4, 2);
@@ -3623,6 +3683,8 @@ static bool sweep_compatible(const pf_handle* a, const pf_handle* b) {
            (a->A.dt_tab != nullptr) == (b->A.dt_tab != nullptr) &&
            // structured models: what the two launches of a step take from the leader (the extend launch's LDS and, through it, the capacities)
            a->pipe_mp == b->pipe_mp &&
+           // the LDS tree (9 to 16 haplotypes): the flag and the extend launch's LDS (n = 12 does not run with n = 16, nor either with n <= 8)
+           a->pipe_lds == b->pipe_lds && (!a->pipe_lds || (a->smem_sweep_x == b->smem_sweep_x && a->A.dcap == b->A.dcap && a->A.n_bias == b->A.n_bias)) &&
            (!a->pipe_mp || (a->smem_sweep_x == b->smem_sweep_x && a->A.mcap == b->A.mcap && a->A.pcap == b->A.pcap && a->A.dcap == b->A.dcap && a->A.n_bias == b->A.n_bias));
 }
 
@@ -3791,7 +3853,7 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
 // PF_DEBUG_ONE_LAUNCH = run_sweep): the extend, bookkeeping and draw roles of all chunks
 // (k_sweep4, one launch after the other on the leader's stream: the chain of dependent loads that is the critical path of a step) and
 // their ledger and count roles (k_sweep_blc, on the counting stream, behind the extend launch of the step before by its completion
-// signal and paced by the sixteen-slot ring as in run_sweep_mp).  The second launch needs no dynamic LDS -- that is the bookkeeping
+// signal and paced by the sixteen-slot ring as in run_sweep_x).  The second launch needs no dynamic LDS -- that is the bookkeeping
 // role's -- and fewer registers than the extend role: four of its workgroups share a compute unit where the single launch has room for
 // three, and its tail no longer holds up the next row's extend role.  Same bits as run_sweep.
 static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
@@ -3819,7 +3881,7 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
     for (long long t = 0; t < steps; ++t) {
         const long long s = s_begin + t;
         static_assert(PF_RING == 16, "the wait schedule below is written for sixteen ring slots");
-        if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);      // ring slot reuse, as in run_sweep_mp
+        if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);      // ring slot reuse, as in run_sweep_x
         // The second launches follow in batches of `batch` steps: only the last extend launch of a batch carries a completion signal, and the
         // batch's second launches wait for that one (each needs the extend launch of the step before it: complete by then).
         const bool batch_end = ((t + 1) % batch) == 0 || t == steps - 1;
@@ -3873,7 +3935,12 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
 // next row on the previous row's ledger upkeep are gone from the critical stream.  A chunk never reads another chunk's memory and
 // takes nothing from the launch geometry but its own blockIdx.x: every chunk is bit-identical to its own pf_run
 // (tests/test_gpu_sweep_structured.py).
-static int run_sweep_mp(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
+// The same runner serves one population with the tree in LDS (pipe_lds: 9 to 16 haplotypes, several chunks through pf_run_many): the
+// extend role is k_sweep_xl (256 particles per workgroup, 100 KB of tree columns at 16 haplotypes -- the same reason for two
+// launches), the other roles k_sweep_blc<16, 1, *>, and the table says so with SweepChunk::split = 1 (sweep_plan: the extend role
+// runs ahead).  Everything else -- the table, the seed, the two waits per step, the windows -- is shared line for line, which is why
+// this is one function with two launch sites and not a sibling (tests/test_gpu_sweep_lds.py).
+static int run_sweep_x(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
     pf_handle* h = hs[0];
     if (s_begin >= s_end) return 0;
     const int nb = h->nblocks;
@@ -3882,7 +3949,7 @@ static int run_sweep_mp(pf_handle* const* hs, int nh, long long s_begin, long lo
     sweep_join(hs, nh);
     if (sweep_event_ring(h)) return -1;
     bool failed = false;
-    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, 0, &failed);
+    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, h->pipe_lds ? 1 : 0, &failed);
     if (failed) return -1;
     if (steps == 0) return 0;
     // the counting stream starts behind the table and the seed
@@ -3899,14 +3966,22 @@ static int run_sweep_mp(pf_handle* const* hs, int nh, long long s_begin, long lo
         if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);
         {
             Timed tm(h, 0, timing_on(h, s));
-            pf_mp_launch_sweep_x(h->A, h->d_sweep, nh, t, h->smem_sweep_x, h->stream, h->ev_x[(size_t)(t & 15)]);
+            if (h->pipe_lds) {
+                const dim3 gx((unsigned)nb, (unsigned)nh), bx(PF_BS);
+                hipEvent_t xdone = h->ev_x[(size_t)(t & 15)];
+                if (biased) hipExtLaunchKernelGGL((k_sweep_xl<true>), gx, bx, h->smem_sweep_x, h->stream, nullptr, xdone, 0, h->d_sweep, t);
+                else hipExtLaunchKernelGGL((k_sweep_xl<false>), gx, bx, h->smem_sweep_x, h->stream, nullptr, xdone, 0, h->d_sweep, t);
+            } else {
+                pf_mp_launch_sweep_x(h->A, h->d_sweep, nh, t, h->smem_sweep_x, h->stream, h->ev_x[(size_t)(t & 15)]);
+            }
         }
-        if (check_launch("k_sweep_xmp")) return -1;
+        if (check_launch(h->pipe_lds ? "k_sweep_xl" : "k_sweep_xmp")) return -1;
         hipStreamWaitEvent(h->cstream, t >= 1 ? h->ev_x[(size_t)((t - 1) & 15)] : seeded, 0);
         const dim3 grid((unsigned)(1 + sweep_lc_wgs(hs, nh, s_begin, s, W2.data(), nL_full)), (unsigned)nh), blk(PF_BS);
         hipEvent_t done = h->ev_blc[(size_t)(t & 15)];
 #define PF_LAUNCH_BLC(NMV, PV, BV) hipExtLaunchKernelGGL((k_sweep_blc<NMV, PV, BV>), grid, blk, h->smem_pipe, h->cstream, nullptr, done, 0, h->d_sweep, t)
-        if (h->P == 2) { if (biased) PF_LAUNCH_BLC(8, 2, true); else PF_LAUNCH_BLC(8, 2, false); }
+        if (h->pipe_lds) { if (biased) PF_LAUNCH_BLC(PF_NMAX, 1, true); else PF_LAUNCH_BLC(PF_NMAX, 1, false); }
+        else if (h->P == 2) { if (biased) PF_LAUNCH_BLC(8, 2, true); else PF_LAUNCH_BLC(8, 2, false); }
         else { if (biased) PF_LAUNCH_BLC(8, PF_PMAX, true); else PF_LAUNCH_BLC(8, PF_PMAX, false); }
 #undef PF_LAUNCH_BLC
         if (check_launch("k_sweep_blc")) return -1;
@@ -3929,10 +4004,15 @@ static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles
         if (!g) return "pf_run_many: null handle";
         const bool one_pop = extend_can_fuse(g) && g->pipe && !g->two_launch_rows;
         const bool structured = g->pipe_mp && g->A.apf == 0 && !g->force_lds && !g->no_fuse;
-        if (!one_pop && !structured)
-            return "pf_run_many: the chunks must run on the row pipeline (one population, or a structured model of two to four populations with "
-                   "the tree in registers; at most 8 haplotypes, no look-ahead, no -arg)";
-        if (!sweep_compatible(h, g)) return "pf_run_many: the chunks must share device, particle count, haplotypes, epochs and options";
+        // one population, 9 to 16 haplotypes, the tree in LDS.  Out of scope here: structured models above 8 haplotypes, -arg and the
+        // look-ahead in lockstep, the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the general kernels
+        const bool lds_tree = g->pipe_lds && g->A.apf == 0;
+        if (!one_pop && !structured && !lds_tree)
+            return "pf_run_many: the chunks must run on the row pipeline (one population of at most 16 haplotypes, or a structured model of two to "
+                   "four populations with the tree in registers, at most 8 haplotypes; no look-ahead, no -arg above 8 haplotypes, no debug "
+                   "switch that selects another path)";
+        if (!sweep_compatible(h, g)) return "pf_run_many: the chunks must share device, particle count, haplotypes (and with them the form of the tree: registers up to 8, "
+                                              "LDS columns of one width from 9 to 16), epochs and options";
         for (int j = 0; j < k; ++j) if (handles[j] == g) return "pf_run_many: a handle appears twice";
     }
     return nullptr;
@@ -3947,7 +4027,7 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
     pf_handle* h = handles[0];
     HIPCHK(hipSetDevice(h->device));
     if (s_begin < 0) { g_err = "segment range out of bounds"; return -1; }        // a chunk with fewer rows sits the call out
-    if (h->pipe_mp) return run_sweep_mp(handles, n_handles, s_begin, s_end);
+    if (h->pipe_mp || h->pipe_lds) return run_sweep_x(handles, n_handles, s_begin, s_end);
     if (h->split_many && !h->A.rec_trees) return run_sweep_split(handles, n_handles, s_begin, s_end);
     return run_sweep(handles, n_handles, s_begin, s_end);
 }
@@ -3962,7 +4042,7 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end) {
         if (h->split_many && !h->A.rec_trees) return run_sweep_split(one, 1, s_begin, s_end);
         return run_sweep(one, 1, s_begin, s_end);
     }
-    if (h->pipe_mp && h->A.apf == 0 && !h->force_lds && !h->no_fuse) { pf_handle* one[1] = {h}; return run_sweep_mp(one, 1, s_begin, s_end); }
+    if (h->pipe_mp && h->A.apf == 0 && !h->force_lds && !h->no_fuse) { pf_handle* one[1] = {h}; return run_sweep_x(one, 1, s_begin, s_end); }
     // structured models on the register-tree kernel: the next row's extend completes this row while it loads (two
     // launches per row on the main stream instead of three); the last row of the call is completed by k_resample
     const bool mp_fuse = h->P > 1 && pf_mp_can_fuse(h->A, h->force_lds) && h->A.apf == 0 && !h->no_fuse;

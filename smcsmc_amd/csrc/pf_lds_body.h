@@ -92,6 +92,9 @@ __device__ __forceinline__ void init_lds_body(const KArgs& A, double initial_pos
 // ------------------------------------------------------------------ k_extend
 // ParticleContainer::extend_ARGs + update_weight_at_site (particleContainer.cpp:98-135, 187-224)
 // with ForestState::extend_ARG (particle.cpp:743-918) per lane.
+// (extend_lds_pipe_body, pf_lds_pipe.h, repeats the row loop, the delayed-factor store, the site likelihood and the partials of this
+// body statement for statement for the row pipeline -- k_sweep_xl: a change to any of them here is a change there as well;
+// tests/test_gpu_sweep_lds.py compares the two bit for bit)
 __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, double* smem) {
     Smem m = carve(smem, A.n, A.E);
     load_model(A, m);

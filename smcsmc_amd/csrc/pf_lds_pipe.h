@@ -1,0 +1,484 @@
+// smcsmc_amd/csrc/pf_lds_pipe.h -- the extend role of the row pipeline on the per-lane LDS tree (k_sweep_xl, pf_hip.hip): one
+// population, 9 to PF_NMAX haplotypes.  What extend_lds_body (pf_lds_body.h) does for a row between k_resample and k_decide,
+// with the decision on the previous row, the parent search and k_resample's part taken into the prologue, as
+// extend_reg_body<..., PIPE> does for the register tree.  A function of its own: k_extend, k_extend_wide and the calibration
+// and simulation kernels keep the body they had, instruction for instruction.
+// The price is a second copy: from "the row" on, extend_lds_pipe_body repeats extend_lds_body's statements (row loop, delayed-factor
+// store, guide, site likelihood, partials), load_model_k / make_lane_k repeat load_model / make_lane (pf_lane.h), and the prologue
+// follows extend_reg_body<..., PIPE> (pf_hip.hip).  A fix to one of them belongs in both; tests/test_gpu_sweep_lds.py holds the
+// copies together bit for bit.
+#pragma once
+#include "pf_device.h"
+#include "pf_types.h"
+#include "pf_lane.h"
+#include "pf_pipe.h"
+
+// load_model / make_lane for an argument block in either address space
+template <class KA>
+__device__ __forceinline__ void load_model_k(const KA& A, Smem& m) {
+    for (int e = threadIdx.x; e < A.E; e += blockDim.x) {
+        m.T[e] = A.T[e];
+        m.I[e] = A.inv2N[e];
+        m.RF[e] = A.recflags[e];
+    }
+}
+template <class KA>
+__device__ __forceinline__ Lane make_lane_k(const KA& A, Smem& m, long long p) {
+    Lane ln;
+    ln.S = m.S + threadIdx.x;
+    ln.C = m.C + threadIdx.x;
+    ln.T = m.T; ln.I = m.I; ln.RF = m.RF; ln.H = A.Hc;
+    ln.E = A.E; ln.n = A.n;
+    ln.L = A.L; ln.mu = A.mu; ln.rho = A.rho;
+    ln.seed = A.seed;
+    ln.slot = (unsigned)p;
+    ln.stream = 0;
+    ln.ctr = 0; ln.ebuf = 0; ln.Ltree = 0;
+    ln.vbc = A.vb_coal; ln.upd_fac = 1.0;
+    return ln;
+}
+
+// the decision tables of the prologue lie where the lanes' tree columns (S, t0, t1) go afterwards
+__host__ __device__ inline bool lds_pipe_tables_fit(int n, int nc) { return pipe_lds_doubles(nc) <= (size_t)3 * (n - 1) * PF_BS; }
+
+// BIASED: focused sampling or a guide (the delayed-factor store, the guide's segment index)
+template <bool BIASED, class KA>
+__device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, const PipeRow PR, double* smem) {
+    Smem m = carve(smem, A.n, A.E);
+    __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
+    const Ctrl* c = A.ctrl;
+    const int n = A.n;
+    const long long p = (long long)pf_bx() * PF_BS + threadIdx.x;
+    const bool active = p < A.Np;
+    const int lane = threadIdx.x & 63;
+    const bool guided = BIASED && A.g_K > 0;
+    const bool biased = BIASED;                          // a guide alone runs with one band of strength 1
+    // ---- everything the prologue and the lane need first, requested in one round trip: the row's own segment, the partials of the
+    // decision, the pilot scans around this workgroup (the parent search of a resampling row), what the slot owns ----
+    double sg_start = 0.0, sg_len = 0.0;
+    int sg_limit = 0, sg_state = 1;
+    if (PR.extend) {
+        sg_start = A.seg_start[s]; sg_len = A.seg_len[s];
+        sg_limit = A.seg_limit[s]; sg_state = A.seg_state[s];
+    }
+    const int fs = __builtin_amdgcn_readfirstlane(PR.slot_prev >= 0 ? PR.slot_prev : c->cur);
+    RowPre pre;
+    long long o_nres = 0; int o_bflag = 0, o_bgen = 0;
+    double spec_sm[PF_PIPE_STAGE * 64 / PF_BS];
+    int spec_lo = 0;
+    double o_sm = 0.0, o_xmark = 0.0, o_ebuf = 0.0;
+    int o_ml = 0;
+    unsigned o_widx = 0;
+    unsigned long long o_ctr = 0;
+    if (PR.complete) {
+        pre = row_preload(A, fs);
+        // the row before it: what the extend role of the previous launch noted (the bookkeeping role runs on another stream and
+        // is not waited for)
+        const int bs = (fs + PF_RING - 1) & (PF_RING - 1);
+        o_nres = c->xr[bs].n_res; o_bflag = c->xr[bs].flag; o_bgen = c->xr[bs].gen;
+        spec_lo = pf_bx() * (PF_BS / 64) - (PF_PIPE_STAGE - PF_BS / 64) / 2;
+        if (spec_lo > A.nc - PF_PIPE_STAGE) spec_lo = A.nc - PF_PIPE_STAGE;
+        if (spec_lo < 0) spec_lo = 0;
+        const double* sm0 = A.rg_scan1m + (size_t)fs * A.Np;
+#pragma unroll
+        for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) {
+            const long long src = (long long)spec_lo * 64 + k * PF_BS + threadIdx.x;
+            spec_sm[k] = src < A.Np ? sm0[src] : PF_INF;
+        }
+    }
+    if (active) {
+        const DState own = state_slot(A, fs);
+        o_xmark = own.x_mark[p]; o_ml = own.mark_limit[p];
+        o_widx = PR.complete ? A.rg_widx[(size_t)fs * A.Np + p] : A.widx[p];
+        o_ctr = A.rng_ctr[p]; o_ebuf = A.ebuf[p];
+        if (PR.complete) o_sm = A.rg_scan1m[(size_t)fs * A.Np + p];
+    }
+    load_model_k(A, m);
+    if (threadIdx.x < PF_BIAS_MAX + 2) {
+        sBH[threadIdx.x] = A.bias_H[threadIdx.x];
+        if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
+    }
+    // ---- the decision on the previous row and, when it resampled, the parent of every slot of this workgroup (extend_reg_body's
+    // prologue: decide_row, the offspring offsets in closed form, the two-level search over the pilot prefix sums) ----
+    const bool completing = PR.complete != 0;
+    bool gather = false;
+    double inv = 1.0, S1v = 0.0;
+    const double pos_prev = PR.pos_prev;
+    int lo_p = 0, lo_p1 = 0;
+    bool first_copy = true;
+    long long a = p;
+    int G_end = 0, ev = 0;
+    if (completing) {
+        PipeLds q = pipe_carve(smem, A.nc);
+        const int row_slot = fs;
+        const long long n_res = o_nres + o_bflag;
+        G_end = o_bgen + o_bflag;
+        ev = (int)n_res;
+#pragma unroll
+        for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) q.stage[k * PF_BS + threadIdx.x] = spec_sm[k];    // visible after decide_row's barriers
+        RowDecision d = decide_row<true>(A, q, row_slot, n_res, pre);
+        inv = d.inv; S1v = d.S1;
+        gather = d.flag != 0;
+        if (pf_bx() == 0 && threadIdx.x == 0) {
+            Ctrl* cw = A.ctrl;
+            cw->xr[row_slot].n_res = n_res; cw->xr[row_slot].gen = G_end; cw->xr[row_slot].flag = d.flag;
+        }
+        if (gather) {
+            const double dn = (double)A.Np;
+            const double invS1 = 1.0 / d.S1;
+            const double* sm = A.rg_scan1m + (size_t)row_slot * A.Np;
+            const int wave = threadIdx.x >> 6;
+            const int ch_own = (int)(p >> 6);
+            int lo_next = 0;
+            if (active) {
+                const double w = pipe_chunk_offset(q, ch_own) + o_sm;
+                const double v_own = q.pmx[ch_own] > w ? q.pmx[ch_own] : w;          // largest pilot prefix sum up to particle p
+                lo_next = p + 1 < A.Np ? pipe_lo_from(v_own, dn, A.Np, d.S1, invS1, d.u) : (int)A.Np;
+                q.slo[threadIdx.x] = lo_next;
+            }
+            // parent of slot p: the first particle a with (p+u) * S1 < N * (largest prefix sum up to a)
+            const double lhs = ((double)p + d.u) * d.S1;
+            int pch = 0;
+            if (active) {
+                int lo_c = 0, hi_c = A.nc - 1;
+                while (lo_c < hi_c) {
+                    int mid = (lo_c + hi_c) >> 1;
+                    if (lhs < dn * q.pmx[mid + 1]) hi_c = mid; else lo_c = mid + 1;
+                }
+                pch = lo_c;
+            }
+            int cmin = active ? pch : 0x7fffffff, cmax = active ? pch : -1;
+#pragma unroll
+            for (int k = 1; k < 64; k <<= 1) {
+                int o1 = __shfl_xor(cmin, k, 64), o2 = __shfl_xor(cmax, k, 64);
+                cmin = o1 < cmin ? o1 : cmin; cmax = o2 > cmax ? o2 : cmax;
+            }
+            if (lane == 0) { q.wint[wave] = cmin; q.wint[PF_BS / 64 + wave] = cmax; }
+            __syncthreads();
+            if (active) {
+                lo_p1 = lo_next;
+                if (threadIdx.x > 0) lo_p = q.slo[threadIdx.x - 1];
+                else lo_p = p > 0 ? pipe_lo_from(q.pmx[ch_own], dn, A.Np, d.S1, invS1, d.u) : 0;
+            }
+            cmin = q.wint[0]; cmax = q.wint[PF_BS / 64];
+            for (int w = 1; w < PF_BS / 64; ++w) {
+                cmin = q.wint[w] < cmin ? q.wint[w] : cmin;
+                cmax = q.wint[PF_BS / 64 + w] > cmax ? q.wint[PF_BS / 64 + w] : cmax;
+            }
+            // survivors of this workgroup (the ledger positions the run list of the ending generation with them)
+            {
+                unsigned long long bal = __ballot(active && lo_p1 > lo_p);
+                if (lane == 0) q.wint[2 * (PF_BS / 64) + wave] = __popcll(bal);
+            }
+            int nst = cmax - cmin + 1;
+            if (nst > PF_PIPE_STAGE) nst = PF_PIPE_STAGE;
+            if (nst < 0) nst = 0;
+            int stage_lo = cmin;
+            if (cmin >= spec_lo && cmax < spec_lo + PF_PIPE_STAGE) {
+                stage_lo = spec_lo; nst = PF_PIPE_STAGE;       // the scans requested with the prologue cover the range
+            } else {
+                __syncthreads();                               // everybody has read the range before the buffer is refilled
+                for (int idx = threadIdx.x; idx < nst * 64; idx += PF_BS) {
+                    long long src = (long long)cmin * 64 + idx;
+                    q.stage[idx] = src < A.Np ? sm[src] : PF_INF;
+                }
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                int tot = 0;
+                for (int w = 0; w < PF_BS / 64; ++w) tot += q.wint[2 * (PF_BS / 64) + w];
+                A.rg_blkcnt[(size_t)row_slot * (size_t)((A.Np + PF_BS - 1) / PF_BS) * A.blk_gran + pf_bx()] = tot;
+            }
+            if (active) {
+                const double coff_p = pipe_chunk_offset(q, pch);
+                const double pm_p = q.pmx[pch];
+                const bool staged = pch >= stage_lo && pch - stage_lo < nst;
+                auto val_at = [&](int l) -> double {           // largest prefix sum up to particle pch*64 + l
+                    long long idx = (long long)pch * 64 + l;
+                    double smv = staged ? q.stage[(pch - stage_lo) * 64 + l] : (idx < A.Np ? sm[idx] : PF_INF);
+                    double w = coff_p + smv;
+                    return pm_p > w ? pm_p : w;
+                };
+                int lo_l = 0, hi_l = 63;
+                while (lo_l < hi_l) {
+                    int mid = (lo_l + hi_l) >> 1;
+                    if (lhs < dn * val_at(mid)) hi_l = mid; else lo_l = mid + 1;
+                }
+                a = (long long)pch * 64 + lo_l;
+                if (a > A.Np - 1) a = A.Np - 1;
+                // slot p is the first copy of a (it keeps a's next recombination position) iff it equals a's offset
+                const int la = (int)(a & 63);
+                if (p == 0 || a == 0) first_copy = (p == 0);
+                else {
+                    double vprev = la > 0 ? val_at(la - 1) : pm_p;      // largest prefix sum up to a - 1
+                    if (a != (long long)pch * 64 + lo_l) {             // clamped: recompute on the true chunk of a - 1
+                        long long am = a - 1;
+                        int chm = (int)(am >> 6);
+                        double w = pipe_chunk_offset(q, chm) + sm[am];
+                        vprev = q.pmx[chm] > w ? q.pmx[chm] : w;
+                    }
+                    first_copy = ((((double)(p - 1)) + d.u) * d.S1 < dn * vprev);
+                }
+                // the offspring table of the generation that ends here, for the ledger
+                int* lo_tab = A.lo + (size_t)(G_end % A.Gcap) * (A.Np + 1);
+                lo_tab[p] = lo_p;
+                if (p == A.Np - 1) lo_tab[A.Np] = (int)A.Np;
+            }
+        }
+    }
+    __syncthreads();          // the tables are dead from here on: the lanes' tree columns take their place (and the model tables are in)
+    const int cur = __builtin_amdgcn_readfirstlane(PR.slot_out);
+    const int from_slot = fs;
+    bool has_pending = false;
+    double w_post = 0.0, w_pilot = 0.0;
+    if (active) {
+        const DState st = state_slot(A, cur);
+        const DState from = state_slot(A, from_slot);
+        Lane ln = make_lane_k(A, m, p);
+        // the parent's tree into this lane's columns (its own when the row did not resample)
+        for (int r = 0; r < n - 1; ++r) {
+            LS(ln, r) = from.S[(size_t)r * A.Np + a];
+            LC(ln, r, 0) = from.C[(size_t)(2 * r) * A.Np + a];
+            LC(ln, r, 1) = from.C[(size_t)(2 * r + 1) * A.Np + a];
+        }
+        w_post = from.w_post[a];
+        w_pilot = from.w_pilot[a];
+        double next_base = from.next_base[a];
+        double x_mark = from.x_mark[a];
+        int mark_limit = from.mark_limit[a];
+        ln.Ltree = from.Ltree[a];
+        ln.ctr = o_ctr;
+        ln.ebuf = o_ebuf;
+        unsigned widx = o_widx;
+        DStore ds;
+        d_bind(ds, A, st, p);
+        ds.count = 0; ds.total = 1.0;
+        if (biased) {
+            ds.count = from.dcount[a]; ds.total = from.total_delayed[a];
+            // the copy constructor copies the pending factors (particle.cpp:122-123); the ring moves them every row
+            for (int k = 0; k < ds.count; ++k) {
+                st.dpos[(size_t)k * A.Np + p] = from.dpos[(size_t)k * A.Np + a];
+                st.dfac[(size_t)k * A.Np + p] = from.dfac[(size_t)k * A.Np + a];
+                st.ddelta[(size_t)k * A.Np + p] = from.ddelta[(size_t)k * A.Np + a];
+                st.dk[(size_t)k * A.Np + p] = from.dk[(size_t)k * A.Np + a];
+            }
+        }
+        int ridx = guided ? from.ridx[a] : 0;
+        double* tmp0 = m.t0 + threadIdx.x;
+        double* tmp1 = m.t1 + threadIdx.x;
+        if (completing) {
+            // k_resample's part (pc.cpp:321-392, 435-437), operation for operation
+            if (!gather) {
+                w_post *= inv;                             // normalize_probability, pc.cpp:435-437
+                w_pilot *= inv;
+            } else {
+                // role of the old slot p: close its stretch if it has offspring
+                if (lo_p1 > lo_p) {
+                    double* rec = rec_ptr(A, p, widx);
+                    rec[0] = o_xmark;
+                    rec[1] = pos_prev;
+                    rec[2] = 0.0; rec[3] = 0.0;
+                    rec[4] = __longlong_as_double((long long)make_meta(1, o_ml, -1, n));
+                    for (int r = 0; r < n - 1; ++r) rec[5 + r] = from.S[(size_t)r * A.Np + p];
+                    ++widx;
+                }
+                A.gstart[(size_t)((G_end + 1) % A.Gcap) * A.Np + p] = widx;
+                // role of the new slot p: weights of the copy (pc.cpp:350-351), fresh position for all but the first
+                if (ev < A.max_trace_events) A.ev_parents[(size_t)ev * A.Np + p] = (int)a;
+                const double wp = w_post * inv;
+                const double wq = w_pilot * inv;
+                const double sumn = S1v * inv;
+                const double adj = sumn / ((double)A.Np * wq);
+                w_post = wp * adj;
+                w_pilot = wq * adj;
+                x_mark = pos_prev;
+                if (!first_copy && pos_prev < A.L) next_base = sample_next_base_guided(ln, pos_prev, A.g_K, A.g_pos, A.g_rho, ridx);     // pc.cpp:357-368
+            }
+        }
+
+        // ---- the row itself: extend_lds_body ----
+        const bool do_extend = PR.extend != 0;             // the flush step of a call only completes the last row
+        const int8_t* data = A.seg_alleles + (size_t)s * n;
+        const double seg_end = do_extend ? sg_start + sg_len : 0.0;
+        const double extend_to = seg_end < A.L ? seg_end : A.L;
+        const int limit = sg_limit;
+        int missing = 0;
+        for (int i = 0; i < n && do_extend; ++i) missing += data[i] == -1;
+        int leaf_status = 0;
+        if (missing == 0) leaf_status = 1;
+        if (missing == n) leaf_status = -1;
+
+        double updated_to = completing ? pos_prev : c->cur_pos;
+        if (!do_extend) updated_to = extend_to;             // completion only: the loop below does not run
+        double B = 0;
+        if (do_extend) {
+            if (leaf_status == -1) B = 0;
+            else if (leaf_status == 1) B = ln.Ltree;
+            else B = tracked_len_lane(ln, data, tmp0);
+        }
+
+        while (updated_to < extend_to) {
+            double new_to = extend_to < next_base ? extend_to : next_base;
+            double f = fastexp(-A.mu * B * (new_to - updated_to));
+            w_post *= f;
+            w_pilot *= f;
+            if (guided) {
+                // importance_weight_over_segment (particle.cpp:1138-1181): true over guide rate for the stretch
+                // without recombination
+                const double dist = new_to - updated_to;
+                const double target_rate = dist * A.rho * ln.Ltree;
+                const double sampled_rate = dist * A.g_rho[ridx] * ln.Ltree;
+                const double iws = fastexp(sampled_rate - target_rate);
+                w_post *= iws;
+                w_pilot *= iws;
+            }
+            updated_to = new_to;
+            if (guided && updated_to < extend_to && ridx + 1 < A.g_K && updated_to == A.g_pos[ridx + 1]) {
+                // reached a change of the guide rate: no genealogy change, new draw under the new rate
+                ridx += 1;
+                next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
+                continue;
+            }
+            if (updated_to < extend_to) {
+                // a recombination: log the stretch that ends here together with the event
+                double* rec = rec_ptr(A, p, widx);
+                rec[0] = x_mark;
+                rec[1] = updated_to;
+                for (int r = 0; r < n - 1; ++r) rec[5 + r] = LS(ln, r);
+                double h, tc, sp_removed;
+                bool changed;
+                pf_mask_t desc = 0;
+                double iw = 1.0, rbiw = 1.0;
+                genealogy_update(ln, &h, &tc, &sp_removed, &changed, A.lmap_opp ? &desc : nullptr, tmp0,
+                                 biased ? sBH : nullptr, sBS, A.n_bias + 1, &iw,
+                                 guided ? A.g_leaf + (size_t)ridx * n : nullptr, guided ? A.rho / A.g_rho[ridx] : 1.0, &rbiw, nullptr);
+                if (ln.vbc) { w_post *= ln.upd_fac; w_pilot *= ln.upd_fac; ln.upd_fac = 1.0; }
+                rec[2] = h;
+                rec[3] = tc;
+                rec[4] = __longlong_as_double((long long)make_meta(0, mark_limit, limit, n, desc, 0u));
+                ++widx;
+                if (leaf_status == 0) B = tracked_len_lane(ln, data, tmp0);
+                if (leaf_status == 1) B = ln.Ltree;
+                if (biased) {
+                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
+                    const int nbands = A.n_bias + 1;
+                    const double delay_height = (A.delay_type & 3) == 0 ? h : tc;
+                    int idx = 0;
+                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
+                    if (idx >= nbands) idx = nbands - 1;
+                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
+                    const double delay = A.app_delays[epoch_of(ln, delay_height)];
+                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+                }
+                next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
+                ln.uqn = 0;                    // the update's unused uniforms are dropped
+                x_mark = updated_to;
+                mark_limit = limit;
+            }
+        }
+
+        if (biased) {
+            // apply the factors that fell due during this extension (particle.cpp:910-916)
+            for (;;) {
+                if (ds.count == 0 || !do_extend) break;
+                double pm = ds.pos[0];
+                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
+                if (!(pm < extend_to)) break;
+                d_apply_earliest(ds, w_pilot);
+            }
+            st.dcount[p] = ds.count;
+            st.total_delayed[p] = ds.total;
+            if (guided) st.ridx[p] = ridx;
+            has_pending = ds.count > 0;
+        }
+        if (do_extend && sg_state == 0) {
+            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
+            const bool dephase = A.flags & 2;
+            const bool anc = A.flags & 1;
+            pf_mask_t one_mask = 0, zero_mask = 0, het_pairs = 0;
+            int ncfg = 1;
+            for (int i = 0; i < n; ++i) {
+                if (data[i] == 1) one_mask |= (pf_mask_t)1 << i;
+                if (data[i] == 0) zero_mask |= (pf_mask_t)1 << i;
+            }
+            for (int i = 0; i + 1 < n; i += 2) {
+                bool het = (data[i] == 2) || (dephase && data[i] + data[i + 1] == 1);
+                if (het) {
+                    ncfg *= 2;
+                    het_pairs |= (pf_mask_t)1 << i;
+                    one_mask &= ~((pf_mask_t)3 << i); zero_mask &= ~((pf_mask_t)3 << i);
+                    zero_mask |= (pf_mask_t)1 << i;          // hap[i] = 0
+                    one_mask |= (pf_mask_t)1 << (i + 1);     // hap[i+1] = 1
+                }
+            }
+            double norm = 1.0 / (double)ncfg;
+            double lik = 0;
+            for (;;) {
+                lik += site_lik_lane(ln, one_mask, zero_mask, anc, tmp0, tmp1);
+                if (ncfg == 1) break;
+                bool more = false;                  // next_haplotype (pc.cpp:163-181)
+                for (int i = 0; i + 1 < n; i += 2) {
+                    if (!((het_pairs >> i) & 1)) continue;
+                    if ((zero_mask >> i) & 1) {     // phase 0 -> phase 1
+                        zero_mask &= ~((pf_mask_t)1 << i); one_mask |= (pf_mask_t)1 << i;
+                        one_mask &= ~((pf_mask_t)1 << (i + 1)); zero_mask |= (pf_mask_t)1 << (i + 1);
+                        more = true;
+                        break;
+                    }
+                    one_mask &= ~((pf_mask_t)1 << i); zero_mask |= (pf_mask_t)1 << i;
+                    zero_mask &= ~((pf_mask_t)1 << (i + 1)); one_mask |= (pf_mask_t)1 << (i + 1);
+                }
+                if (!more) break;
+            }
+            lik *= norm;
+            w_post *= lik;
+            w_pilot *= lik;
+        }
+
+        for (int r = 0; r < n - 1; ++r) {
+            st.S[(size_t)r * A.Np + p] = LS(ln, r);
+            st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
+            st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
+        }
+        st.w_post[p] = w_post;
+        st.w_pilot[p] = w_pilot;
+        st.next_base[p] = next_base;
+        st.x_mark[p] = x_mark;
+        st.mark_limit[p] = mark_limit;
+        st.Ltree[p] = ln.Ltree;
+        A.rng_ctr[p] = ln.ctr;
+        A.ebuf[p] = ln.ebuf;
+        A.rg_widx[(size_t)cur * A.Np + p] = widx;
+        if (!do_extend) A.widx[p] = widx;              // the state goes back to the general kernels
+        {
+            // this launch runs up to PF_RING - 2 rows ahead of the counts: the writer itself checks that it has not overwritten a
+            // record that a pending count can still ask for (Ctrl::g_safe: the oldest generation those counts reach)
+            const unsigned kold = A.gstart[(size_t)(A.ctrl->g_safe % A.Gcap) * A.Np + p];
+            if (widx - kold > A.cap && !A.ctrl->err) A.ctrl->err = ERR_LOG_OVERFLOW;
+        }
+    }
+    // per-wavefront canonical partials (level 1 of the radix-64 reduction / scan) into the row's ring slot
+    double sp = wave_tree_sum(w_post);
+    double sq = wave_tree_sum(w_pilot * w_pilot);
+    double sc = wave_hs_scan(w_pilot, lane);
+    double scp = wave_hs_scan(w_post, lane);
+    double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
+    const long long chunk = p >> 6;
+    const size_t ro = (size_t)cur * A.Np, co = (size_t)cur * A.nc;
+    if (active) { A.rg_scan1[ro + p] = sc; A.rg_scanp[ro + p] = scp; A.rg_scan1m[ro + p] = scm; }
+    if (p == A.Np - 1) A.ctrl->last1[cur] = sc;
+    if (lane == 63 && chunk < A.nc) {
+        A.rg_cpost[co + chunk] = sp;
+        A.rg_csq[co + chunk] = sq;
+        A.rg_cpil[co + chunk] = sc;
+        A.rg_cpp[co + chunk] = scp;
+        A.rg_cmx1[co + chunk] = scm;
+    }
+    if (biased) {
+        unsigned long long pend = __ballot(has_pending);
+        if (lane == 0 && chunk < A.nc) {
+            A.rg_dpend[co + chunk] = __popcll(pend);
+            if (!PR.extend) A.chunk_dpend[chunk] = __popcll(pend);     // the state goes back to the general kernels
+        }
+    }
+}

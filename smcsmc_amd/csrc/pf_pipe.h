@@ -1,5 +1,5 @@
 // smcsmc_amd/csrc/pf_pipe.h -- what the row pipeline's kernels share across translation units (pf_hip.hip: k_pipe, k_sweep and
-// the bookkeeping / ledger / count roles; pf_mp.hip: the extend role of the structured models): the decision on a finished
+// the bookkeeping / ledger / count roles, k_sweep_xl through pf_lds_pipe.h; pf_mp.hip: the extend role of the structured models): the decision on a finished
 // row taken redundantly by every workgroup, the offspring offsets in closed form, the plan of a step, the per-chunk table
 // of k_sweep.  Workgroup size is a template parameter here (PF_BS differs between the two units).
 #pragma once
@@ -200,7 +200,8 @@ struct SweepChunk {
     int nblk;                      // particle blocks of 256
     int nT;                        // draw-table workgroups per step (0: no table)
     int split;                     // 2: the ledger and count roles are a launch of their own beside the extend, bookkeeping and draw roles
-                                   // (run_sweep_split); 0: one launch per step (run_sweep), or the structured models' two (run_sweep_mp)
+                                   // (run_sweep_split); 1: the extend role alone is a launch of its own and runs ahead of the other roles (run_sweep_x
+                                   // for one population on the LDS tree); 0: one launch per step (run_sweep), or the structured models' two (run_sweep_x)
     unsigned long long* trace;     // pf_set_wg_trace: four words per workgroup of steps [trace_t0, trace_t0 + trace_n) (k_sweep4t only)
     int trace_t0, trace_n, trace_stride;
     int workers;                   // pf_params.count_workers (PipeLaunch::workers)
