@@ -271,6 +271,13 @@ int pf_test_search_lut(const double* tab, int32_t n, uint8_t* lut, int32_t* kbas
  * release stores, an arrival counter per row, polling, coherent loads), with spin_ticks x 10 ns of stand-in work per wavefront
  * and row and the same reduction of all wavefronts' five partials either way.  Microseconds per row in *us_per_row. */
 int pf_probe_handoff(int32_t mode, int32_t rows, int32_t nw, int64_t spin_ticks, double* us_per_row, double* checksum, int32_t device);
+/* testing probe (pf_probe.hip; not part of the filter, no timing): the integer part of a genealogy update at four haplotypes -- which
+ * branch a point (h, lin) selects, and the edit that cuts branch (rp, sb) and re-attaches it at time tc by u_attach -- computed for
+ * `ncases` cases, one per lane, by the general form (form 0) and by the by-case form of the row kernel (form 1).  S[ncases][3] heights,
+ * C[ncases][6] children (rank by rank, child 0 then 1).  out_i[2][ncases][10] = selected rp, sb, samples below the selected branch,
+ * the six children after the edit, changed; out_d[2][ncases][4] = the three heights after the edit, the height of the removed node. */
+int pf_probe_tree_edit(int32_t ncases, const double* S, const int32_t* C, const double* h, const int32_t* lin, const int32_t* rp,
+                        const int32_t* sb, const double* tc, const double* u_attach, int32_t* out_i, double* out_d, int32_t device);
 /* measurement aid: time stamps of every workgroup of the row kernel (k_sweep4t, pf_hip.hip; at most four haplotypes, no focused sampling)
  * for steps [first_step, first_step + n_steps) of the following pf_run / pf_run_many calls led by `h`.  pf_get_wg_trace copies four
  * 64-bit words per workgroup slot and traced step -- start, end (100 MHz clock; 0 0: the step's grid did not use the slot),

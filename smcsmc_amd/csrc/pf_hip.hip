@@ -537,7 +537,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
                 double h, tc;
                 PF_TICK(tk2);
                 PF_ACC(1, tk1, tk2);
-                r_genealogy_update<NM, BIASED, PIPE>(cx, t, &h, &tc);
+                r_genealogy_update<NM, BIASED, PIPE, PIPE && EXACT && NM == 4 && !BIASED && !TREES>(cx, t, &h, &tc);
                 PF_TICK(tk3);
                 PF_ACC(2, tk2, tk3);
 #ifdef PF_STAMPS

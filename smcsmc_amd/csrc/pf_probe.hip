@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "pf_tree_reg.h"
+
 namespace {
 
 constexpr int NPART = 5;
@@ -107,6 +109,46 @@ __global__ __launch_bounds__(256) void k_handoff_resident_wg(double* part, unsig
     if (gw < nw && lane == 0) out[gw] = acc;
 }
 
+// One case per lane: the selection and the edit of a genealogy update at four haplotypes, by the general form (form 0) and by
+// the by-case form of the row kernel (form 1).  oi[form][case][10] = rp, sb, descendants of the cut branch, the six children (rank
+// by rank, child 0 then 1), changed; od[form][case][4] = the three heights and the height of the removed node.
+__global__ __launch_bounds__(256) void k_tree_edit4(int ncases, const double* S, const int32_t* Cin, const double* h, const int32_t* lin,
+                                                    const int32_t* rp, const int32_t* sb, const double* tc, const double* u_attach,
+                                                    int32_t* oi, double* od) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ncases) return;
+#pragma unroll
+    for (int form = 0; form < 2; ++form) {
+        pf::RTree<4> t;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { t.S[r] = S[(size_t)3 * i + r]; t.C0[r] = Cin[(size_t)6 * i + 2 * r]; t.C1[r] = Cin[(size_t)6 * i + 2 * r + 1]; }
+        int s_rp = 0, s_sb = 0;
+        unsigned desc = 0;
+        double Sp = 0.0;
+        bool changed = false;
+        if (form == 0) {
+            pf::RCtx cx = {};
+            cx.n = 4; cx.want_desc = true;
+            unsigned tmask[7];
+            pf::r_update_select<4>(cx, t, 4, h[i], lin[i], false, true, &s_rp, &s_sb, tmask);
+            desc = cx.last_desc;
+            pf::r_update_edit<4>(cx, t, 4, rp[i], sb[i], tc[i], u_attach[i], tmask, &Sp, &changed);
+        } else {
+            pf::r4_select(t, h[i], lin[i], &s_rp, &s_sb, &desc);
+            pf::r4_edit(t, rp[i], sb[i], tc[i], u_attach[i], &Sp, &changed);
+        }
+        int32_t* o = oi + ((size_t)form * ncases + i) * 10;
+        o[0] = s_rp; o[1] = s_sb; o[2] = (int32_t)desc;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) { o[3 + 2 * r] = t.C0[r]; o[4 + 2 * r] = t.C1[r]; }
+        o[9] = changed ? 1 : 0;
+        double* d = od + ((size_t)form * ncases + i) * 4;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) d[r] = t.S[r];
+        d[3] = Sp;
+    }
+}
+
 }  // namespace
 
 // mode 0: `rows` launches of k_handoff_launch back to back on one stream; mode 1: one launch of the resident grid, every wavefront
@@ -161,4 +203,35 @@ extern "C" int pf_probe_handoff(int32_t mode, int32_t rows, int32_t nw, int64_t 
     hipFree(part); hipFree(out); hipFree(arrive); hipFree(err);
     hipEventDestroy(e0); hipEventDestroy(e1); hipStreamDestroy(st);
     return (rc == hipSuccess && herr == 0) ? 0 : -2;
+}
+
+// The two forms of the integer part of a genealogy update at four haplotypes, side by side on cases from the host (k_tree_edit4
+// above; not part of the filter, no timing).  Per case: the tree (S[3] ascending, C[6]), a point (h, lin) for the selection, and a
+// cut branch (rp, sb), a coalescence time tc and the uniform u_attach for the edit.  out_i[2][ncases][10], out_d[2][ncases][4].
+extern "C" int pf_probe_tree_edit(int32_t ncases, const double* S, const int32_t* C, const double* h, const int32_t* lin, const int32_t* rp,
+                                   const int32_t* sb, const double* tc, const double* u_attach, int32_t* out_i, double* out_d, int32_t device) {
+    if (ncases < 1 || ncases > (1 << 24)) return -1;
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    const size_t nc = (size_t)ncases;
+    const void* src[8] = {S, C, h, lin, rp, sb, tc, u_attach};
+    const size_t bytes[8] = {nc * 3 * 8, nc * 6 * 4, nc * 8, nc * 4, nc * 4, nc * 4, nc * 8, nc * 8};
+    void* d[8] = {};
+    int32_t* d_oi = nullptr;
+    double* d_od = nullptr;
+    bool ok = true;
+    for (int k = 0; k < 8 && ok; ++k)
+        ok = hipMalloc(&d[k], bytes[k]) == hipSuccess && hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMalloc(&d_oi, nc * 2 * 10 * 4) == hipSuccess && hipMalloc(&d_od, nc * 2 * 4 * 8) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_tree_edit4, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, 0, ncases, (const double*)d[0], (const int32_t*)d[1],
+                           (const double*)d[2], (const int32_t*)d[3], (const int32_t*)d[4], (const int32_t*)d[5], (const double*)d[6],
+                           (const double*)d[7], d_oi, d_od);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out_i, d_oi, nc * 2 * 10 * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(out_d, d_od, nc * 2 * 4 * 8, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    for (int k = 0; k < 8; ++k) if (d[k]) hipFree(d[k]);
+    if (d_oi) hipFree(d_oi);
+    if (d_od) hipFree(d_od);
+    return ok ? 0 : -2;
 }

@@ -543,74 +543,17 @@ __device__ __forceinline__ void r_sample_point_guided(RCtx& cx, const RTree<NM>&
     *h_out = h;
 }
 
-// One SMC' genealogy update; mirrors genealogy_update() in pf_hip.hip / Filter::genealogy_update in the oracle.
-template <int NM, bool BIASED, bool TAB = false>
-__device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, double* h_out, double* tc_out,
-                                                   double* sp_out = nullptr, bool* changed_out = nullptr) {
-    const int n = cx.n;
-    double h = 0.0;
-    int lin = 0;
-    bool guided_pt = false;
-    // the update's four uniforms: two Philox blocks, drawn together (philox_pair)
-    // TAB: from the draw table when the numbers of exactly this update were requested in time (then the second and the fourth
-    // arrive as logarithms), and the request for the next update goes out at once
-    double u_point, u_refresh, u_attach;
-    bool from_tab = false;
-    if constexpr (TAB) {
-        from_tab = cx.pf_ok && cx.pf_ctr == (unsigned)cx.ctr;
-        cx.draws_log = from_tab;
-        u_point = cx.pf_u0; u_refresh = cx.pf_e1; u_attach = cx.pf_u2; cx.u_nb = cx.pf_e3;
-    }
-    if (!from_tab) {
-        philox_pair(cx.seed, cx.slot, cx.stream, cx.ctr, u_point, u_refresh);
-        philox_pair(cx.seed, cx.slot, cx.stream, cx.ctr + 1, u_attach, cx.u_nb);
-    }
-    cx.ctr += 2;
-    if constexpr (TAB) r_draws_prefetch(cx);
-    PF_GTICK(0);
-    if (BIASED && cx.gK > 0 && cx.stream == 0) {
-        r_sample_point_guided(cx, t, cx.nb > 1, u_point, &h);
-        guided_pt = true;
-    } else if (BIASED) {
-        r_sample_point_biased(cx, t, u_point, &h, &lin);
-        cx.last_rbiw = cx.last_iw;
-    } else {
-        // the slice is found first, the one division follows (inside the unrolled scan every rank would carry its own)
-        double r = u_point * cx.Ltree;
-        double prev = 0.0;
-        double sel_r = 0.0, sel_d = 1.0, sel_prev = 0.0, sel_sr = 0.0;
-        int sel_k = 1;
-        bool done = false;
-#pragma unroll
-        for (int ri = 0; ri < RTree<NM>::NI; ++ri) {
-            if (!done && ri < n - 1) {
-                int k = n - ri;
-                double sr = t.S[ri];
-                double d = sr - prev;
-                double seg = (double)k * d;
-                if (r < seg || ri == n - 2) {
-                    sel_r = r; sel_d = d; sel_prev = prev; sel_sr = sr; sel_k = k;
-                    done = true;
-                } else {
-                    r -= seg;
-                    prev = sr;
-                }
-            }
-        }
-        {
-            double q = sel_r / sel_d;
-            lin = min((int)q, sel_k - 1);
-            h = sel_prev + (q - (double)lin) * sel_d;
-            if (!(h < sel_sr)) h = sel_prev;
-        }
-    }
+// ---------------------------------------------------------------- the integer part of an update, in two pieces
+// The selection: which branch the point (h, lin) sits on -- rank rp of its upper node, child slot sb -- and, when wanted, the samples
+// below that branch (cx.last_desc; `tmask`: those below every node, for the edit of a -arg run).
+template <int NM>
+__device__ __forceinline__ void r_update_select(RCtx& cx, const RTree<NM>& t, int n, double h, int lin, bool guided_pt, bool desc,
+                                                int* rp_out, int* sb_out, unsigned (&tmask)[RTree<NM>::NI + NM]) {
     int rp = 0, sb = 0;
     if (guided_pt) { rp = cx.g_rp; sb = cx.g_sb; }
     else r_lineages_at(t, n, n - 1, h, lin, &rp, &sb);
-    *h_out = h;
     PF_GTICK(1);
-    unsigned tmask[RTree<NM>::NI + NM];          // -arg only: samples below every node id of the tree before the cut
-    if (TAB || cx.want_desc) {
+    if (desc) {
         // (on the rows of k_sweep always: a dozen selects that the scheduler can place beside the search that follows, where
         //  a branch on the flag made them a block of their own in the chain; the local map is on by default)
         // get_descendants (descendants.hpp:22-33) of the cut branch on the tree before it changes: masks bottom-up
@@ -635,10 +578,15 @@ __device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, doubl
             for (int r = 0; r < RTree<NM>::NI; ++r) tmask[r] = below[r];
         }
     }
-    PF_GTICK(2);
-    double tc = r_coalesce_up<NM, TAB>(cx, t, n - 1, n, h, u_refresh);
-    PF_GTICK(4);
-    *tc_out = tc;
+    *rp_out = rp; *sb_out = sb;
+}
+
+// The edit: the branch (rp, sb) is cut, its upper node leaves the tree, and the floating lineage re-attaches at time tc to the
+// slot that u_attach picks (a lineage of the pruned tree, above its root, or back into its own branch: then the tree is restored).
+// Heights are moved and compared, never computed with.
+template <int NM>
+__device__ __forceinline__ void r_update_edit(RCtx& cx, RTree<NM>& t, int n, int rp, int sb, double tc, double u_attach,
+                                              const unsigned (&tmask)[RTree<NM>::NI + NM], double* sp_out, bool* changed_out) {
     double Sp = t.getS(rp);
     int b_id = t.getC(rp, sb), s_id = t.getC(rp, 1 - sb);
     bool p_was_root = (rp == n - 2);
@@ -698,6 +646,188 @@ __device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, doubl
         cx.last_desc_new = dn;
     }
     r_insert_node(t, n, ni, h_ins, b_id, pr_ins, ps_ins, troot);
+}
+
+// ---------------------------------------------------------------- the same two pieces for exactly four haplotypes
+// Three internal nodes, child ids 0..6: the six ids are held as 4-bit fields of one word (field 2 r + s = child s of rank r)
+// and every loop of the general form over ranks and slots becomes a few integer instructions on all fields at once.  Ids stay
+// below 8, so bit 3 of a field is free: adding (8 - x) to every field sets it exactly where the id is >= x, without a carry
+// into the next field.  Same results as the general form on every tree (pf_probe_tree_edit holds one to the other).
+#define PF_R4_ONES 0x111111u
+#define PF_R4_TOPS 0x888888u
+__device__ __forceinline__ unsigned r4_pack(const RTree<4>& t) {
+    return (unsigned)t.C0[0] | ((unsigned)t.C1[0] << 4) | ((unsigned)t.C0[1] << 8) | ((unsigned)t.C1[1] << 12) |
+           ((unsigned)t.C0[2] << 16) | ((unsigned)t.C1[2] << 20);
+}
+// the m-th set bit of `live` upwards (m < 4), as the mask that has it for its lowest bit
+__device__ __forceinline__ unsigned r4_skip(unsigned live, int m) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) live = (m > i) ? (live & (live - 1u)) : live;
+    return live;
+}
+
+__device__ __forceinline__ void r4_select(const RTree<4>& t, double h, int lin, int* rp_out, int* sb_out, unsigned* desc_out) {
+    const unsigned P = r4_pack(t);
+    // r_lineages_at: the lineages at time h are the children of the ranks from R on that are leaves or nodes below rank R
+    const int R = (t.S[0] <= h ? 1 : 0) + (t.S[1] <= h ? 1 : 0) + (t.S[2] <= h ? 1 : 0);
+    const unsigned live = ~(P + (unsigned)(4 - R) * PF_R4_ONES) & (PF_R4_TOPS << (8 * R)) & PF_R4_TOPS;
+    const unsigned m = r4_skip(live, lin);
+    const int f = m ? ((__ffs((int)m) - 1) >> 2) : 0;
+    *rp_out = f >> 1; *sb_out = f & 1;
+    // the samples below the cut branch: rank 0 joins two leaves; a child of rank 1 is a leaf or rank 0; the cut child is a
+    // leaf, rank 0 or rank 1
+    const unsigned x0 = (1u << t.C0[0]) | (1u << t.C1[0]), x1 = (1u << t.C0[1]) | (1u << t.C1[1]);
+    const unsigned below0 = x0 & 15u;
+    const unsigned below1 = (x1 & 15u) | ((x1 & 16u) ? below0 : 0u);
+    const unsigned xb = 1u << ((P >> (4 * f)) & 15u);
+    *desc_out = (xb & 15u) | ((xb & 16u) ? below0 : 0u) | ((xb & 32u) ? below1 : 0u);
+}
+
+__device__ __forceinline__ void r4_edit(RTree<4>& t, int rp, int sb, double tc, double u_attach, double* sp_out, bool* changed_out) {
+    unsigned P = r4_pack(t);
+    const double Sp = rp == 0 ? t.S[0] : (rp == 1 ? t.S[1] : t.S[2]);
+    const int fb = 2 * rp + sb;
+    const unsigned b_id = (P >> (4 * fb)) & 15u, s_id = (P >> (4 * (fb ^ 1))) & 15u;
+    const bool p_was_root = rp == 2;
+    // r_remove_rank: the reference to p (id 4 + rp; at most one, in a rank above) becomes p's other child ...
+    {
+        const unsigned z = ~((P ^ ((unsigned)(4 + rp) * PF_R4_ONES)) + 7u * PF_R4_ONES) & PF_R4_TOPS;      // bit 3 of the fields that hold p
+        const unsigned fm = (z << 1) - (z >> 3);                                                          // those fields whole
+        P = (P & ~fm) | ((s_id * PF_R4_ONES) & fm);
+    }
+    // ... the ranks above rp move down one (b and s are below p: their ids stay) ...
+    const unsigned lo_p = (1u << (8 * rp)) - 1u;
+    P = (P & lo_p) | ((P >> 8) & ~lo_p);
+    const double S0 = rp == 0 ? t.S[1] : t.S[0];
+    const double S1 = rp <= 1 ? t.S[2] : t.S[1];
+    // ... and so do the ids above p's
+    P -= ((P + (unsigned)(3 - rp) * PF_R4_ONES) & PF_R4_TOPS) >> 3;
+    // the pruned tree has ranks 0 and 1 (fields 0..3); its root is p's other child if p was the root, rank 1 otherwise
+    const unsigned troot = p_was_root ? s_id : 5u;
+    const bool le0 = S0 <= tc, le1 = S1 <= tc;
+    const int R = (le0 ? 1 : 0) + (le1 ? 1 : 0);
+    const unsigned A = P + (unsigned)(4 - R) * PF_R4_ONES;               // bit 3: id >= 4 + R
+    const unsigned live = ~A & (0x8888u << (8 * R)) & 0x8888u;          // the lineages of the pruned tree at tc, below its root
+    const int nslots = __popc(live);
+    const bool has_root = troot < 4u ? (tc >= 0.0) : (troot == 4u ? le0 : le1);
+    const bool has_stub = tc < Sp;
+    const int k = nslots + (has_root ? 1 : 0) + (has_stub ? 1 : 0);
+    const int idx = min((int)(u_attach * (double)k), k - 1);
+    *sp_out = Sp;
+    *changed_out = !(has_stub && idx == k - 1);
+    // where the floating lineage re-attaches: a slot, above the root, or back into its own branch -- then p is restored at
+    // time Sp on the slot that holds its other child (or above the pruned root); one insertion serves all three
+    const bool slot = idx < nslots;
+    const bool stub = !slot && !(has_root && idx == nslots);
+    const double h_ins = stub ? Sp : tc;
+    const int Rs = (S0 <= Sp ? 1 : 0) + (S1 <= Sp ? 1 : 0);
+    const unsigned As = P + (unsigned)(4 - Rs) * PF_R4_ONES;
+    const unsigned live_s = ~As & (0x8888u << (8 * Rs)) & 0x8888u;
+    const unsigned is_s = ~((P ^ (s_id * PF_R4_ONES)) + 7u * PF_R4_ONES) & 0x8888u;
+    const unsigned m = slot ? r4_skip(live, idx) : ((stub && !p_was_root) ? (live_s & is_s) : 0u);
+    const bool has_pr = m != 0u;
+    const int sh = has_pr ? (__ffs((int)m) - 4) : 0;                    // bit 4 f + 3 is set: the field starts at 4 f
+    // r_insert_node: the new node takes rank rn, the ids from 4 + rn on move up one ...
+    const int rn = stub ? Rs : R;
+    const unsigned nid = 4u + (unsigned)rn;
+    P += ((stub ? As : A) & 0x8888u) >> 3;
+    const unsigned fl = b_id + (b_id >= nid ? 1u : 0u);
+    const unsigned root_id = troot + (troot >= nid ? 1u : 0u);
+    // ... the slot it lands on now holds the new node, which joins the floating lineage to what the slot held ...
+    const unsigned target = has_pr ? ((P >> sh) & 15u) : root_id;
+    const unsigned fm = has_pr ? (15u << sh) : 0u;
+    P = (P & ~fm) | ((nid << sh) & fm);
+    // ... and the ranks from rn on move up one
+    const unsigned lo_n = (1u << (8 * rn)) - 1u;
+    P = (P & lo_n) | ((P & ~lo_n) << 8) | ((fl | (target << 4)) << (8 * rn));
+    t.S[2] = rn < 2 ? S1 : h_ins;
+    t.S[1] = rn == 1 ? h_ins : (rn < 1 ? S0 : S1);
+    t.S[0] = rn == 0 ? h_ins : S0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { t.C0[r] = (int)((P >> (8 * r)) & 15u); t.C1[r] = (int)((P >> (8 * r + 4)) & 15u); }
+}
+
+// One SMC' genealogy update; mirrors genealogy_update() in pf_hip.hip / Filter::genealogy_update in the oracle.
+// CASE4: exactly four haplotypes, no focused sampling, no -arg masks, on the rows of k_sweep: the selection and the edit by
+// r4_select / r4_edit.
+template <int NM, bool BIASED, bool TAB = false, bool CASE4 = false>
+__device__ __forceinline__ void r_genealogy_update(RCtx& cx, RTree<NM>& t, double* h_out, double* tc_out,
+                                                   double* sp_out = nullptr, bool* changed_out = nullptr) {
+    static_assert(!CASE4 || (NM == 4 && !BIASED && TAB), "the by-case form is that of k_sweep4 at four haplotypes");
+    const int n = cx.n;
+    double h = 0.0;
+    int lin = 0;
+    bool guided_pt = false;
+    // the update's four uniforms: two Philox blocks, drawn together (philox_pair)
+    // TAB: from the draw table when the numbers of exactly this update were requested in time (then the second and the fourth
+    // arrive as logarithms), and the request for the next update goes out at once
+    double u_point, u_refresh, u_attach;
+    bool from_tab = false;
+    if constexpr (TAB) {
+        from_tab = cx.pf_ok && cx.pf_ctr == (unsigned)cx.ctr;
+        cx.draws_log = from_tab;
+        u_point = cx.pf_u0; u_refresh = cx.pf_e1; u_attach = cx.pf_u2; cx.u_nb = cx.pf_e3;
+    }
+    if (!from_tab) {
+        philox_pair(cx.seed, cx.slot, cx.stream, cx.ctr, u_point, u_refresh);
+        philox_pair(cx.seed, cx.slot, cx.stream, cx.ctr + 1, u_attach, cx.u_nb);
+    }
+    cx.ctr += 2;
+    if constexpr (TAB) r_draws_prefetch(cx);
+    PF_GTICK(0);
+    if (BIASED && cx.gK > 0 && cx.stream == 0) {
+        r_sample_point_guided(cx, t, cx.nb > 1, u_point, &h);
+        guided_pt = true;
+    } else if (BIASED) {
+        r_sample_point_biased(cx, t, u_point, &h, &lin);
+        cx.last_rbiw = cx.last_iw;
+    } else {
+        // the slice is found first, the one division follows (inside the unrolled scan every rank would carry its own)
+        double r = u_point * cx.Ltree;
+        double prev = 0.0;
+        double sel_r = 0.0, sel_d = 1.0, sel_prev = 0.0, sel_sr = 0.0;
+        int sel_k = 1;
+        bool done = false;
+#pragma unroll
+        for (int ri = 0; ri < RTree<NM>::NI; ++ri) {
+            if (!done && ri < n - 1) {
+                int k = n - ri;
+                double sr = t.S[ri];
+                double d = sr - prev;
+                double seg = (double)k * d;
+                if (r < seg || ri == n - 2) {
+                    sel_r = r; sel_d = d; sel_prev = prev; sel_sr = sr; sel_k = k;
+                    done = true;
+                } else {
+                    r -= seg;
+                    prev = sr;
+                }
+            }
+        }
+        {
+            double q = sel_r / sel_d;
+            lin = min((int)q, sel_k - 1);
+            h = sel_prev + (q - (double)lin) * sel_d;
+            if (!(h < sel_sr)) h = sel_prev;
+        }
+    }
+    *h_out = h;
+    int rp = 0, sb = 0;
+    unsigned tmask[RTree<NM>::NI + NM];          // -arg only: samples below every node id of the tree before the cut
+    if constexpr (CASE4) { r4_select(t, h, lin, &rp, &sb, &cx.last_desc); PF_GTICK(1); }
+    else r_update_select(cx, t, n, h, lin, guided_pt, TAB || cx.want_desc, &rp, &sb, tmask);
+    PF_GTICK(2);
+    double tc = r_coalesce_up<NM, TAB>(cx, t, n - 1, n, h, u_refresh);
+    PF_GTICK(4);
+    *tc_out = tc;
+    if constexpr (CASE4) {
+        double Sp; bool changed;
+        r4_edit(t, rp, sb, tc, u_attach, &Sp, &changed);
+        if (sp_out) *sp_out = Sp;
+        if (changed_out) *changed_out = changed;
+    } else {
+        r_update_edit(cx, t, n, rp, sb, tc, u_attach, tmask, sp_out, changed_out);
+    }
     PF_GTICK(5);
     cx.Ltree = r_tree_length(t, n);
 }

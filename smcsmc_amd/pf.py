@@ -97,7 +97,7 @@ EXPORTS = [
     "pf_terminal_branch_quantiles",
     "pf_update_segment", "pf_count", "pf_resample", "pf_run", "pf_run_many", "pf_can_run_many", "pf_finish", "pf_sync",
     "pf_num_segments_done", "pf_logl", "pf_get_counts", "pf_get_trace", "pf_get_resample_events",
-    "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
+    "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_probe_tree_edit", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
     "pf_simulate_sites_wide", "pf_median_survival", "pf_median_survival_opts", "pf_test_math", "pf_test_div", "pf_test_uniform", "pf_test_reduce", "pf_test_systematic",
 ]
 
@@ -149,6 +149,7 @@ def load_library(path=None):
     L.pf_get_stats.argtypes = [vp, vp, vp, vp]
     L.pf_get_delay_stats.argtypes = [vp, vp, vp]
     L.pf_probe_handoff.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32]
+    L.pf_probe_tree_edit.argtypes = [C.c_int32] + [vp] * 10 + [C.c_int32]
     L.pf_set_wg_trace.argtypes = [vp, C.c_int64, C.c_int32]
     L.pf_get_wg_trace.argtypes = [vp, vp, C.c_int64, vp]
     L.pf_get_wg_trace.restype = C.c_int64
@@ -268,6 +269,21 @@ def probe_handoff(mode, rows=2000, nw=157, spin_us=0.0, device=0):
     if rc != 0:
         raise PfError("pf_probe_handoff failed (%d)" % rc)
     return us.value, cs.value
+
+
+def probe_tree_edit(S, Cc, h, lin, rp, sb, tc, u_attach, device=0):
+    """The selection and the edit of a genealogy update at four haplotypes by the general form and by the by-case form of the row
+    kernel (pf_probe_tree_edit), one case per row of the inputs.  Returns (out_i[2][n][10], out_d[2][n][4]), form 0 = general."""
+    L = load_library()
+    f8 = lambda a, shape: np.ascontiguousarray(a, dtype=np.float64).reshape(shape)
+    i4 = lambda a, shape: np.ascontiguousarray(a, dtype=np.int32).reshape(shape)
+    n = len(h)
+    a = [f8(S, (n, 3)), i4(Cc, (n, 6)), f8(h, n), i4(lin, n), i4(rp, n), i4(sb, n), f8(tc, n), f8(u_attach, n)]
+    oi = np.zeros((2, n, 10), np.int32); od = np.zeros((2, n, 4), np.float64)
+    rc = L.pf_probe_tree_edit(n, *[x.ctypes.data for x in a], oi.ctypes.data, od.ctypes.data, int(device))
+    if rc != 0:
+        raise PfError("pf_probe_tree_edit failed (%d)" % rc)
+    return oi, od
 
 
 class ParticleFilter:
