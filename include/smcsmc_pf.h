@@ -235,6 +235,16 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
  * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path -- or they
  * differ in shape: haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks) */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
+/* Which runner takes the rows of this handle as it stands now (a look-ahead loaded later changes the answer): pf_run's with many == 0,
+ * pf_run_many's otherwise, where -1 says that pf_run_many refuses the handle.  DESIGN.md, "Which path runs when". */
+#define PF_PATH_GENERAL     0    /* one launch per role and row, two streams (every model; the only path with a look-ahead) */
+#define PF_PATH_TWO_LAUNCH  1    /* k_row + k_decide_ledger (PF_DEBUG_TWO_LAUNCH, or more than 131 072 particles) */
+#define PF_PATH_K_PIPE      2    /* k_pipe (PF_DEBUG_K_PIPE) */
+#define PF_PATH_SWEEP       3    /* k_sweep: every role of a step in one launch */
+#define PF_PATH_SWEEP_SPLIT 4    /* k_sweep4 + k_sweep_blc4: one population, at most four haplotypes, the default */
+#define PF_PATH_SWEEP_XMP   5    /* k_sweep_xmp + k_sweep_blc: structured models, at most 8 haplotypes */
+#define PF_PATH_SWEEP_XL    6    /* k_sweep_xl + k_sweep_blc: one population, 9 to 16 haplotypes, pf_run_many only */
+int pf_get_run_path(pf_handle* h, int many);
 int pf_finish(pf_handle* h);
 int pf_sync(pf_handle* h);
 

@@ -2604,6 +2604,11 @@ const char* pf_last_error(void) { return g_err.c_str(); }
         }                                                                                 \
     } while (0)
 
+// The row pipeline a handle's rings were allocated for at creation (create_impl); run_path() (pf_run.h) picks the runner from this, the debug
+// switches and the look-ahead.  None: two copies of the state, the general kernels or k_row.  Reg: one population, n <= 8, tree in registers
+// (k_sweep*).  Xmp: two to four populations, n <= 8 (k_sweep_xmp).  Xl: one population, 9 <= n <= 16, tree in LDS (k_sweep_xl, pf_run_many only).
+enum class Rings { None, Reg, Xmp, Xl };
+
 struct pf_handle {
     int device = 0;
     hipStream_t stream = nullptr;      // filter stream: k_extend, k_decide, k_resample
@@ -2626,29 +2631,22 @@ struct pf_handle {
     bool finished = false;
     bool fin_pending = false;     // k_count partials not yet folded into the totals
     Windows step_windows;         // windows of the step being processed
-    bool force_lds = false;       // pf_params.debug & PF_DEBUG_FORCE_LDS: use the LDS-tree kernel for every n (testing)
+    int debug = 0;                // pf_params.debug: the PF_DEBUG_* switches that select a path are read from here (run_path)
+    Rings rings = Rings::None;
     bool wide = false;            // one population on the wide kernels of pf_wide.hip: nsam > PF_NMAX, or PF_DEBUG_FORCE_WIDE (testing)
-    bool no_fuse = false;         // PF_DEBUG_NO_FUSE: always run k_resample as its own kernel (testing)
     bool no_count = false;        // PF_DEBUG_NO_COUNT: no lagged counting, no ledger upkeep (profiling)
-    bool two_launch_rows = false; // PF_DEBUG_TWO_LAUNCH: the round-1 row pipeline (k_row + k_decide_ledger) instead of k_pipe
-    bool pipe = false;            // the single-launch pipeline applies (one population, n <= 8; rings allocated)
-    size_t smem_pipe = 0;
+    size_t smem_pipe = 0;         // dynamic LDS of the row pipeline's launches (rings != None)
     int ncw = 0;                  // count workgroups per epoch in the row pipeline (pf_params.count_wgs): the most a column gets
     int ledger_wgs = 192;         // workgroups per step that re-base the older generations' run lists after a resampling (beside one per particle block)
     int workers = 0;              // pf_params.count_workers: workgroups per step that take the ledger and count items off a queue (0: one workgroup per item)
     std::vector<int> cw_off;      // [E + 1] first count workgroup of the j-th column, oldest epoch first (KArgs::cw_off)
-    bool split_many = false;      // a step as two launches (run_sweep_split; not with PF_DEBUG_ONE_LAUNCH)
-    int split_batch = 0;          // ... the second launches enqueued in batches of this many steps behind one completion signal (0: chosen by the runner)
+    int split_batch = 0;          // run_sweep_split: the second launches enqueued in batches of this many steps behind one completion signal (0: chosen by the runner)
     unsigned long long* d_trace = nullptr;   // pf_set_wg_trace (leader of a pf_run_many call): four words per workgroup and step
     size_t trace_words = 0;
     int trace_t0 = 0, trace_n = 0, trace_stride = 0, trace_grid[3] = {0, 0, 0};
-    bool pipe_mp = false;         // structured models on the row pipeline: extend launches on the filter stream, the other roles on the counting stream
-    size_t smem_sweep_x = 0;
-    bool pipe_lds = false;        // one population, 9 to 16 haplotypes: pf_run_many takes the chunks on the row pipeline with the tree in LDS
-                                  // (k_sweep_xl + k_sweep_blc, run_sweep_x); pf_run on one handle keeps the general kernels
+    size_t smem_sweep_x = 0;      // dynamic LDS of the extend launch of run_sweep_x (rings Xmp, Xl)
     std::vector<hipEvent_t> ev_x, ev_blc;   // completion of the last 16 extend / bookkeeping-ledger-count launches
     bool no_spec_stage = false;   // PF_DEBUG_NO_SPEC_STAGE
-    bool use_k_pipe = false;      // PF_DEBUG_K_PIPE: rows through k_pipe (argument block by value, one chunk per launch) instead of k_sweep
     SweepChunk* d_sweep = nullptr; // device table of the chunks this handle leads through k_sweep
     int d_sweep_cap = 0;
     std::vector<SweepChunk> h_sweep;
@@ -2860,16 +2858,27 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
         if (gen_cap > 0x7fffffffLL / 2) gen_cap = 0x7fffffffLL / 2;
         h->max_trace_events = (int)gen_cap;
     }
-    h->force_lds = (p->debug & PF_DEBUG_FORCE_LDS) != 0;
-    h->no_fuse = (p->debug & PF_DEBUG_NO_FUSE) != 0;
+    h->debug = p->debug;
     h->no_count = (p->debug & PF_DEBUG_NO_COUNT) != 0;
-    h->two_launch_rows = (p->debug & PF_DEBUG_TWO_LAUNCH) != 0;
-    h->use_k_pipe = (p->debug & PF_DEBUG_K_PIPE) != 0;
     h->no_spec_stage = (p->debug & PF_DEBUG_NO_SPEC_STAGE) != 0;
     h->split_batch = (p->debug >> 16) & 15;       // (bits 16-19 of debug: tuning experiments; 0 = four with several chunks, one with one)
-    // one population, at most four haplotypes, no focused sampling, no -arg: a step is two launches (run_sweep_split) unless the switch says one
-    h->split_many = !(p->debug & PF_DEBUG_ONE_LAUNCH) && P == 1 && n <= 4 && m->n_bias_heights == 0 && m->n_rate_segments == 0 && !(p->flags & 2) &&
-                    !(p->debug & (PF_DEBUG_K_PIPE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_NO_FUSE));
+    // What this handle is allocated for, decided here and nowhere else: the rings of a row pipeline (sixteen copies of the state, the
+    // second run-list copy, the decision rings, the count columns' table, smem_pipe) and the draw table.
+    const size_t nc = (size_t)((Np + 63) / 64);
+    const bool fits = Np <= 131072 && !wide;      // beyond that the decision tables outgrow the default dynamic LDS
+    const bool plain = !(p->flags & 2) && !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE));     // no -arg, no switch to another path
+    if (P == 1 && n <= 8 && fits) h->rings = Rings::Reg;      // (with a switch or a look-ahead that takes the rows elsewhere the rings are there, unused)
+    // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_x)
+    else if (P > 1 && n <= 8 && fits && plain) h->rings = Rings::Xmp;
+    // one population on the LDS tree, several chunks in lockstep (pf_run_many): the same rings, the extend role k_sweep_xl.  Not with a
+    // generation ring too short for an extend role that runs ahead of the counts (what pf_create refuses for structured models; here the
+    // general kernels serve such a handle as before)
+    else if (P == 1 && n > 8 && n <= PF_NMAX && fits && plain && gen_cap >= PF_RING + 4 && !(p->debug & PF_DEBUG_TWO_LAUNCH) && lds_pipe_tables_fit(n, (int)nc))
+        h->rings = Rings::Xl;
+    const bool has_rings = h->rings != Rings::None;
+    // draw table of k_sweep (draw_role)
+    const bool draw_table = h->rings == Rings::Reg && !(p->debug & (PF_DEBUG_K_PIPE | PF_DEBUG_NO_DRAW_TABLE));
+    if (has_rings) h->smem_pipe = ((size_t)(2 * PF_EPAD + E + 2 * PF_BIAS_MAX + 3) + pipe_lds_doubles((int)nc)) * 8;
     // (several chunks per GPU -- the caller set count_wgs -- : on the rows that do not resample, nine in ten, these workgroups find nothing to do and
     // leave after 2 us of a slot each; with 32 instead of 192 eight chunks gain 3 %, one chunk is the same either way: 28.7 us per row)
     h->ledger_wgs = p->count_wgs > 0 ? 32 : std::max(16, std::min(PF_LEDGER_BLOCKS, 192));
@@ -2950,18 +2959,9 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
         hipStreamSynchronize(h->stream);
         A.app_delays = dad;
     }
-    h->pipe = P == 1 && n <= 8 && Np <= 131072 && !wide;      // beyond that the decision tables outgrow the default dynamic LDS
-    // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_x)
-    h->pipe_mp = P > 1 && n <= 8 && Np <= 131072 && !(p->flags & 2) && !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE));
-    // one population on the LDS tree, several chunks in lockstep (pf_run_many): the same rings, the extend role k_sweep_xl.  Not with
-    // -arg, not with a debug switch that selects a path, and not with a generation ring too short for an extend role that runs
-    // ahead of the counts (what pf_create refuses for structured models; here the general kernels serve such a handle as before)
-    h->pipe_lds = P == 1 && n > 8 && n <= PF_NMAX && Np <= 131072 && !wide && !(p->flags & 2) && gen_cap >= PF_RING + 4 &&
-                  !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_FORCE_WIDE)) &&
-                  lds_pipe_tables_fit(n, (int)((Np + 63) / 64));
-    A.blk_gran = h->pipe_mp ? 4 : 1;
+    A.blk_gran = h->rings == Rings::Xmp ? 4 : 1;
     {
-        const size_t K = (h->pipe || h->pipe_mp || h->pipe_lds) ? PF_RING : 2;               // copies of the particle state (KArgs::st0)
+        const size_t K = has_rings ? PF_RING : 2;               // copies of the particle state (KArgs::st0)
         A.nslots = (int)K;
         DState& st = A.st0;
         rc |= dalloc(h, &st.S, K * (size_t)(n - 1) * Np);
@@ -3011,8 +3011,8 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     }
     rc |= dalloc(h, &A.rng_ctr, Np);
     A.dt_tab = nullptr; A.dt_filled = nullptr; A.dt_ctr = nullptr;
-    if (h->pipe && !h->use_k_pipe && !(p->debug & PF_DEBUG_NO_DRAW_TABLE)) {
-        // draw table of k_sweep (draw_role): 512 bytes per slot
+    if (draw_table) {
+        // 512 bytes per slot
         rc |= dalloc(h, &A.dt_tab, (size_t)2 * PF_DRAW_RING * Np);
         rc |= dalloc(h, &A.dt_filled, (size_t)2 * Np);
         rc |= dalloc(h, &A.dt_ctr, (size_t)2 * Np);
@@ -3038,9 +3038,8 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     rc |= dalloc(h, &A.run_st, (size_t)A.Gcap * Np);
     rc |= dalloc(h, &A.run_anc, (size_t)A.Gcap * Np);
     rc |= dalloc(h, &A.nruns, A.Gcap);
-    const size_t nc = (size_t)((Np + 63) / 64);
     A.nc = (int)nc;
-    if (h->pipe || h->pipe_mp || h->pipe_lds) {
+    if (has_rings) {
         rc |= dalloc(h, &A.run_st2, (size_t)A.Gcap * Np);
         rc |= dalloc(h, &A.run_anc2, (size_t)A.Gcap * Np);
         rc |= dalloc(h, &A.nruns2, A.Gcap);
@@ -3049,7 +3048,6 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
         rc |= dalloc(h, &A.rg_cpost, PF_RING * nc); rc |= dalloc(h, &A.rg_csq, PF_RING * nc); rc |= dalloc(h, &A.rg_cpil, PF_RING * nc);
         rc |= dalloc(h, &A.rg_cpp, PF_RING * nc); rc |= dalloc(h, &A.rg_cmx1, PF_RING * nc); rc |= dalloc(h, &A.rg_coffp, PF_RING * nc);
         rc |= dalloc(h, &A.rg_dpend, PF_RING * nc); rc |= dalloc(h, &A.rg_blkcnt, PF_RING * (size_t)h->nblocks * 4);
-        h->smem_pipe = ((size_t)(2 * PF_EPAD + E + 2 * PF_BIAS_MAX + 3) + pipe_lds_doubles((int)nc)) * 8;
     }
     rc |= dalloc(h, &A.chunk_post, nc); rc |= dalloc(h, &A.chunk_sq, nc); rc |= dalloc(h, &A.chunk_pil, nc);
     rc |= dalloc(h, &A.scan1, Np); rc |= dalloc(h, &A.chunk_off, nc); rc |= dalloc(h, &A.l2scan, nc);
@@ -3070,7 +3068,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     // workgroups 32.9 us per row, 16: 38.7, 8: 53.7, 4: 91.4, 2: 168 -- profiles/round3/count_wgs.md)
     h->ncw = p->count_wgs > 0 ? std::min<int>(p->count_wgs, h->nblocks) : h->nblocks;
     // (the queue has one kernel instance so far: one population, at most four haplotypes, no focused sampling, no -arg, single launch per step)
-    h->workers = (h->pipe && !h->use_k_pipe && P == 1 && n <= 4 && !(m->n_bias_heights > 0 || m->n_rate_segments > 0) && !(p->flags & 2)) ? std::max(0, std::min(p->count_workers, 4096)) : 0;
+    h->workers = (h->rings == Rings::Reg && !(p->debug & PF_DEBUG_K_PIPE) && n <= 4 && !(m->n_bias_heights > 0 || m->n_rate_segments > 0) && !(p->flags & 2)) ? std::max(0, std::min(p->count_workers, 4096)) : 0;
     {
         // count workgroups per epoch column of the row pipeline: the tasks of an epoch are the live ancestors of the generations in its
         // window, about Np / (1 + depth), depth = generations between window and front, i.e. in proportion to its lag: a column whose
@@ -3088,7 +3086,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
             h->cw_off[j + 1] = h->cw_off[j] + w;
         }
         int* dcw = nullptr;
-        if (h->pipe || h->pipe_mp || h->pipe_lds) {
+        if (has_rings) {
             rc |= dalloc(h, &dcw, E + 1);
             if (!rc) { hipMemcpyAsync(dcw, h->cw_off.data(), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, h->stream); hipStreamSynchronize(h->stream); }
             // (with every column at full width the kernels compute column and workgroup from the index: no table)
@@ -3112,19 +3110,21 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     }
     // structured models: the LDS-tree kernels serve the prior tree and calibration for every n, the row kernel is the
     // register-tree one for n <= 8
-    const bool lds_rows = P > 1 && (n > 8 || h->force_lds);
+    const bool lds_rows = P > 1 && (n > 8 || (p->debug & PF_DEBUG_FORCE_LDS));
     if (h->smem > 160 * 1024 || (P > 1 && pf_mp_prepare(h->smem, A.mcap)) ||
         (P > 1 && !lds_rows && pf_mp_reg_smem_bytes(E, P, A.mcap) > 160 * 1024)) {
         pf_destroy(h);
         return fail(P > 1 ? "pf_create: the local-tree state (tree, epoch tables and pf_params.mig_cap migration events per lane) does not fit the LDS of one workgroup"
                           : "pf_create: the local-tree state does not fit the LDS of one workgroup");
     }
-    if (h->pipe_mp) {
+    // a row pipeline the device then refuses: the rings stay, the general kernels take the rows (and pf_run_many refuses)
+    auto demote = [&] { h->rings = Rings::None; };
+    if (h->rings == Rings::Xmp) {
         h->smem_sweep_x = pf_mp_sweep_smem_bytes(E, P, A.mcap, A.nc);
-        if (pf_mp_sweep_prepare(h->smem_sweep_x)) h->pipe_mp = false;        // the event lists and the decision tables do not fit together: the two-stream path
+        if (pf_mp_sweep_prepare(h->smem_sweep_x)) demote();                  // the event lists and the decision tables do not fit together: the two-stream path
     }
-    if (h->pipe_lds) {
-        // k_sweep_xl: the LDS of k_extend (the decision tables lie in the tree columns); the rings stay, pf_run_many refuses
+    if (h->rings == Rings::Xl) {
+        // k_sweep_xl: the LDS of k_extend (the decision tables lie in the tree columns)
         h->smem_sweep_x = h->smem;
         // (the attribute belongs to the kernel, not to the handle: the largest any handle of the process has asked for, so that a
         // handle of twelve haplotypes made after one of sixteen does not lower it)
@@ -3136,7 +3136,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
             (hipFuncSetAttribute((const void*)k_sweep_xl<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
              hipFuncSetAttribute((const void*)k_sweep_xl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)) {
             (void)hipGetLastError();
-            h->pipe_lds = false;
+            demote();
         }
     }
     return h;
@@ -3308,761 +3308,7 @@ int pf_load_segments(pf_handle* h, const pf_segments* sg) {
     return 0;
 }
 
-// the particle-independent window rule of extract_and_update_count (count.cpp:363-385)
-static Windows host_windows(pf_handle* h, double current_base, bool end_data) {
-    const int E = h->E;
-    Windows W;
-    memset(&W, 0, sizeof(W));
-    W.first = E;
-    W.end_data = end_data ? 1 : 0;
-    for (int e = 0; e < E; ++e) {
-        double lagging = end_data ? 0.0 : h->h_lags[e];
-        double x_end = current_base - lagging;
-        W.a[e] = h->h_counted_to[e];
-        if ((x_end - h->h_counted_to[e]) < lagging * 0.1 && W.first > e) {
-            W.b[e] = h->h_counted_to[e];
-        } else {
-            W.b[e] = x_end;
-            W.first = std::min(W.first, e);
-        }
-    }
-    for (int e = 0; e < E; ++e) h->h_counted_to[e] = W.b[e];
-    return W;
-}
-
-static bool timing_on(pf_handle* h, long long s) { return h->timing_period > 0 && (s % h->timing_period) == 0; }
-
-static Windows no_windows(pf_handle* h) {
-    Windows W;
-    memset(&W, 0, sizeof(W));
-    W.first = h->E;
-    for (int e = 0; e < h->E; ++e) { W.a[e] = h->h_counted_to[e]; W.b[e] = h->h_counted_to[e]; }
-    return W;
-}
-
-// the register-tree kernels can complete the previous row while loading the particle (fused k_resample)
-static bool extend_can_fuse(const pf_handle* h) {
-    return h->P == 1 && h->n <= 8 && !h->force_lds && !h->wide && !h->no_fuse && h->A.apf == 0;
-}
-
-static int launch_extend(pf_handle* h, long long s, int fuse = 0) {
-    const bool t = timing_on(h, s);
-    {
-        Timed tm(h, 0, t);
-        const size_t smem_reg = (size_t)(2 * PF_EPAD + h->E + 2 * PF_BIAS_MAX + 3) * 8;
-        const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
-        if (h->P > 1)
-            pf_mp_launch_extend(h->A, s, h->smem, h->stream, h->force_lds, fuse);
-        else if (h->wide)
-            pf_wide_launch_extend(h->A, s, h->smem, h->stream);
-        else if (h->n <= 4 && biased && !h->force_lds)
-        {
-            if (h->A.rec_trees) hipLaunchKernelGGL((k_extend_reg<4, true, true>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-            else hipLaunchKernelGGL((k_extend_reg<4, true>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-        }
-        else if (h->n <= 8 && biased && !h->force_lds)
-        {
-            if (h->A.rec_trees) hipLaunchKernelGGL((k_extend_reg<8, true, true>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-            else hipLaunchKernelGGL((k_extend_reg<8, true>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-        }
-        else if (h->n <= 4 && !h->force_lds)
-        {
-            if (h->A.rec_trees) hipLaunchKernelGGL((k_extend_reg<4, false, true>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-            else hipLaunchKernelGGL((k_extend_reg<4, false>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-        }
-        else if (h->n <= 8 && !h->force_lds)
-        {
-            if (h->A.rec_trees) hipLaunchKernelGGL((k_extend_reg<8, false, true>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-            else hipLaunchKernelGGL((k_extend_reg<8, false>), dim3(h->nblocks), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse);
-        }
-        else
-            hipLaunchKernelGGL(k_extend, dim3(h->nblocks), dim3(PF_BS), h->smem, h->stream, h->A, s);
-    }
-    if (check_launch("k_extend")) return -1;
-    if (h->A.apf > 0) {
-        hipLaunchKernelGGL(k_lookahead, dim3(h->nblocks), dim3(PF_BS), h->smem_la, h->stream, h->A, s);
-        return check_launch("k_lookahead");
-    }
-    return 0;
-}
-
-static int launch_decide(pf_handle* h, long long s, int mode, const Windows& W) {
-    const bool t = timing_on(h, s);
-    // k_decide rewrites what k_count / k_ledger read
-    // (window generations, offspring tables): it must not start before the counting stream is done with them
-    if (h->ev_cnt) hipStreamWaitEvent(h->stream, h->ev_cnt, 0);
-    {
-        Timed tm(h, 1, t);
-        if (!h->no_count) {
-            // the event the counting stream waits on is the kernel's own completion signal (no marker packet between
-            // this kernel and the next row's extend)
-            h->ev_dec = next_sync_event(h);
-            hipExtLaunchKernelGGL(k_decide, dim3(h->nblocks + 1), dim3(PF_BS), 0, h->stream, nullptr, h->ev_dec, 0, h->A, s, mode, W, h->nblocks);
-        } else {
-            hipLaunchKernelGGL(k_decide, dim3(h->nblocks + 1), dim3(PF_BS), 0, h->stream, h->A, s, mode, W, h->nblocks);
-        }
-    }
-    return check_launch("k_decide");
-}
-
-static int launch_count(pf_handle* h, long long s, const Windows& W) {
-    if (h->no_count) return 0;
-    const int first = W.first;
-    if (first >= h->E) return 0;
-    const bool t = timing_on(h, s);
-    if (h->ev_dec) hipStreamWaitEvent(h->cstream, h->ev_dec, 0);
-    {
-        Timed tm(h, 2, t, h->cstream);
-        const dim3 grid(h->nblocks, h->E - first), blk(PF_BS);
-#define PF_LAUNCH_COUNT(NMV, PV) hipLaunchKernelGGL((k_count<NMV, PV>), grid, blk, 0, h->cstream, h->A, first, W)
-        const int P = h->P;
-        if (P == 1 && h->wide) {
-            PF_LAUNCH_COUNT(PF_NMAX_WIDE, 1);                  // the wide records (descendants in their own word)
-        } else if (P == 1) {
-            if (h->n <= 4) PF_LAUNCH_COUNT(4, 1);
-            else if (h->n <= 8) PF_LAUNCH_COUNT(8, 1);
-            else if (h->pipe_lds && h->A.cw_off)               // count_wgs set: the columns as wide as pf_run_many makes them
-                hipLaunchKernelGGL((k_count_cw<PF_NMAX, 1>), dim3(h->ncw, h->E - first), blk, 0, h->cstream, h->A, first, W);
-            else PF_LAUNCH_COUNT(PF_NMAX, 1);
-        } else if (P == 2) {
-            if (h->n <= 4) PF_LAUNCH_COUNT(4, 2);
-            else if (h->n <= 8) PF_LAUNCH_COUNT(8, 2);
-            else PF_LAUNCH_COUNT(PF_NMAX, 2);
-        } else {
-            if (h->n <= 8) PF_LAUNCH_COUNT(8, PF_PMAX);
-            else PF_LAUNCH_COUNT(PF_NMAX, PF_PMAX);
-        }
-#undef PF_LAUNCH_COUNT
-        h->fin_pending = true;
-    }
-    return check_launch("k_count");
-}
-
-// ancestor-ledger maintenance of this step (no-op unless the step resampled); closes the step on the counting stream
-static int launch_ledger(pf_handle* h, long long s) {
-    (void)s;
-    if (h->no_count) return 0;
-    if (h->ev_dec) hipStreamWaitEvent(h->cstream, h->ev_dec, 0);
-    hipLaunchKernelGGL(k_ledger, dim3(h->nblocks + PF_LEDGER_BLOCKS), dim3(PF_BS), 0, h->cstream, h->A, h->nblocks);
-    h->ev_cnt = next_sync_event(h);
-    hipEventRecord(h->ev_cnt, h->cstream);
-    return check_launch("k_ledger");
-}
-
-static int launch_resample(pf_handle* h, long long s) {
-    const bool t = timing_on(h, s);
-    {
-        Timed tm(h, 3, t);
-        hipLaunchKernelGGL(k_resample, dim3(h->nblocks), dim3(PF_BS), 0, h->stream, h->A, s, h->nblocks);
-    }
-    return check_launch("k_resample");
-}
-
-static double seg_pos(pf_handle* h, long long s) {
-    return std::min(h->h_seg_start[s] + h->h_seg_len[s], h->h_L);
-}
-
-// Single steps.  update and count of one segment share the window set: pf_update_segment evaluates the
-// window rule for segment s (the bookkeeping workgroup of k_decide needs it), pf_count launches the sums.
-int pf_update_segment(pf_handle* h, int64_t s) {
-    HIPCHK(hipSetDevice(h->device));
-    if (s < 0 || s >= h->n_segs) { g_err = "segment index out of range"; return -1; }
-    h->step_windows = host_windows(h, seg_pos(h, s), false);
-    h->A.sp = (int)(s & 1);
-    if (launch_extend(h, s)) return -1;
-    return launch_decide(h, s, 0, h->step_windows);
-}
-int pf_count(pf_handle* h, int64_t s, int end_data) {
-    HIPCHK(hipSetDevice(h->device));
-    (void)end_data;
-    return launch_count(h, s, h->step_windows);
-}
-int pf_resample(pf_handle* h, int64_t s) {
-    HIPCHK(hipSetDevice(h->device));
-    int rc = launch_resample(h, s);
-    if (!rc) rc = launch_ledger(h, s);
-    h->seg_done = std::max<long long>(h->seg_done, s + 1);
-    return rc;
-}
-
-// keep the timing-event pool bounded without stalling the queue: only harvest finished spans
-static void trim_spans(pf_handle* h) {
-    if (h->spans.empty() || hipEventQuery(h->spans.front().b) != hipSuccess) return;
-    size_t done = 0;
-    while (done < h->spans.size() && hipEventQuery(h->spans[done].b) == hipSuccess) ++done;
-    std::vector<pf_handle::Span> rest(h->spans.begin() + done, h->spans.end());
-    h->spans.resize(done);
-    harvest_spans(h);
-    h->spans = rest;
-}
-
-// The single-stream pipeline of the register-tree kernels.  Per row two launches and nothing else:
-//   k_row(s)           extend over row s (completing row s-1 while loading)  ||  lagged counts of row s-1
-//   k_decide_ledger(s) normalisation / ESS / offspring table of row s        ||  ancestor-ledger upkeep of row s-1
-// Stream order provides every dependency; the two halves of each launch touch disjoint (immutable or parity
-// double-buffered) data.  The last row of the call is flushed with the stand-alone kernels so that the state is
-// whole when the call returns.
-template <int NM, bool BIASED>
-static void launch_row(pf_handle* h, long long s, int fuse, int count_first, const Windows& Wprev) {
-    const size_t smem_reg = (size_t)(2 * PF_EPAD + h->E + 2 * PF_BIAS_MAX + 3) * 8;
-    const int nb = h->nblocks;
-    const int ncount = count_first < h->E ? nb * (h->E - count_first) : 0;
-    if (h->A.rec_trees)
-        hipLaunchKernelGGL((k_row<NM, BIASED, false, true>), dim3(nb + ncount), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse, nb, count_first, Wprev);
-    else if (h->n == NM)
-        hipLaunchKernelGGL((k_row<NM, BIASED, true>), dim3(nb + ncount), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse, nb, count_first, Wprev);
-    else
-        hipLaunchKernelGGL((k_row<NM, BIASED, false>), dim3(nb + ncount), dim3(PF_BS), smem_reg, h->stream, h->A, s, fuse, nb, count_first, Wprev);
-}
-
-static int run_single_stream(pf_handle* h, long long s_begin, long long s_end) {
-    const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
-    bool pending = false;             // counts + ledger of the previous row still to be launched
-    Windows Wprev = no_windows(h);
-    // whatever the two-stream kernels of an earlier call left on the counting stream must be done first
-    if (h->ev_cnt) { hipStreamWaitEvent(h->stream, h->ev_cnt, 0); h->ev_cnt = nullptr; }
-    for (long long s = s_begin; s < s_end; ++s) {
-        h->step_windows = host_windows(h, seg_pos(h, s), false);
-        h->A.sp = (int)(s & 1);
-        const bool t = timing_on(h, s);
-        {
-            Timed tm(h, 0, t);
-            const int cf = pending ? Wprev.first : h->E;
-            const int fuse = s > s_begin ? 1 : 0;
-            if (h->n <= 4 && biased) launch_row<4, true>(h, s, fuse, cf, Wprev);
-            else if (h->n <= 4) launch_row<4, false>(h, s, fuse, cf, Wprev);
-            else if (biased) launch_row<8, true>(h, s, fuse, cf, Wprev);
-            else launch_row<8, false>(h, s, fuse, cf, Wprev);
-            if (pending && Wprev.first < h->E) h->fin_pending = true;
-        }
-        if (check_launch("k_row")) return -1;
-        {
-            Timed tm(h, 1, t);
-            // decide and ledger workgroups each hold ~120 KB of LDS, one per CU: keep the launch within one wave of 256 CUs
-            const int lroom = 256 - (h->nblocks + 1) - h->nblocks;
-            const int lnbt = pending ? h->nblocks + std::max(16, std::min(PF_LEDGER_BLOCKS, lroom)) : 0;
-            hipLaunchKernelGGL(k_decide_ledger, dim3(h->nblocks + 1 + lnbt), dim3(PF_LEDGER_MAXT), 0, h->stream, h->A, s, 0, h->step_windows,
-                               h->nblocks, lnbt);
-        }
-        if (check_launch("k_decide")) return -1;
-        pending = true;
-        Wprev = h->step_windows;
-        h->seg_done = s + 1;
-        const bool last = (s + 1 == s_end) || (h->h_seg_start[s] + h->h_seg_len[s] >= h->h_L);
-        if (last) {
-            // flush: complete the row, then its counts and ledger with the stand-alone kernels (same stream)
-            if (launch_resample(h, s)) return -1;
-            if (Wprev.first < h->E) {
-                const dim3 grid(h->nblocks, h->E - Wprev.first), blk(PF_BS);
-                if (h->n <= 4) hipLaunchKernelGGL((k_count<4, 1>), grid, blk, 0, h->stream, h->A, Wprev.first, Wprev);
-                else hipLaunchKernelGGL((k_count<8, 1>), grid, blk, 0, h->stream, h->A, Wprev.first, Wprev);
-                h->k_launches[2] += 1;
-                h->fin_pending = true;
-            }
-            hipLaunchKernelGGL(k_ledger, dim3(h->nblocks + PF_LEDGER_BLOCKS), dim3(PF_BS), 0, h->stream, h->A, h->nblocks);
-            if (check_launch("k_count/k_ledger")) return -1;
-            break;
-        }
-        if ((s & 1023) == 1023) trim_spans(h);
-    }
-    return 0;
-}
-
-// The single-launch pipeline (k_pipe): per row ONE launch on one stream, see the kernel's header.  Rows [s_begin, s_end)
-// are followed by two flush launches (completion of the last row with the bookkeeping / ledger / counts still owed)
-// after which the handle's state is in the form the general kernels expect.
-template <int NM, bool BIASED>
-static void launch_pipe(pf_handle* h, long long s, const PipeLaunch& PL, int ncount_wg, const Windows& Wb) {
-    const dim3 grid((unsigned)(PL.nb + 1 + PL.nL + ncount_wg)), blk(PF_BS);
-    if (h->A.rec_trees)
-        hipLaunchKernelGGL((k_pipe<NM, BIASED, false, true>), grid, blk, h->smem_pipe, h->stream, h->A, s, PL, Wb);
-    else if (h->n == NM)
-        hipLaunchKernelGGL((k_pipe<NM, BIASED, true, false>), grid, blk, h->smem_pipe, h->stream, h->A, s, PL, Wb);
-    else
-        hipLaunchKernelGGL((k_pipe<NM, BIASED, false, false>), grid, blk, h->smem_pipe, h->stream, h->A, s, PL, Wb);
-}
-
-static int run_pipeline(pf_handle* h, long long s_begin, long long s_end) {
-    if (s_begin >= s_end) return 0;
-    const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
-    const int nb = h->nblocks, E = h->E;
-    // whatever the two-stream kernels of an earlier call left on the counting stream must be done first
-    if (h->ev_cnt) { hipStreamWaitEvent(h->stream, h->ev_cnt, 0); h->ev_cnt = nullptr; }
-    hipLaunchKernelGGL(k_pipe_seed, dim3(1), dim3(1), 0, h->stream, h->A, (int)((s_begin + PF_RING - 1) & (PF_RING - 1)));
-    Windows W1 = no_windows(h), W2 = no_windows(h);      // windows of rows s-1 and s-2
-    long long last = s_begin - 1;                        // last row extended so far
-    const int nL_full = nb + h->ledger_wgs;
-    auto dispatch = [&](long long s, const PipeLaunch& PL, int ncount_wg, const Windows& Wb) {
-        if (h->n <= 4 && biased) launch_pipe<4, true>(h, s, PL, ncount_wg, Wb);
-        else if (h->n <= 4) launch_pipe<4, false>(h, s, PL, ncount_wg, Wb);
-        else if (biased) launch_pipe<8, true>(h, s, PL, ncount_wg, Wb);
-        else launch_pipe<8, false>(h, s, PL, ncount_wg, Wb);
-    };
-    // one launch: extend row s (or only complete row s-1 / nothing), bookkeeping of row s-1, ledger + counts of row s-2
-    auto launch = [&](long long s, bool extend, bool have_b, bool have_lc, int set_cur) -> int {
-        PipeLaunch PL;
-        memset(&PL, 0, sizeof(PL));
-        PL.nb = nb; PL.nblk = nb;
-        PL.row.extend = extend ? 1 : 0;
-        PL.row.complete = (s > s_begin && s - 1 <= last && (extend || have_b)) ? 1 : 0;
-        if (!extend && !have_b) PL.row.complete = 0;
-        PL.row.slot_prev = PL.row.complete ? (int)((s - 1) & (PF_RING - 1)) : -1;
-        PL.row.slot_out = (int)(s & (PF_RING - 1));
-        PL.row.pos_prev = (PL.row.complete && s > s_begin) ? seg_pos(h, s - 1) : 0.0;   // row s - 1 of the second flush step may lie past the table
-        PL.b_slot = have_b ? (int)((s - 1) & (PF_RING - 1)) : -1;
-        PL.b_row = s - 1;
-        PL.b_pos = have_b ? seg_pos(h, s - 1) : 0.0;
-        PL.b_set_cur = set_cur;
-        PL.lc_slot = (have_lc && !h->no_count) ? (int)((s - 2) & (PF_RING - 1)) : -1;
-        PL.live_slot = (int)((s - 1) & (PF_RING - 1));
-        PL.nL = PL.lc_slot >= 0 ? nL_full : 0;
-        PL.ncw = h->ncw;
-        PL.nT = 0; PL.row.draws = 0;               // k_pipe keeps no draw table
-        const int ncount_wg = (PL.lc_slot >= 0 && W2.first < E) ? h->cw_off[E - W2.first] : 0;
-        if (ncount_wg > 0) h->fin_pending = true;
-        const bool t = extend && timing_on(h, s);
-        {
-            Timed tm(h, 0, t);
-            if (!extend) h->k_launches[0] -= 1;          // flush launches are not rows
-            dispatch(s, PL, ncount_wg, W1);
-        }
-        return check_launch("k_pipe");
-    };
-    long long s = s_begin;
-    for (; s < s_end; ++s) {
-        if (launch(s, true, s > s_begin, s > s_begin + 1, -1)) return -1;
-        last = s;
-        W2 = W1;
-        W1 = host_windows(h, seg_pos(h, s), false);
-        h->step_windows = W1;
-        h->seg_done = s + 1;
-        if ((s & 1023) == 1023) trim_spans(h);
-        if (h->h_seg_start[s] + h->h_seg_len[s] >= h->h_L) { ++s; break; }      // smcsmc.cpp:353-356
-    }
-    // flush 1: complete row `last` into the next ring slot (the general kernels continue from there), its bookkeeping,
-    // ledger + counts of the row before it; flush 2: ledger + counts of row `last`
-    if (launch(last + 1, false, true, last - 1 >= s_begin, (int)((last + 1) & (PF_RING - 1)))) return -1;
-    W2 = W1;
-    if (launch(last + 2, false, false, true, -1)) return -1;
-    return 0;
-}
-
-// Rows [s_begin, s_end) of several chunks (handles on one device, same shape) in lockstep, one k_sweep launch per step on
-// the leader's stream.  Every chunk is bit-identical to its own pf_run (tests/test_gpu_sweep.py): a chunk never reads
-// another chunk's memory, and the launch geometry a chunk sees is the one k_pipe gives it.
-template <int NM, bool BIASED>
-static void launch_sweep(pf_handle* h, const dim3& grid, long long t) {
-    const dim3 blk(PF_BS);
-    const size_t lds = h->smem_pipe;
-    if constexpr (NM == 4 && !BIASED) {
-        const bool traced = h->d_trace && t >= h->trace_t0 && t < h->trace_t0 + h->trace_n;
-        if (h->h_sweep[0].workers > 0) {
-            if (h->n == NM) { if (traced) hipLaunchKernelGGL((k_sweep4q<true, true>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks); else hipLaunchKernelGGL((k_sweep4q<true, false>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks); }
-            else { if (traced) hipLaunchKernelGGL((k_sweep4q<false, true>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks); else hipLaunchKernelGGL((k_sweep4q<false, false>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks); }
-            return;
-        }
-        if (h->d_trace && !h->A.rec_trees && t >= h->trace_t0 && t < h->trace_t0 + h->trace_n) {
-            if (h->n == NM) hipLaunchKernelGGL((k_sweep4t<true>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-            else hipLaunchKernelGGL((k_sweep4t<false>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-            return;
-        }
-        if (h->A.rec_trees) hipLaunchKernelGGL((k_sweep4<false, true>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-        else if (h->n == NM) hipLaunchKernelGGL((k_sweep4<true, false>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-        else hipLaunchKernelGGL((k_sweep4<false, false>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-    } else {
-        if (h->A.rec_trees) hipLaunchKernelGGL((k_sweep<NM, BIASED, false, true>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-        else if (h->n == NM) hipLaunchKernelGGL((k_sweep<NM, BIASED, true, false>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-        else hipLaunchKernelGGL((k_sweep<NM, BIASED, false, false>), grid, blk, lds, h->stream, h->d_sweep, t, h->nblocks);
-    }
-}
-
-static bool sweep_compatible(const pf_handle* a, const pf_handle* b) {
-    const bool ba = a->A.n_bias > 0 || a->A.g_K > 0, bb = b->A.n_bias > 0 || b->A.g_K > 0;
-    return a->device == b->device && a->Np == b->Np && a->n == b->n && a->E == b->E && a->P == b->P && ba == bb &&
-           a->A.rec_trees == b->A.rec_trees && a->ncw == b->ncw && a->workers == b->workers && a->ledger_wgs == b->ledger_wgs && a->split_many == b->split_many && a->cw_off == b->cw_off && a->smem_pipe == b->smem_pipe && a->no_count == b->no_count &&
-           (a->A.dt_tab != nullptr) == (b->A.dt_tab != nullptr) &&
-           // structured models: what the two launches of a step take from the leader (the extend launch's LDS and, through it, the capacities)
-           a->pipe_mp == b->pipe_mp &&
-           // the LDS tree (9 to 16 haplotypes): the flag and the extend launch's LDS (n = 12 does not run with n = 16, nor either with n <= 8)
-           a->pipe_lds == b->pipe_lds && (!a->pipe_lds || (a->smem_sweep_x == b->smem_sweep_x && a->A.dcap == b->A.dcap && a->A.n_bias == b->A.n_bias)) &&
-           (!a->pipe_mp || (a->smem_sweep_x == b->smem_sweep_x && a->A.mcap == b->A.mcap && a->A.pcap == b->A.pcap && a->A.dcap == b->A.dcap && a->A.n_bias == b->A.n_bias));
-}
-
-// the per-chunk table of a k_sweep call in the leader's device buffer; returns the number of steps (0: nothing to do)
-// (split: SweepChunk::split of every chunk)
-static long long sweep_table(pf_handle* const* hs, int nh, long long s_begin, long long s_end, int nL_full, int split, bool* failed) {
-    pf_handle* h = hs[0];
-    const int E = h->E;
-    *failed = true;
-    if (h->d_sweep_cap < nh) {
-        if (h->d_sweep) { if (hipStreamSynchronize(h->stream) != hipSuccess || hipFree(h->d_sweep) != hipSuccess) return 0; }
-        if (hipMalloc((void**)&h->d_sweep, sizeof(SweepChunk) * (size_t)nh) != hipSuccess) { g_err = "hipMalloc of the chunk table failed"; return 0; }
-        h->d_sweep_cap = nh;
-    }
-    // the table of the previous call may still be read by its launches: a fresh host copy per call, uploaded in stream order
-    if (hipStreamSynchronize(h->stream) != hipSuccess) { g_err = "hipStreamSynchronize failed"; return 0; }
-    h->h_sweep.assign((size_t)nh, SweepChunk());
-    long long steps = 0;
-    for (int k = 0; k < nh; ++k) {
-        pf_handle* g = hs[k];
-        SweepChunk& ch = h->h_sweep[k];
-        memset(&ch, 0, sizeof(ch));
-        ch.A = g->A;
-        ch.s_begin = s_begin;
-        long long e = std::min<long long>(s_end, g->n_segs), last = s_begin - 1;
-        for (long long s = s_begin; s < e; ++s) { last = s; if (g->h_seg_start[s] + g->h_seg_len[s] >= g->h_L) break; }   // smcsmc.cpp:353-356
-        ch.s_last = last;
-        for (int q = 0; q < E; ++q) ch.counted_to[q] = g->h_counted_to[q];
-        ch.no_count = g->no_count ? 1 : 0;
-        ch.nL_full = nL_full;
-        ch.ncw = g->ncw;
-        ch.nblk = g->nblocks;
-        ch.nT = (g->A.dt_tab && g->P == 1) ? g->nblocks : 0;
-        ch.split = split;
-        ch.workers = g->workers;
-        ch.trace = h->d_trace; ch.trace_t0 = h->trace_t0; ch.trace_n = h->d_trace ? h->trace_n : 0; ch.trace_stride = h->trace_stride;
-        if (last >= s_begin) steps = std::max(steps, last - s_begin + 3);
-    }
-    *failed = false;
-    if (steps == 0) return 0;
-    if (hipMemcpyAsync(h->d_sweep, h->h_sweep.data(), sizeof(SweepChunk) * (size_t)nh, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-        g_err = "upload of the chunk table failed"; *failed = true; return 0;
-    }
-    hipLaunchKernelGGL(k_sweep_seed, dim3(nh), dim3(PF_BS), 0, h->stream, h->d_sweep);
-    return steps;
-}
-
-// What the sweep runners share.  A sweep runs on the leader's streams (hs[0]); the other handles' streams, and anything they still have
-// in flight, come first ...
-static void sweep_join(pf_handle* const* hs, int nh) {
-    pf_handle* h = hs[0];
-    for (int k = 0; k < nh; ++k) {
-        pf_handle* g = hs[k];
-        if (g->ev_cnt) { hipStreamWaitEvent(h->stream, g->ev_cnt, 0); g->ev_cnt = nullptr; }
-        if (k > 0) {
-            hipEvent_t ev = next_sync_event(g);
-            hipEventRecord(ev, g->stream);
-            hipStreamWaitEvent(h->stream, ev, 0);
-        }
-    }
-}
-
-// ... and each chunk's own stream continues after the sweep
-static void sweep_leave(pf_handle* const* hs, int nh, long long s_begin) {
-    pf_handle* h = hs[0];
-    for (int k = 0; k < nh; ++k) {
-        pf_handle* g = hs[k];
-        const long long last = h->h_sweep[k].s_last;
-        if (last >= s_begin) g->seg_done = last + 1;
-        if (k > 0) {
-            hipEvent_t ev = next_sync_event(h);
-            hipEventRecord(ev, h->stream);
-            hipStreamWaitEvent(g->stream, ev, 0);
-        }
-    }
-}
-
-// completion events of the last sixteen extend launches (ev_x) and of the last sixteen launches of the other roles (ev_blc)
-static int sweep_event_ring(pf_handle* h) {
-    if (!h->ev_x.empty()) return 0;
-    // all thirty-two or none: a vector left half filled would pass for complete on the next call, and launches with null
-    // completion events lose the ordering between the two streams without a word
-    std::vector<hipEvent_t> ev(32, nullptr);
-    bool ok = true;
-    for (auto& e : ev) if (ok && hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { e = nullptr; ok = false; }
-    if (!ok) {
-        for (auto e : ev) if (e) hipEventDestroy(e);
-        g_err = "hipEventCreate failed";
-        return -1;
-    }
-    h->ev_x.assign(ev.begin(), ev.begin() + 16); h->ev_blc.assign(ev.begin() + 16, ev.end());
-    return 0;
-}
-
-// Ledger and count workgroups per chunk in the step of row s.  They belong to row s - 2, whose windows (W2) the host knows as well as the
-// device does: the grid ends with the last epoch column any chunk needs (epochs before a chunk's first moving one are not launched at all)
-static int sweep_lc_wgs(pf_handle* const* hs, int nh, long long s_begin, long long s, const Windows* W2, int nL_full) {
-    pf_handle* h = hs[0];
-    int columns = 0;
-    bool any_lc = false;
-    for (int k = 0; k < nh; ++k)
-        if (s >= s_begin + 2 && s - 2 <= h->h_sweep[k].s_last && !hs[k]->no_count) { any_lc = true; columns = std::max(columns, h->E - W2[k].first); }
-    const int workers = h->h_sweep[0].workers;
-    return workers > 0 ? (any_lc ? workers : 0) : nL_full + h->cw_off[columns];
-}
-
-// after the step of row s: W1 / W2 become the windows of rows s and s - 1 of every chunk
-static void sweep_advance_windows(pf_handle* const* hs, int nh, long long s, Windows* W1, Windows* W2) {
-    pf_handle* h = hs[0];
-    for (int k = 0; k < nh; ++k) {
-        pf_handle* g = hs[k];
-        W2[k] = W1[k];
-        if (s <= h->h_sweep[k].s_last) {
-            W1[k] = host_windows(g, seg_pos(g, s), false);
-            g->step_windows = W1[k];
-            if (W1[k].first < g->E && !g->no_count) g->fin_pending = true;
-        } else {
-            W1[k] = no_windows(g);
-        }
-    }
-}
-
-static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
-    pf_handle* h = hs[0];
-    if (s_begin >= s_end) return 0;
-    const int nb = h->nblocks, E = h->E;
-    const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
-    const int nL_full = nb + h->ledger_wgs;
-    sweep_join(hs, nh);
-    if (h->trace_n > 0 && !h->d_trace) {
-        // pf_set_wg_trace: room for the largest grid a step of these chunks can have
-        const int nT = (h->A.dt_tab && h->P == 1) ? nb : 0;
-        h->trace_stride = nh * (nb + 1 + nT + nL_full + h->cw_off[E]);
-        h->trace_words = (size_t)h->trace_n * (size_t)h->trace_stride * 4;
-        if (hipMalloc((void**)&h->d_trace, h->trace_words * 8) != hipSuccess) { h->d_trace = nullptr; g_err = "hipMalloc of the workgroup trace failed"; return -1; }
-        hipMemsetAsync(h->d_trace, 0, h->trace_words * 8, h->stream);
-    }
-    bool failed = false;
-    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, 0, &failed);
-    if (failed) return -1;
-    if (steps == 0) return 0;
-    std::vector<Windows> W1((size_t)nh), W2((size_t)nh);
-    for (int k = 0; k < nh; ++k) { W1[k] = no_windows(hs[k]); W2[k] = W1[k]; }
-    for (long long t = 0; t < steps; ++t) {
-        const long long s = s_begin + t;
-        const unsigned per_chunk = (unsigned)(nb + 1 + h->h_sweep[0].nT + sweep_lc_wgs(hs, nh, s_begin, s, W2.data(), nL_full));
-        const dim3 grid(per_chunk, (unsigned)nh);          // (pf_bx() / pf_chunk(), pf_device.h)
-        const bool tm_on = timing_on(h, s);
-        {
-            Timed tm(h, 0, tm_on);
-            if (h->n <= 4 && biased) launch_sweep<4, true>(h, grid, t);
-            else if (h->n <= 4) launch_sweep<4, false>(h, grid, t);
-            else if (biased) launch_sweep<8, true>(h, grid, t);
-            else launch_sweep<8, false>(h, grid, t);
-        }
-        if (check_launch("k_sweep")) return -1;
-        if ((t & 1023) == 1023) trim_spans(h);
-        sweep_advance_windows(hs, nh, s, W1.data(), W2.data());
-    }
-    h->k_launches[0] -= 2;                                      // flush steps are not rows
-    sweep_leave(hs, nh, s_begin);
-    return 0;
-}
-
-// One or several chunks in lockstep as TWO launches per step (the default for one population, at most four haplotypes, no focused sampling;
-// PF_DEBUG_ONE_LAUNCH = run_sweep): the extend, bookkeeping and draw roles of all chunks
-// (k_sweep4, one launch after the other on the leader's stream: the chain of dependent loads that is the critical path of a step) and
-// their ledger and count roles (k_sweep_blc, on the counting stream, behind the extend launch of the step before by its completion
-// signal and paced by the sixteen-slot ring as in run_sweep_x).  The second launch needs no dynamic LDS -- that is the bookkeeping
-// role's -- and fewer registers than the extend role: four of its workgroups share a compute unit where the single launch has room for
-// three, and its tail no longer holds up the next row's extend role.  Same bits as run_sweep.
-static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
-    pf_handle* h = hs[0];
-    if (s_begin >= s_end) return 0;
-    const int nb = h->nblocks;
-    const int nL_full = nb + h->ledger_wgs;
-    sweep_join(hs, nh);
-    if (sweep_event_ring(h)) return -1;
-    bool failed = false;
-    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, 2, &failed);
-    if (failed) return -1;
-    if (steps == 0) return 0;
-    hipEvent_t seeded = next_sync_event(h);
-    hipEventRecord(seeded, h->stream);
-    const int nT = h->h_sweep[0].nT;
-    const dim3 gx((unsigned)(nb + 1 + nT), (unsigned)nh), blk(PF_BS);
-    std::vector<Windows> W1((size_t)nh), W2((size_t)nh);
-    for (int k = 0; k < nh; ++k) { W1[k] = no_windows(hs[k]); W2[k] = W1[k]; }
-    // (at most four: the second launch of step t - 7 must be enqueued when step t waits for it.  Several chunks: eight 20 Mb chunks 1.205e5 ->
-    // 1.248e5 segments/s with two, 1.272e5 with four; one chunk is the same with any)
-    const long long batch = std::max(1, std::min(4, h->split_batch > 0 ? h->split_batch : (nh > 1 ? 4 : 1)));
-    std::vector<unsigned> pending_grid((size_t)batch, 1u);
-    hipStreamWaitEvent(h->cstream, seeded, 0);
-    for (long long t = 0; t < steps; ++t) {
-        const long long s = s_begin + t;
-        static_assert(PF_RING == 16, "the wait schedule below is written for sixteen ring slots");
-        if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);      // ring slot reuse, as in run_sweep_x
-        // The second launches follow in batches of `batch` steps: only the last extend launch of a batch carries a completion signal, and the
-        // batch's second launches wait for that one (each needs the extend launch of the step before it: complete by then).
-        const bool batch_end = ((t + 1) % batch) == 0 || t == steps - 1;
-        {
-            Timed tm(h, 0, timing_on(h, s));
-            hipEvent_t xdone = h->ev_x[(size_t)(t & 15)];
-            if (batch_end) {
-                if (h->n == 4) hipExtLaunchKernelGGL((k_sweep4<true, false>), gx, blk, h->smem_pipe, h->stream, nullptr, xdone, 0, h->d_sweep, t, nb);
-                else hipExtLaunchKernelGGL((k_sweep4<false, false>), gx, blk, h->smem_pipe, h->stream, nullptr, xdone, 0, h->d_sweep, t, nb);
-            } else {
-                if (h->n == 4) hipLaunchKernelGGL((k_sweep4<true, false>), gx, blk, h->smem_pipe, h->stream, h->d_sweep, t, nb);
-                else hipLaunchKernelGGL((k_sweep4<false, false>), gx, blk, h->smem_pipe, h->stream, h->d_sweep, t, nb);
-            }
-        }
-        if (check_launch("k_sweep4 (extend, bookkeeping and draw roles)")) return -1;
-        const int W = h->h_sweep[0].workers;
-        pending_grid[(size_t)(t % batch)] = (unsigned)(1 + sweep_lc_wgs(hs, nh, s_begin, s, W2.data(), nL_full));
-        if (batch_end) {
-            hipStreamWaitEvent(h->cstream, h->ev_x[(size_t)(t & 15)], 0);
-            for (long long u = t - (t % batch); u <= t; ++u) {
-                const dim3 grid(pending_grid[(size_t)(u % batch)], (unsigned)nh);
-                hipEvent_t bdone = h->ev_blc[(size_t)(u & 15)];
-                if (W > 0) {
-                    if (h->n == 4) hipExtLaunchKernelGGL((k_sweep_blc4q<true>), grid, blk, 0, h->cstream, nullptr, bdone, 0, h->d_sweep, u);
-                    else hipExtLaunchKernelGGL((k_sweep_blc4q<false>), grid, blk, 0, h->cstream, nullptr, bdone, 0, h->d_sweep, u);
-                } else {
-                    if (h->n == 4) hipExtLaunchKernelGGL((k_sweep_blc4<true>), grid, blk, 0, h->cstream, nullptr, bdone, 0, h->d_sweep, u);
-                    else hipExtLaunchKernelGGL((k_sweep_blc4<false>), grid, blk, 0, h->cstream, nullptr, bdone, 0, h->d_sweep, u);
-                }
-            }
-            if (check_launch("k_sweep_blc (ledger and count roles)")) return -1;
-        }
-        if ((t & 1023) == 1023) trim_spans(h);
-        sweep_advance_windows(hs, nh, s, W1.data(), W2.data());
-    }
-    h->k_launches[0] -= 2;                                      // flush steps are not rows
-    // what follows on any chunk's stream waits for the last launch of the other roles
-    hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((steps - 1) & 15)], 0);
-    sweep_leave(hs, nh, s_begin);
-    return 0;
-}
-
-// Structured models (register-tree kernel) on the row pipeline, one chunk or several in lockstep.  Per step two launches for all
-// of them: the extend role (k_sweep_xmp, with the decision on the previous row in its prologue; grid = particle blocks x chunks) on
-// the leader's filter stream, the bookkeeping / ledger / count roles (k_sweep_blc, grid = workgroups per chunk x chunks) on the
-// leader's counting stream -- separate launches because the extend workgroups' LDS (their trees' migration events) would be
-// allocated to every count workgroup too.  Step t's second launch needs the extend launch of step t - 1 (partials, offspring
-// table, records), the extend launch of step t must not overwrite ring slot t & (PF_RING - 1) before the counts of step t - 2 are done:
-// one wait each way per step, on the kernels' own completion signals; the extend role does not read anything the other
-// launch writes (it keeps its own note of n_resample / generation, Ctrl::xr).  k_decide, its boundary and the wait of the
-// next row on the previous row's ledger upkeep are gone from the critical stream.  A chunk never reads another chunk's memory and
-// takes nothing from the launch geometry but its own blockIdx.x: every chunk is bit-identical to its own pf_run
-// (tests/test_gpu_sweep_structured.py).
-// The same runner serves one population with the tree in LDS (pipe_lds: 9 to 16 haplotypes, several chunks through pf_run_many): the
-// extend role is k_sweep_xl (256 particles per workgroup, 100 KB of tree columns at 16 haplotypes -- the same reason for two
-// launches), the other roles k_sweep_blc<16, 1, *>, and the table says so with SweepChunk::split = 1 (sweep_plan: the extend role
-// runs ahead).  Everything else -- the table, the seed, the two waits per step, the windows -- is shared line for line, which is why
-// this is one function with two launch sites and not a sibling (tests/test_gpu_sweep_lds.py).
-static int run_sweep_x(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
-    pf_handle* h = hs[0];
-    if (s_begin >= s_end) return 0;
-    const int nb = h->nblocks;
-    const bool biased = h->A.n_bias > 0 || h->A.g_K > 0;
-    const int nL_full = nb + h->ledger_wgs;
-    sweep_join(hs, nh);
-    if (sweep_event_ring(h)) return -1;
-    bool failed = false;
-    const long long steps = sweep_table(hs, nh, s_begin, s_end, nL_full, h->pipe_lds ? 1 : 0, &failed);
-    if (failed) return -1;
-    if (steps == 0) return 0;
-    // the counting stream starts behind the table and the seed
-    hipEvent_t seeded = next_sync_event(h);
-    hipEventRecord(seeded, h->stream);
-    std::vector<Windows> W1((size_t)nh), W2((size_t)nh);
-    for (int k = 0; k < nh; ++k) { W1[k] = no_windows(hs[k]); W2[k] = W1[k]; }
-    for (long long t = 0; t < steps; ++t) {
-        const long long s = s_begin + t;
-        // ring slot reuse: the extend launch of step t overwrites the slot of row t - PF_RING, which the counts read in step
-        // t - PF_RING + 2.  One wait every eight steps, for the second launch of seven steps ago, covers the eight steps that
-        // follow (t + 7 - 14 <= t - 7); between two waits the extend launches are dispatched back to back.
-        static_assert(PF_RING == 16, "the wait schedule below is written for sixteen ring slots");
-        if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);
-        {
-            Timed tm(h, 0, timing_on(h, s));
-            if (h->pipe_lds) {
-                const dim3 gx((unsigned)nb, (unsigned)nh), bx(PF_BS);
-                hipEvent_t xdone = h->ev_x[(size_t)(t & 15)];
-                if (biased) hipExtLaunchKernelGGL((k_sweep_xl<true>), gx, bx, h->smem_sweep_x, h->stream, nullptr, xdone, 0, h->d_sweep, t);
-                else hipExtLaunchKernelGGL((k_sweep_xl<false>), gx, bx, h->smem_sweep_x, h->stream, nullptr, xdone, 0, h->d_sweep, t);
-            } else {
-                pf_mp_launch_sweep_x(h->A, h->d_sweep, nh, t, h->smem_sweep_x, h->stream, h->ev_x[(size_t)(t & 15)]);
-            }
-        }
-        if (check_launch(h->pipe_lds ? "k_sweep_xl" : "k_sweep_xmp")) return -1;
-        hipStreamWaitEvent(h->cstream, t >= 1 ? h->ev_x[(size_t)((t - 1) & 15)] : seeded, 0);
-        const dim3 grid((unsigned)(1 + sweep_lc_wgs(hs, nh, s_begin, s, W2.data(), nL_full)), (unsigned)nh), blk(PF_BS);
-        hipEvent_t done = h->ev_blc[(size_t)(t & 15)];
-#define PF_LAUNCH_BLC(NMV, PV, BV) hipExtLaunchKernelGGL((k_sweep_blc<NMV, PV, BV>), grid, blk, h->smem_pipe, h->cstream, nullptr, done, 0, h->d_sweep, t)
-        if (h->pipe_lds) { if (biased) PF_LAUNCH_BLC(PF_NMAX, 1, true); else PF_LAUNCH_BLC(PF_NMAX, 1, false); }
-        else if (h->P == 2) { if (biased) PF_LAUNCH_BLC(8, 2, true); else PF_LAUNCH_BLC(8, 2, false); }
-        else { if (biased) PF_LAUNCH_BLC(8, PF_PMAX, true); else PF_LAUNCH_BLC(8, PF_PMAX, false); }
-#undef PF_LAUNCH_BLC
-        if (check_launch("k_sweep_blc")) return -1;
-        if ((t & 1023) == 1023) trim_spans(h);
-        sweep_advance_windows(hs, nh, s, W1.data(), W2.data());
-    }
-    h->k_launches[0] -= 2;                                      // flush steps are not rows
-    // what follows on any chunk's stream waits for the last launch of the other roles
-    hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((steps - 1) & 15)], 0);
-    sweep_leave(hs, nh, s_begin);
-    return 0;
-}
-
-// why pf_run_many would refuse these handles (null: it would not)
-static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles) {
-    if (n_handles < 1 || !handles || !handles[0]) return "pf_run_many: no handles";
-    pf_handle* h = handles[0];
-    for (int k = 0; k < n_handles; ++k) {
-        pf_handle* g = handles[k];
-        if (!g) return "pf_run_many: null handle";
-        const bool one_pop = extend_can_fuse(g) && g->pipe && !g->two_launch_rows;
-        const bool structured = g->pipe_mp && g->A.apf == 0 && !g->force_lds && !g->no_fuse;
-        // one population, 9 to 16 haplotypes, the tree in LDS.  Out of scope here: structured models above 8 haplotypes, -arg and the
-        // look-ahead in lockstep, the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the general kernels
-        const bool lds_tree = g->pipe_lds && g->A.apf == 0;
-        if (!one_pop && !structured && !lds_tree)
-            return "pf_run_many: the chunks must run on the row pipeline (one population of at most 16 haplotypes, or a structured model of two to "
-                   "four populations with the tree in registers, at most 8 haplotypes; no look-ahead, no -arg above 8 haplotypes, no debug "
-                   "switch that selects another path)";
-        if (!sweep_compatible(h, g)) return "pf_run_many: the chunks must share device, particle count, haplotypes (and with them the form of the tree: registers up to 8, "
-                                              "LDS columns of one width from 9 to 16), epochs and options";
-        for (int j = 0; j < k; ++j) if (handles[j] == g) return "pf_run_many: a handle appears twice";
-    }
-    return nullptr;
-}
-
-int pf_can_run_many(pf_handle* const* handles, int32_t n_handles) {
-    return run_many_refusal(handles, n_handles) == nullptr ? 1 : 0;
-}
-
-int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, int64_t s_end) {
-    if (const char* why = run_many_refusal(handles, n_handles)) { g_err = why; return -1; }
-    pf_handle* h = handles[0];
-    HIPCHK(hipSetDevice(h->device));
-    if (s_begin < 0) { g_err = "segment range out of bounds"; return -1; }        // a chunk with fewer rows sits the call out
-    if (h->pipe_mp || h->pipe_lds) return run_sweep_x(handles, n_handles, s_begin, s_end);
-    if (h->split_many && !h->A.rec_trees) return run_sweep_split(handles, n_handles, s_begin, s_end);
-    return run_sweep(handles, n_handles, s_begin, s_end);
-}
-
-int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end) {
-    HIPCHK(hipSetDevice(h->device));
-    if (s_begin < 0 || s_end > h->n_segs) { g_err = "segment range out of bounds"; return -1; }
-    if (extend_can_fuse(h)) {
-        if (!h->pipe || h->two_launch_rows) return run_single_stream(h, s_begin, s_end);
-        if (h->use_k_pipe) return run_pipeline(h, s_begin, s_end);
-        pf_handle* one[1] = {h};
-        if (h->split_many && !h->A.rec_trees) return run_sweep_split(one, 1, s_begin, s_end);
-        return run_sweep(one, 1, s_begin, s_end);
-    }
-    if (h->pipe_mp && h->A.apf == 0 && !h->force_lds && !h->no_fuse) { pf_handle* one[1] = {h}; return run_sweep_x(one, 1, s_begin, s_end); }
-    // structured models on the register-tree kernel: the next row's extend completes this row while it loads (two
-    // launches per row on the main stream instead of three); the last row of the call is completed by k_resample
-    const bool mp_fuse = h->P > 1 && pf_mp_can_fuse(h->A, h->force_lds) && h->A.apf == 0 && !h->no_fuse;
-    long long owed = -1;              // row decided but not completed yet
-    for (long long s = s_begin; s < s_end; ++s) {
-        h->step_windows = host_windows(h, seg_pos(h, s), false);
-        h->A.sp = (int)(s & 1);
-        if (launch_extend(h, s, owed >= 0 ? 1 : 0)) return -1;
-        if (launch_decide(h, s, 0, h->step_windows)) return -1;
-        if (mp_fuse) owed = s;
-        else if (launch_resample(h, s)) return -1;
-        if (launch_count(h, s, h->step_windows)) return -1;
-        if (launch_ledger(h, s)) return -1;
-        h->seg_done = s + 1;
-        if (h->h_seg_start[s] + h->h_seg_len[s] >= h->h_L) break;   // smcsmc.cpp:353-356
-        if ((s & 1023) == 1023) trim_spans(h);
-    }
-    if (owed >= 0 && launch_resample(h, owed)) return -1;
-    return 0;
-}
+#include "pf_run.h"
 
 int pf_finish(pf_handle* h) {
     HIPCHK(hipSetDevice(h->device));

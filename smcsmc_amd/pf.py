@@ -95,7 +95,7 @@ class PackedLookahead:
 EXPORTS = [
     "pf_last_error", "pf_device_count", "pf_create", "pf_destroy", "pf_init_prior", "pf_load_segments", "pf_load_lookahead",
     "pf_terminal_branch_quantiles",
-    "pf_update_segment", "pf_count", "pf_resample", "pf_run", "pf_run_many", "pf_can_run_many", "pf_finish", "pf_sync",
+    "pf_update_segment", "pf_count", "pf_resample", "pf_run", "pf_run_many", "pf_can_run_many", "pf_get_run_path", "pf_finish", "pf_sync",
     "pf_num_segments_done", "pf_logl", "pf_get_counts", "pf_get_trace", "pf_get_resample_events",
     "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_probe_tree_edit", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
     "pf_simulate_sites_wide", "pf_median_survival", "pf_median_survival_opts", "pf_test_math", "pf_test_div", "pf_test_uniform", "pf_test_reduce", "pf_test_systematic",
@@ -128,6 +128,7 @@ def load_library(path=None):
     L.pf_run.argtypes = [vp, C.c_int64, C.c_int64]
     L.pf_run_many.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64]
     L.pf_can_run_many.argtypes = [vp, C.c_int32]
+    L.pf_get_run_path.argtypes = [vp, C.c_int]
     L.pf_finish.argtypes = [vp]
     L.pf_sync.argtypes = [vp]
     L.pf_sample_tree_events.restype = C.c_int64
@@ -286,6 +287,10 @@ def probe_tree_edit(S, Cc, h, lin, rp, sb, tc, u_attach, device=0):
     return oi, od
 
 
+# pf_get_run_path (PF_PATH_* of smcsmc_pf.h, in order)
+RUN_PATHS = ("General", "TwoLaunch", "KPipe", "Sweep", "SweepSplit", "SweepXmp", "SweepXl")
+
+
 class ParticleFilter:
     def __init__(self, model, np_particles, ess_fraction=0.5, seed=1, max_trace_events=64, device=0, local_recomb=False,
                  record_trees=False, log_cap=0, gen_cap=0, piece_cap=0, debug=0, mig_cap=0, count_wgs=0, delay_cap=0,
@@ -380,6 +385,12 @@ class ParticleFilter:
             return False
         hs = (C.c_void_p * len(filters))(*[f.h for f in filters])
         return bool(filters[0].L.pf_can_run_many(hs, len(filters)))
+
+    def run_path(self, many=False):
+        """Name of the runner that takes this filter's rows as it stands now (pf_get_run_path; RUN_PATHS): run()'s, or with
+        many=True run_many()'s, where None says that run_many refuses the filter."""
+        k = int(self.L.pf_get_run_path(self.h, int(bool(many))))
+        return None if k < 0 else RUN_PATHS[k]
 
     def update_segment(self, s):
         self._chk(self.L.pf_update_segment(self.h, int(s)))
