@@ -214,8 +214,12 @@ int pf_resample(pf_handle* h, int64_t s);
 int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
 /* the same loop for several chunks at once: rows [s_begin, s_end) of n_handles independent filters (one per chromosome
  * chunk; same device, particle count, haplotypes, epochs, populations and options) step in lockstep through the same kernel launches, whose
- * grids cover all of them (two per row for at most four haplotypes without focused sampling -- the extend roles; the ledger and
- * count roles on the counting stream -- one otherwise).  Structured models with the tree in registers (two to four populations, at
+ * grids cover all of them (two per row for at most four haplotypes without focused sampling or -arg -- the extend roles; the ledger and
+ * count roles on the counting stream -- one otherwise).  One population with at most 8 haplotypes and tree recording (-arg, pf_params.flags
+ * bit 1) is taken in lockstep: the TREES instances of k_sweep / k_sweep4, one launch per row, for pf_run and pf_run_many alike; every
+ * handle of such a group records trees (a recording handle does not run with a plain one), and the chunks may differ in log_cap and
+ * gen_cap -- each chunk brings its own argument block and rings.  pf_sample_tree_events* after pf_run_many + pf_finish returns what it
+ * returns after pf_run: the sampled particle and its events, bit for bit.  Structured models with the tree in registers (two to four populations, at
  * most 8 haplotypes, no look-ahead, no -arg) are taken too: one extend launch (k_sweep_xmp, grid = particle blocks x chunks) and one
  * launch of the bookkeeping, ledger and count roles (k_sweep_blc) per row for all chunks; such chunks must also share mig_cap,
  * piece_cap, delay_cap and the number of bias bands, and cannot be mixed with one-population chunks.
@@ -224,7 +228,7 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * launch of the other roles (k_sweep_blc<16, 1, *>) per row for all chunks.  Such chunks must have the same number of haplotypes (the
  * width of the tree columns is the launch's LDS size: 12 does not run with 16, nor either with 8 or fewer), delay_cap and bias bands.
  * pf_run on ONE such handle keeps the general kernels (k_extend -> k_decide -> k_resample); nobody has measured one chunk on the pipeline.
- * Not taken: structured models above 8 haplotypes, -arg and the look-ahead above 8 haplotypes, more than 16 haplotypes (the wide kernels).
+ * Not taken: structured models above 8 haplotypes, -arg with structure or above 8 haplotypes, the look-ahead, more than 16 haplotypes (the wide kernels).
  * The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
  * every chunk's results are bit-identical to its own pf_run.  A chunk that runs out of rows simply stops and sits later calls out.
  * Afterwards every handle's own stream continues behind the call: pf_run, pf_finish, pf_get_counts and the step API mix freely with it. */
@@ -233,7 +237,9 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
  * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure
  * (at any number of haplotypes: such handles run on the general path, row kernel -> k_decide -> k_resample),
  * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path -- or they
- * differ in shape: haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks) */
+ * differ in shape: haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks,
+ * or a tree-recording handle mixed with a plain one).  One population with at most 8 haplotypes and -arg IS taken, whatever the chunks'
+ * log_cap / gen_cap. */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 /* Which runner takes the rows of this handle as it stands now (a look-ahead loaded later changes the answer): pf_run's with many == 0,
  * pf_run_many's otherwise, where -1 says that pf_run_many refuses the handle.  DESIGN.md, "Which path runs when". */

@@ -147,6 +147,24 @@ static void release_filter(ChunkFilter& F) {
     if (F.h) { pf_destroy(F.h); F.h = nullptr; }
 }
 
+// -arg: the rings of a filter that keeps the whole history of `rows` rows, and the device memory they take
+struct ArgRings { long long log_cap = 0, gen_cap = 0; double bytes = 0; };
+
+static ArgRings arg_rings(const PfParam& P, size_t rows) {
+    const HostModel& M = P.model;
+    // nothing may be overwritten while the history is needed: a slot appends about 0.6 records per row for its
+    // recombinations and up to one per resampling, and there are at most as many generations as rows
+    auto pow2_at_least = [](double v) { long long c = 16384; while ((double)c < v) c <<= 1; return c; };
+    ArgRings r;
+    // (recombinations per row grow with the tree length: the figure above is for four samples)
+    r.log_cap = pow2_at_least(1.4 * (double)rows * std::max(1.0, (M.nsam - 1) / 3.0));
+    r.gen_cap = pow2_at_least((double)rows + 2.0);
+    // (structured models: plus the piece ring, four pieces of three words per record by default -- pf_params.piece_cap)
+    const double piece_bytes = M.npop > 1 ? (double)P.particles * 4.0 * (double)r.log_cap * 3.0 * 8.0 : 0.0;
+    r.bytes = (double)P.particles * (double)r.log_cap * (5.0 + M.nsam - 1) * 8.0 + piece_bytes + (double)r.gen_cap * (double)P.particles * 20.0;
+    return r;
+}
+
 static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int device, const ChunkJob* job) {
     F.P = &P;
     HostModel& M = P.model;
@@ -270,19 +288,11 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
     if (P.delay_evict) pp.flags |= 4;
     if (P.record_trees) {
         pp.flags |= 2;     // -arg (pfparam.cpp:353-357)
-        // nothing may be overwritten while the history is needed: a slot appends about 0.6 records per row for its
-        // recombinations and up to one per resampling, and there are at most as many generations as rows
-        auto pow2_at_least = [](double v) { long long c = 16384; while ((double)c < v) c <<= 1; return c; };
-        // (recombinations per row grow with the tree length: the figure above is for four samples)
-        const long long log_cap = pow2_at_least(1.4 * (double)start.size() * std::max(1.0, (M.nsam - 1) / 3.0));
-        const long long gen_cap = pow2_at_least((double)start.size() + 2.0);
-        // (structured models: plus the piece ring, four pieces of three words per record by default -- pf_params.piece_cap)
-        const double piece_bytes = NP > 1 ? (double)P.particles * 4.0 * (double)log_cap * 3.0 * 8.0 : 0.0;
-        const double gib = ((double)P.particles * (double)log_cap * (5.0 + M.nsam - 1) * 8.0 + piece_bytes + (double)gen_cap * (double)P.particles * 20.0) / (1024.0 * 1024.0 * 1024.0);
-        clog << " -arg: event log of " << log_cap << " records per particle, " << gen_cap << " generations (" << fixed << setprecision(1)
-             << gib << " GiB)" << setprecision(6) << scientific << endl;
-        pp.log_cap = log_cap;
-        pp.gen_cap = gen_cap;
+        const ArgRings rings = arg_rings(P, start.size());
+        clog << " -arg: event log of " << rings.log_cap << " records per particle, " << rings.gen_cap << " generations (" << fixed << setprecision(1)
+             << rings.bytes / (1024.0 * 1024.0 * 1024.0) << " GiB)" << setprecision(6) << scientific << endl;
+        pp.log_cap = rings.log_cap;
+        pp.gen_cap = rings.gen_cap;
     }
     pf_handle* h = pf_create(&pm, &pp, device);
     if (!h) throw std::runtime_error(pf_last_error());
@@ -332,6 +342,36 @@ static void run_filters(std::vector<ChunkFilter*>& group, bool progress) {
 
 static void report_counts(PfParam& P, const HostModel& M0, const std::vector<double>& packed, double chunks);
 
+// <prefix>.trees.gz (ParticleContainer::printTrees, pc.cpp:515-555) after the one-particle draw of smcsmc.cpp:395: the draw is the
+// filter's own (its seed), the positions are those of the whole sequence (start_position: a chunk's first base)
+static void write_trees(const PfParam& P, pf_handle* h) {
+    int64_t particle = 0;
+    const int64_t nev = pf_sample_tree_events_pops(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &particle);
+    if (nev < 0) pf_check(-1);
+    std::vector<int32_t> kind((size_t)nev), from((size_t)nev), to((size_t)nev);
+    std::vector<double> xs((size_t)nev), ts((size_t)nev);
+    std::vector<uint32_t> ds((size_t)nev);
+    if (pf_sample_tree_events_pops(h, kind.data(), xs.data(), ts.data(), ds.data(), from.data(), to.data(), nev, &particle) < 0)
+        pf_check(-1);
+    std::string text;
+    text.reserve((size_t)nev * 48);
+    char buf[96];
+    for (int64_t i = 0; i < nev; ++i) {
+        // out << eventcode << x + start_position - 1 << t << from_pop << to_pop, fixed, one decimal
+        int len = snprintf(buf, sizeof buf, "%c\t%.1f\t%.1f\t%d\t%d\t", kind[i] == 0 ? 'R' : (kind[i] == 1 ? 'C' : 'M'),
+                           xs[i] + P.start_position - 1, ts[i], from[i], to[i]);
+        text.append(buf, (size_t)len);
+        // print_descendants (descendants.hpp:51-65)
+        const uint32_t m = ds[i];
+        if (m == 0) text += '0';
+        else
+            for (int b = 0; (m >> b) != 0; ++b) text += ((m >> b) & 1u) ? '1' : '0';
+        text += '\n';
+    }
+    gzFile gz = gzopen(P.trees_path.c_str(), "wb");
+    if (gz) { gzwrite(gz, text.data(), (unsigned)text.size()); gzclose(gz); }
+}
+
 static void close_filter(ChunkFilter& F, const HostModel& M0, const ChunkJob* job) {
     PfParam& P = *F.P;
     HostModel& M = P.model;
@@ -356,11 +396,12 @@ static void close_filter(ChunkFilter& F, const HostModel& M0, const ChunkJob* jo
                      << " applied early to make room" << endl;
         }
         clog << " Inference step completed." << endl;
-        // a chunk of a multi-chunk E-step: the statistics go to the reduction; its local recombination map is written like any
-        // chunk process's (<prefix>.chunkN.recomb.gz: the reference writes one per chunk process, smcsmc.cpp:376-383)
+        // a chunk of a multi-chunk E-step: the statistics go to the reduction; its .resample rows, its local recombination map and
+        // its tree dump are written like any chunk process's (<prefix>.chunkN.*: the reference writes them per chunk process,
+        // smcsmc.cpp:376-383, 395; the paths are the chunk's own, run_chunks)
         const bool chunk_job = job && job->packed_out;
         if (chunk_job) *job->packed_out = packed;
-        if (!chunk_job && P.write_resample) {
+        if (P.write_resample) {
             std::vector<double> ess(done);
             std::vector<int32_t> flag(done);
             pf_check(pf_get_trace(h, nullptr, ess.data(), flag.data(), nullptr, done));
@@ -427,35 +468,8 @@ static void close_filter(ChunkFilter& F, const HostModel& M0, const ChunkJob* jo
                 fclose(fz);
             }
         }
+        if (P.record_trees) write_trees(P, h);          // every E-step overwrites it, as the reference does
         if (chunk_job) return;
-        // <prefix>.trees.gz (ParticleContainer::printTrees, pc.cpp:515-555) after the one-particle draw of smcsmc.cpp:395
-        if (P.record_trees) {          // every E-step overwrites it, as the reference does
-            int64_t particle = 0;
-            const int64_t nev = pf_sample_tree_events_pops(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, &particle);
-            if (nev < 0) pf_check(-1);
-            std::vector<int32_t> kind((size_t)nev), from((size_t)nev), to((size_t)nev);
-            std::vector<double> xs((size_t)nev), ts((size_t)nev);
-            std::vector<uint32_t> ds((size_t)nev);
-            if (pf_sample_tree_events_pops(h, kind.data(), xs.data(), ts.data(), ds.data(), from.data(), to.data(), nev, &particle) < 0)
-                pf_check(-1);
-            std::string text;
-            text.reserve((size_t)nev * 48);
-            char buf[96];
-            for (int64_t i = 0; i < nev; ++i) {
-                // out << eventcode << x + start_position - 1 << t << from_pop << to_pop, fixed, one decimal
-                int len = snprintf(buf, sizeof buf, "%c\t%.1f\t%.1f\t%d\t%d\t", kind[i] == 0 ? 'R' : (kind[i] == 1 ? 'C' : 'M'),
-                                   xs[i] + P.start_position - 1, ts[i], from[i], to[i]);
-                text.append(buf, (size_t)len);
-                // print_descendants (descendants.hpp:51-65)
-                const uint32_t m = ds[i];
-                if (m == 0) text += '0';
-                else
-                    for (int b = 0; (m >> b) != 0; ++b) text += ((m >> b) & 1u) ? '1' : '0';
-                text += '\n';
-            }
-            gzFile gz = gzopen(P.trees_path.c_str(), "wb");
-            if (gz) { gzwrite(gz, text.data(), (unsigned)text.size()); gzclose(gz); }
-        }
         report_counts(P, M0, packed, 1.0);
     }
 }
@@ -557,7 +571,12 @@ static void report_counts(PfParam& P, const HostModel& M0, const std::vector<dou
 // all of them from a fresh prior (chunks are independent, smcsmc.cpp:296) through one kernel launch per row whose grid
 // covers them (pf_run_many) when the single-launch row pipeline applies, one after the other otherwise.  Then ONE
 // all-gather of the packed statistics (mgpu.cpp: RCCL over xGMI when every rank has its own device) and a sum in chunk
-// order on every rank -- bit-identical for any R and G.
+// order on every rank -- bit-identical for any R and G.  Every chunk leaves the files a chunk process of the front-end leaves:
+// <prefix>.chunkN.recomb.gz, with -arg <prefix>.chunkN.trees.gz (the chunk's own one-particle draw, positions of the whole sequence)
+// and with -record_ess <prefix>.chunkN.resample.  They depend on the chunk alone (its data window, seed + 1000 * iteration + N), not on
+// R, G or on whether its group shared the launches; there is no merged tree file (chunks start from fresh priors: their trees do not join).
+// With -arg a group runs in lockstep at one population and at most 8 haplotypes; structured models and 9 to 16 haplotypes record trees on
+// the general kernels, one chunk after the other.
 struct ChunkPlan {                      // what stays the same over the EM iterations of a run
     int K = 0, R = 0, G = 0, slots = 0;
     size_t LEN = 0;
@@ -568,8 +587,6 @@ struct ChunkPlan {                      // what stays the same over the EM itera
 };
 
 static void plan_chunks(ChunkPlan& C, PfParam& P) {
-    if (P.record_trees) throw Unsupported("-arg together with -chunks / -ranks (the tree dump is that of one filter)");
-    if (P.write_resample) throw Unsupported("-record_ess together with -chunks / -ranks (one .resample file per filter)");
     C.K = P.chunks;
     C.G = P.devices > 0 ? P.devices : visible_devices();
     if (C.G < 1) throw std::runtime_error("no HIP device available (there is no CPU fallback)");
@@ -599,11 +616,12 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
     std::vector<std::vector<double>> all(R, std::vector<double>((size_t)R * slots * LEN, 0.0));
     std::vector<std::string> failure(R);
     // the chunks of a rank go through the same launches, row by row, when the row pipeline applies to them (include/smcsmc_pf.h, pf_run_many):
-    // one population, at most 16 haplotypes (above 8 on the LDS tree: k_sweep_xl), no look-ahead (-arg never gets here: plan_chunks).
-    // pf_can_run_many decides.  The library takes
+    // one population, at most 16 haplotypes (above 8 on the LDS tree: k_sweep_xl), no look-ahead; with -arg at most 8 haplotypes (the TREES
+    // instances of k_sweep / k_sweep4 -- above 8 the library refuses tree-recording handles, and a group of -arg rings opened only to be
+    // filtered one by one would hold the device's memory for nothing).  pf_can_run_many decides.  The library takes
     // the chunks of a structured model too (pf_run_many), but this binary keeps filtering those one after the other
     // until lockstep has been measured not slower than that at four chunks (section 7: not measured yet) -- npop == 1 below is the switch
-    const bool lockstep = P.model.npop == 1 && P.model.nsam <= 16 && P.apf_level == 0;
+    const bool lockstep = P.model.npop == 1 && P.model.nsam <= 16 && P.apf_level == 0 && !(P.record_trees && P.model.nsam > 8);
     std::mutex notes_lock;
     auto rank_main = [&](int r) {
         bool entered = false;
@@ -622,9 +640,15 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
                 params[k].segments = C.tables[c].get();
                 // the chunk's own local recombination map, as a chunk process of the front-end would leave it
                 // (<out>/emiterI/chunkC.recomb.gz there; model.py:1057-1092)
-                params[k].recomb_map_path = P.recomb_map_path.substr(0, P.recomb_map_path.size() - std::string(".recomb.gz").size()) +
-                                            ".chunk" + std::to_string(c) + ".recomb.gz";
-                if (P.em_iteration == 0) remove(params[k].recomb_map_path.c_str());
+                params[k].recomb_map_path = P.chunk_file(c, ".recomb.gz");
+                // likewise its tree dump (-arg) and its resampling positions (-record_ess): chunkC.trees.gz, chunkC.resample there
+                params[k].trees_path = P.chunk_file(c, ".trees.gz");
+                params[k].resample_path = P.chunk_file(c, ".resample");
+                if (P.em_iteration == 0) {
+                    remove(params[k].recomb_map_path.c_str());
+                    if (P.record_trees) remove(params[k].trees_path.c_str());
+                    if (P.write_resample) remove(params[k].resample_path.c_str());
+                }
                 jobs[k].survival = &survival; jobs[k].survival_out = &survival; jobs[k].packed_out = &packed[k]; jobs[k].seed_offset = (uint64_t)c;
                 // Six or more chunks side by side on a device: count_wgs set (to the most a column can have, one per 256 particles) makes
                 // the library taper the columns of the young epochs and trim its ledger workgroups (8 chunks of the C3 shape: 1.17e5
@@ -643,6 +667,20 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
                 std::vector<ChunkFilter*> group;
                 size_t k1 = k0;
                 while (k1 < my_chunks.size() && (k1 == k0 || lockstep)) {
+                    // -arg: a filter keeps its whole history, tens of GiB at production sizes -- ask the device before opening another one
+                    // beside those that are open (the rings as open_filter sizes them, and an eighth more for the rest of a filter: particles,
+                    // count accumulators and the local map are small beside Np x log_cap records).  Ranks that share a device may
+                    // still meet at the allocation: the catch below stays.
+                    if (P.record_trees && k1 > k0) {
+                        size_t free_bytes = 0, total_bytes = 0;
+                        const double need = 1.125 * arg_rings(params[k1], params[k1].segments->rows()).bytes;
+                        if (device_memory(C.device_of_rank[r], &free_bytes, &total_bytes) && need > (double)free_bytes) {
+                            clog << " rank " << r << ": " << (k1 - k0) << " chunks with their tree records fill the device ("
+                                 << fixed << setprecision(1) << need / (1024.0 * 1024.0 * 1024.0) << " GiB wanted, " << (double)free_bytes / (1024.0 * 1024.0 * 1024.0)
+                                 << " GiB free); the rest follow" << setprecision(6) << scientific << endl;
+                            break;
+                        }
+                    }
                     try {
                         open_filter(filters[k1], params[k1], M0, C.device_of_rank[r], &jobs[k1]);
                     } catch (const std::exception& e) {
@@ -669,7 +707,14 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
                 } else {
                     for (ChunkFilter* F : group) { std::vector<ChunkFilter*> one{F}; run_filters(one, r == 0); }
                 }
-                for (size_t k = k0; k < k1; ++k) { close_filter(filters[k], M0, &jobs[k]); release_filter(filters[k]); }
+                for (size_t k = k0; k < k1; ++k) {
+                    close_filter(filters[k], M0, &jobs[k]);
+                    release_filter(filters[k]);
+                    if (P.record_trees) {
+                        std::lock_guard<std::mutex> hold(notes_lock);
+                        P.chunk_notes.push_back(" rank " + std::to_string(r) + ": chunk " + std::to_string(my_chunks[k]) + ": trees written to " + params[k].trees_path);
+                    }
+                }
                 k0 = k1;
             }
             for (size_t k = 0; k < my_chunks.size(); ++k) std::copy(packed[k].begin(), packed[k].end(), mine[r].begin() + k * LEN);

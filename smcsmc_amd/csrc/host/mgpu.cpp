@@ -26,6 +26,10 @@ int visible_devices() {
     return n;
 }
 
+bool device_memory(int device, size_t* free_bytes, size_t* total_bytes) {
+    return hipSetDevice(device) == hipSuccess && hipMemGetInfo(free_bytes, total_bytes) == hipSuccess;
+}
+
 struct CountAllGather::Impl {
     int ranks = 0;
     size_t per_rank = 0;

@@ -27,3 +27,5 @@ class CountAllGather {
 };
 
 int visible_devices();
+// free and total memory of a device, in bytes (hipMemGetInfo); false when the device cannot be asked
+bool device_memory(int device, size_t* free_bytes, size_t* total_bytes);

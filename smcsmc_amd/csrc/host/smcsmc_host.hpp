@@ -209,7 +209,7 @@ class PfParam {
     bool record_all = false;                         // -record_all: no recording limit far from data
     int mig_cap = 0;                                 // -migcap: pf_params.mig_cap (0 = the library's default)
     int delay_cap = 0;                               // -delaycap: pf_params.delay_cap (0 = the library's default)
-    std::vector<std::string> chunk_notes;            // -chunks: one line per group of a rank's chunks, how they ran (written to the .log)
+    std::vector<std::string> chunk_notes;            // -chunks: one line per group of a rank's chunks, how they ran, and with -arg one per chunk naming its tree file (written to the .log)
     long long log_cap = 0;                           // -log_cap: pf_params.log_cap (0 = the library's default; -arg sizes its own)
     int count_wgs = 0;                               // -count_wgs: pf_params.count_wgs (0 = chosen here: the library's default, or tapered columns with six or more chunks per device)
     bool delay_evict = false;                        // -delay_evict: pf_params.flags bit 2
@@ -217,6 +217,8 @@ class PfParam {
     double segment_cap() const;                      // rows longer than this many bases are cut (pfparam.cpp:364)
     // ---- derived
     std::string out_path, log_path, recomb_map_path, resample_path, trees_path;
+    // -chunks: chunk c's own file, <prefix>.chunkC<suffix> (".recomb.gz", ".trees.gz", ".resample")
+    std::string chunk_file(int c, const char* suffix) const { return out_prefix + ".chunk" + std::to_string(c) + suffix; }
     std::vector<int> record_mask;    // per epoch
     std::vector<std::string> model_tokens;
     HostModel model;

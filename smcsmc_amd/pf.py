@@ -367,9 +367,11 @@ class ParticleFilter:
     def run_many(filters, s_begin=0, s_end=None):
         """Rows [s_begin, s_end) of several chunks (filters on one device, same shape and options) in lockstep: the launches
         of a row cover all of them (pf_run_many).  One-population chunks of at most 16 haplotypes (from 9 on the tree lives in LDS:
-        one extend launch and one launch of the other roles per row for all chunks, no tree recording, and all chunks of a group
+        one extend launch and one launch of the other roles per row for all chunks, no tree recording above 8 haplotypes, and all chunks of a group
         have the same number of haplotypes), or chunks of a structured model (two to four populations, at most 8 haplotypes: the
-        same two launches); no look-ahead, no tree recording with structure.  A chunk with fewer rows stops at its end and sits later
+        same two launches); no look-ahead, no tree recording with structure.  With record_trees, one population of at most 8 haplotypes
+        is taken (all filters of the group recording; log_cap / gen_cap may differ between them), and sample_tree_events() after
+        run_many + finish returns what it returns after run().  A chunk with fewer rows stops at its end and sits later
         calls out.  Every chunk gets the bits of its own run().  Raises PfError for a group can_run_many() refuses."""
         if s_end is None:
             s_end = max(f.n_segs for f in filters)
@@ -380,7 +382,8 @@ class ParticleFilter:
     def can_run_many(filters):
         """True when run_many would take these filters (pf_can_run_many); otherwise run them one after the other with run():
         more than 16 haplotypes, a structured model above 8, look-ahead, tree recording above 8 haplotypes or with structure,
-        a debug path, or chunks that differ in shape (12 haplotypes do not run with 16, nor 9 to 16 with 8 or fewer)."""
+        a debug path, or chunks that differ in shape (12 haplotypes do not run with 16, nor 9 to 16 with 8 or fewer, nor a
+        tree-recording filter with a plain one)."""
         if not filters:
             return False
         hs = (C.c_void_p * len(filters))(*[f.h for f in filters])
