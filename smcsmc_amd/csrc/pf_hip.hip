@@ -100,18 +100,37 @@ __device__ __forceinline__ int gridDim_particles(const KA& A) { return (int)((A.
 // derives the offspring offsets of its own particles and finds the parent of each of its slots by a two-level search
 // over the pilot prefix sums -- no offspring / parent table from an earlier kernel is read --, reads the previous row
 // from one slot of the state ring and writes this row into the next, and leaves the offspring table for the ledger.
-template <int NM, bool BIASED, bool EXACT = false, bool TREES = false, bool PIPE = false, class KA>
-__device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fuse, PipeRow PR = PipeRow()) {
+// HEAD (with PIPE; k_sweep4, k_sweep4q, k_sweep4t): the addresses of the head come from the row header H (SweepHead in registers, pf_pipe.h), which
+// the caller has loaded in one batch.  Every request of the head then goes out back to back in the order the prologue consumes them --
+// the partials of the decision and last1, the note on the row before, the scans the parent search stages, the particle's own state and
+// counters, the epoch tables, the row's segment last -- and nothing is waited for before the last one is out.  What every lane loads
+// from one address (the note, last1, the segment) would be moved to scalar registers, behind a wait, right where it is loaded: those
+// values stay in vector registers until pf_arrive() where they are first used.  PR.pos_prev is not used: the end of row s - 1 is
+// requested with the rest.
+__device__ __forceinline__ int pf_arrive(int v) { asm volatile("" : "+v"(v)); return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ long long pf_arrive(long long v) {
+    asm volatile("" : "+v"(v));
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v & 0xffffffffu));
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ double pf_arrive(double v) { return __longlong_as_double(pf_arrive(__double_as_longlong(v))); }
+
+template <int NM, bool BIASED, bool EXACT = false, bool TREES = false, bool PIPE = false, bool HEAD = false, class KA>
+__device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fuse, PipeRow PR = PipeRow(), const SweepHeadR& H = SweepHeadR()) {
+    static_assert(!HEAD || PIPE, "the row header belongs to the row pipeline");
     extern __shared__ double smem[];
+    int E_head; long long Np_head; int n_head;
+    if constexpr (HEAD) { E_head = PF_HI(H, E); Np_head = PF_HL(H, Np); n_head = PF_HI(H, n); } else { E_head = A.E; Np_head = A.Np; n_head = A.n; }
     double* sT = smem;                            // epoch starts and ...
     double* sH = smem + PF_EPAD;                  // ... cumulative coalescence intensity there, both padded with +inf (r_search4)
     double* sI = sH + PF_EPAD;
-    double* sBH = sI + A.E;                       // bias band boundaries / strengths (focused sampling)
+    double* sBH = sI + E_head;                    // bias band boundaries / strengths (focused sampling)
     double* sBS = sBH + (PF_BIAS_MAX + 2);
     const Ctrl* c = A.ctrl;
-    const int n = EXACT ? NM : A.n;
+    const int n = EXACT ? NM : n_head;
     const long long p = (long long)pf_bx() * PF_BS + threadIdx.x;
-    const bool active = p < A.Np;
+    const bool active = p < Np_head;
     const int lane = threadIdx.x & 63;
     // PIPE: everything the prologue and the particle itself need from memory is requested first, in one round trip: the
     // partials of the decision, this slot's own state of the previous row (what most rows continue from, and what the
@@ -135,7 +154,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
     int sg_allele[NM];
 #pragma unroll
     for (int i = 0; i < NM; ++i) sg_allele[i] = 0;
-    if constexpr (PIPE) {
+    if constexpr (PIPE && !HEAD) {
         if (PR.extend) {
             sg_start = A.seg_start[s]; sg_len = A.seg_len[s];
             sg_limit = A.seg_limit[s]; sg_state = A.seg_state[s];
@@ -144,7 +163,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = al[i];
         }
     }
-    if constexpr (PIPE) {
+    if constexpr (PIPE && !HEAD) {
         const int fs = __builtin_amdgcn_readfirstlane(PR.slot_prev >= 0 ? PR.slot_prev : c->cur);
         if (PR.complete) {
             pre = row_preload(A, fs);
@@ -186,19 +205,104 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             if (PR.complete) o_sm = A.rg_scan1m[(size_t)fs * A.Np + p];
         }
     }
-    for (int e = threadIdx.x; e < PF_EPAD; e += blockDim.x) {
-        sT[e] = e < A.E ? A.T[e] : PF_INF;
-        sH[e] = e < A.E ? A.Hc[e] : PF_INF;
-        if (e < A.E) sI[e] = A.inv2N[e];
-    }
-    if (BIASED && threadIdx.x < PF_BIAS_MAX + 2) {
-        sBH[threadIdx.x] = A.bias_H[threadIdx.x];
-        if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
-    }
     __shared__ unsigned s_lut[PIPE ? 2 * PF_LUT_N / 4 : 1];
-    const bool use_lut = PIPE && A.lut != nullptr;
-    if constexpr (PIPE) {
-        if (use_lut && threadIdx.x < 2 * PF_LUT_N / 4) s_lut[threadIdx.x] = ((const unsigned*)A.lut)[threadIdx.x];
+    bool use_lut = false;
+    double h_T = PF_INF, h_Hc = PF_INF, h_I = 0.0, sgp_start = 0.0, sgp_len = 0.0;
+    unsigned h_lut = 0;
+    if constexpr (HEAD) {
+        static_assert(PF_EPAD <= PF_BS && 2 * PF_LUT_N / 4 <= PF_BS && !BIASED, "one table entry a thread");
+        const int nc = PF_HI(H, nc);
+        // the state the row continues from: ring slot slot_prev, or on the first step of a call the slot Ctrl::cur names
+        auto pS = PF_HP(H, S); auto pC = PF_HP(H, C); auto pwpost = PF_HP(H, w_post); auto pwpil = PF_HP(H, w_pilot);
+        auto pnext = PF_HP(H, next_base); auto pxm = PF_HP(H, x_mark); auto pml = PF_HP(H, mark_limit); auto pLt = PF_HP(H, Ltree);
+        auto pwidx = PF_HP(H, rg_widx);
+        if (!PR.complete) {
+            const long long dk = (long long)__builtin_amdgcn_readfirstlane(PF_HP(H, ctrl)->cur) - PF_HI(H, slot_prev), dN = dk * Np_head, n1 = n_head - 1;
+            pS += dN * n1; pC += dN * 2 * n1; pwpost += dN; pwpil += dN; pnext += dN; pxm += dN; pml += dN; pLt += dN;
+            pwidx = PF_HP(H, widx);
+        }
+        if (PR.complete) {
+            const int ch = threadIdx.x, perc = (nc + PF_BS - 1) / PF_BS;
+            pre.have = true;
+            if (ch < nc) { pre.vp = PF_HP(H, cpost)[ch]; pre.vs = PF_HP(H, csq)[ch]; pre.vl = PF_HP(H, cpil)[ch]; }
+            if (ch + PF_BS < nc) { pre.vp2 = PF_HP(H, cpost)[ch + PF_BS]; pre.vs2 = PF_HP(H, csq)[ch + PF_BS]; pre.vl2 = PF_HP(H, cpil)[ch + PF_BS]; }
+            // (the entry or the two entries of the prefix-maxima pass, row_preload; two plain guarded requests: behind an if / else chain
+            // the second one waited for everything before it)
+            const int cm = perc == 2 ? 2 * ch : ch;
+            if (perc <= 2 && cm < nc) pre.vm = PF_HP(H, cmx1)[cm];
+            if (perc == 2 && cm + 1 < nc) pre.vm2 = PF_HP(H, cmx1)[cm + 1];
+            pre.last1 = *PF_HP(H, last1);
+            asm volatile("" ::: "memory");
+            o_nres = PF_HP(H, xr_before)->n_res; o_bflag = PF_HP(H, xr_before)->flag; o_bgen = PF_HP(H, xr_before)->gen;
+            asm volatile("" ::: "memory");
+            // (the window of scans requested ahead of the parent search: as in the other form of the head above)
+            spec_lo = pf_bx() * (PF_BS / 64) - (PF_PIPE_STAGE - PF_BS / 64) / 2;
+            if (spec_lo > nc - PF_PIPE_STAGE) spec_lo = nc - PF_PIPE_STAGE;
+            if (spec_lo < 0) spec_lo = 0;
+            if (PF_HI(H, flags) & 256) spec_lo = -0x40000000;              // PF_DEBUG_NO_SPEC_STAGE
+#pragma unroll
+            for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) {
+                const long long src = (long long)spec_lo * 64 + k * PF_BS + threadIdx.x;
+                spec_sm[k] = (src >= 0 && src < Np_head) ? PF_HP(H, scan1m)[src] : PF_INF;
+            }
+            asm volatile("" ::: "memory");
+        }
+        // (every lane asks, the lanes behind the last particle for the last particle's and use nothing of it: requests under a lane
+        // condition come out with the widening of the bytes, and a wait, right behind them)
+        const __attribute__((address_space(1))) unsigned char* pCu = (const __attribute__((address_space(1))) unsigned char*)pC;
+        {
+            const long long q = active ? p : Np_head - 1;
+#pragma unroll
+            for (int r = 0; r < RTree<NM>::NI; ++r) {
+                t0.S[r] = 0.0; t0.C0[r] = 0; t0.C1[r] = 0;
+                if (r < n - 1) {
+                    t0.S[r] = pS[(size_t)r * Np_head + q];
+                    t0.C0[r] = pCu[(size_t)(2 * r) * Np_head + q];         // as loaded: sign-extended behind the prologue
+                    t0.C1[r] = pCu[(size_t)(2 * r + 1) * Np_head + q];
+                }
+            }
+            o_wpost = pwpost[q]; o_wpilot = pwpil[q]; o_next = pnext[q]; o_xmark = pxm[q];
+            o_ml = pml[q]; o_Ltree = pLt[q];
+            o_widx = pwidx[q];
+            o_ctr = PF_HP(H, rng_ctr)[q]; o_ebuf = PF_HP(H, ebuf)[q];
+            if (PR.draws) o_tab_end = (unsigned)PF_HP(H, dt_filled)[q];
+            o_sm = PF_HP(H, scan1m)[q];
+        }
+        asm volatile("" ::: "memory");
+        if ((int)threadIdx.x < E_head) { h_T = PF_HP(H, T)[threadIdx.x]; h_Hc = PF_HP(H, Hc)[threadIdx.x]; h_I = PF_HP(H, inv2N)[threadIdx.x]; }
+        use_lut = PF_HP(H, lut) != nullptr;
+        if (use_lut && threadIdx.x < 2 * PF_LUT_N / 4) h_lut = ((const __attribute__((address_space(1))) unsigned*)PF_HP(H, lut))[threadIdx.x];
+        asm volatile("" ::: "memory");
+        // (requested whatever the step, from rows the call has: a flush step and the first step of a call use none of them, and a
+        // request under a condition is one more join at which the value would have to be in its final register)
+        {
+            const long long s_first = PF_HL(H, s_begin), s_last = PF_HL(H, s_last);
+            const long long sq = s <= s_last ? s : s_last, sb = s > s_first ? s - 1 : s_first;
+            sgp_start = PF_HP(H, seg_start)[sb]; sgp_len = PF_HP(H, seg_len)[sb];
+            sg_start = PF_HP(H, seg_start)[sq]; sg_len = PF_HP(H, seg_len)[sq];
+            sg_limit = PF_HP(H, seg_limit)[sq]; sg_state = ((const __attribute__((address_space(1))) unsigned char*)PF_HP(H, seg_state))[sq];
+            // (as loaded, all four in one word where there are four: sign-extended where they arrive)
+            if constexpr (EXACT && NM == 4) sg_allele[0] = (int)*(const __attribute__((address_space(1))) unsigned*)(PF_HP(H, seg_alleles) + (size_t)sq * 4);
+            else {
+#pragma unroll
+                for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = ((const __attribute__((address_space(1))) unsigned char*)PF_HP(H, seg_alleles))[(size_t)sq * n + i];
+            }
+        }
+        asm volatile("" ::: "memory");
+    } else {
+        for (int e = threadIdx.x; e < PF_EPAD; e += blockDim.x) {
+            sT[e] = e < A.E ? A.T[e] : PF_INF;
+            sH[e] = e < A.E ? A.Hc[e] : PF_INF;
+            if (e < A.E) sI[e] = A.inv2N[e];
+        }
+        if (BIASED && threadIdx.x < PF_BIAS_MAX + 2) {
+            sBH[threadIdx.x] = A.bias_H[threadIdx.x];
+            if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
+        }
+        use_lut = PIPE && A.lut != nullptr;
+        if constexpr (PIPE) {
+            if (use_lut && threadIdx.x < 2 * PF_LUT_N / 4) s_lut[threadIdx.x] = ((const unsigned*)A.lut)[threadIdx.x];
+        }
     }
     // ---- what completing the previous row needs ----
     int cur = 0, from_slot = 0;
@@ -215,10 +319,14 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         pos_prev = PR.pos_prev;
         if (completing) {
             const int row_slot = from_slot;                        // ring slot of the row being completed
+            if constexpr (HEAD) {
+                PF_STAMP(1);
+                pre.last1 = pf_arrive(pre.last1); o_nres = pf_arrive(o_nres); o_bflag = pf_arrive(o_bflag); o_bgen = pf_arrive(o_bgen);
+            }
             const long long n_res = o_nres + o_bflag;
             G_end = o_bgen + o_bflag;
             ev = (int)n_res;
-            PF_STAMP(1);
+            if constexpr (!HEAD) PF_STAMP(1);
 #pragma unroll
             for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) q.stage[k * PF_BS + threadIdx.x] = spec_sm[k];    // visible after decide_row's barriers
             RowDecision d = decide_row<true>(A, q, row_slot, n_res, pre);
@@ -346,6 +454,23 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         from_slot = gather ? (cur ^ 1) : cur;
         __syncthreads();
     }
+    if constexpr (HEAD) {
+        // the tables of the update loop go to LDS here, behind the decision: nothing before this point reads them
+        if (threadIdx.x < PF_EPAD) {
+            sT[threadIdx.x] = h_T; sH[threadIdx.x] = h_Hc;
+            if ((int)threadIdx.x < E_head) sI[threadIdx.x] = h_I;
+        }
+        if (use_lut && threadIdx.x < 2 * PF_LUT_N / 4) s_lut[threadIdx.x] = h_lut;
+#pragma unroll
+        for (int r = 0; r < RTree<NM>::NI; ++r) {
+            asm volatile("" : "+v"(t0.C0[r]), "+v"(t0.C1[r]));
+            t0.C0[r] = (int)(int8_t)t0.C0[r]; t0.C1[r] = (int)(int8_t)t0.C1[r];
+        }
+        if (completing && s > PF_HL(H, s_begin)) {
+            const double e = pf_arrive(sgp_start) + pf_arrive(sgp_len), Lq = A.L;       // sweep_seg_pos of row s - 1
+            pos_prev = e < Lq ? e : Lq;
+        } else pos_prev = 0.0;
+    }
     if constexpr (PIPE) __syncthreads();
     PF_STAMP(3);
     // wave-uniform slots: indexed kernel arguments stay scalar loads (a lane-varying index would put them on the stack)
@@ -468,6 +593,23 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
 
         PF_STAMP(4);
         const bool do_extend = !PIPE || PR.extend != 0;
+        if constexpr (HEAD) {
+            if (!do_extend) {
+                sg_start = 0.0; sg_len = 0.0; sg_limit = 0; sg_state = 1;
+#pragma unroll
+                for (int i = 0; i < NM; ++i) sg_allele[i] = 0;
+            } else {
+                sg_start = pf_arrive(sg_start); sg_len = pf_arrive(sg_len); sg_limit = pf_arrive(sg_limit); sg_state = (int)(int8_t)pf_arrive(sg_state);
+                if constexpr (EXACT && NM == 4) {
+                    const unsigned w = (unsigned)pf_arrive(sg_allele[0]);
+#pragma unroll
+                    for (int i = 0; i < NM; ++i) sg_allele[i] = (int)(int8_t)(w >> (8 * i));
+                } else {
+#pragma unroll
+                    for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = (int)(int8_t)pf_arrive(sg_allele[i]);
+                }
+            }
+        }
         const int8_t* data = A.seg_alleles + (size_t)s * n;
         double seg_end = 0.0;
         int limit = 0;
@@ -1946,7 +2088,8 @@ __device__ __forceinline__ void pipe_count_item(const KA& A, const PipeLaunch& P
     count_body<NM, P, EXACT>(A, Q, e, r.wa[e], r.wb[e], cbx, cnb);
 }
 
-template <int NM, bool BIASED, bool EXACT, bool TREES, int P = 1, bool BLC = false, bool QUEUE = false, bool LEAN = false, class KA>
+// (NO_EXTEND: the caller has run the extend role itself -- sweep_kernel_body with the row header)
+template <int NM, bool BIASED, bool EXACT, bool TREES, int P = 1, bool BLC = false, bool QUEUE = false, bool LEAN = false, bool NO_EXTEND = false, class KA>
 __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeLaunch& PL, const Windows& Wb) {
     const int bx = pf_bx();
     const int nb = PL.nb;
@@ -1954,7 +2097,7 @@ __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeL
     // are what would keep it from four workgroups per compute unit)
     if constexpr (!LEAN) {
         if (bx < nb) {
-            if constexpr (P == 1 && !BLC) { if (PL.row.extend || PL.row.complete) extend_reg_body<NM, BIASED, EXACT, TREES, true>(A, s, 0, PL.row); }
+            if constexpr (P == 1 && !BLC && !NO_EXTEND) { if (PL.row.extend || PL.row.complete) extend_reg_body<NM, BIASED, EXACT, TREES, true>(A, s, 0, PL.row); }
             return;
         }
         if (bx == nb) {
@@ -2062,12 +2205,15 @@ __device__ __forceinline__ unsigned long long* wg_trace_slot(SweepChunkC& ch, lo
     return ch.trace + ((size_t)(t - ch.trace_t0) * (size_t)ch.trace_stride + lin) * 4;
 }
 
-template <int NM, bool BIASED, bool EXACT, bool TREES, bool TRACE = false, bool QUEUE = false>
+// HEAD: the extend workgroups take the plan of the step and the addresses of their head from the chunk's row header (SweepHead,
+// pf_pipe.h): entry t & (PF_RING - 1), which lies in front of the chunk table at an address the kernel arguments give (sweep_head_of),
+// loaded in one batch -- two dependent scalar round trips in front of the first request where sweep_plan and the argument block had
+// ten.  The other roles plan as before.
+template <int NM, bool BIASED, bool EXACT, bool TREES, bool TRACE = false, bool QUEUE = false, bool HEAD = false>
 __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long long t, int nb) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[pf_chunk()];
     KArgsC& A = ch.A;
-    const long long s = ch.s_begin + t;
     __shared__ Windows W;           // written and read by the bookkeeping workgroup only
     if constexpr (TRACE) {
         if (threadIdx.x == 0) {
@@ -2078,11 +2224,33 @@ __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long 
             }
         }
     }
-    PipeLaunch PL;
-    if (sweep_plan(ch, s, nb, PL)) {
-        if (ch.split == 2) PL.nL = -3;                     // extend, bookkeeping and draw roles only: ledger and counts are k_sweep_blc's (run_sweep_split)
-        if (pf_bx() == nb && PL.b_slot >= 0) sweep_windows(A, A.ctrl, PL.b_pos, W);
-        pipe_roles<NM, BIASED, EXACT, TREES, 1, false, QUEUE>(A, s, PL, W);
+    if (HEAD && pf_bx() < nb) {
+        if constexpr (HEAD) {
+            // (nothing is outstanding here: said so that no request of the other roles' code is taken for pending in this one's)
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            const SweepHeadR H(sweep_head_of((SweepHeadC*)tab_g, pf_chunk(), t));
+            // sweep_plan for the extend role, from the entry alone (the second flush step has nothing for this role)
+            const long long s_begin = PF_HL(H, s_begin), s_last = PF_HL(H, s_last), sx = s_begin + t;
+            if (s_last >= s_begin && sx <= s_last + 1) {
+                PipeRow PR;
+                PR.extend = sx <= s_last ? 1 : 0;
+                PR.complete = sx > s_begin ? 1 : 0;
+                PR.slot_prev = PR.complete ? (int)((sx - 1) & (PF_RING - 1)) : -1;
+                PR.slot_out = (int)(sx & (PF_RING - 1));
+                PR.pos_prev = 0.0;                                 // (the end of row s - 1 is requested with the head)
+                PR.draws = PF_HI(H, nT) > 0 ? 1 + (int)(sx & 1) : 0;
+                PR.ahead = (PF_HI(H, split) || PF_HI(H, P) > 1) ? 1 : 0;
+                extend_reg_body<NM, BIASED, EXACT, TREES, true, true>(A, sx, 0, PR, H);
+            }
+        }
+    } else {
+        const long long s = ch.s_begin + t;
+        PipeLaunch PL;
+        if (sweep_plan(ch, s, nb, PL)) {
+            if (ch.split == 2) PL.nL = -3;                 // extend, bookkeeping and draw roles only: ledger and counts are k_sweep_blc's (run_sweep_split)
+            if (pf_bx() == nb && PL.b_slot >= 0) sweep_windows(A, A.ctrl, PL.b_pos, W);
+            pipe_roles<NM, BIASED, EXACT, TREES, 1, false, QUEUE, false, HEAD>(A, s, PL, W);
+        }
     }
     if constexpr (TRACE) {
         __syncthreads();
@@ -2100,17 +2268,17 @@ __global__ __launch_bounds__(PF_BS) void k_sweep(const SweepChunk* tab_g, long l
 // spill to scratch memory under the same attribute; they stay as they are.)
 template <bool EXACT, bool TREES>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_sweep4(const SweepChunk* tab_g, long long t, int nb) {
-    sweep_kernel_body<4, false, EXACT, TREES>(tab_g, t, nb);
+    sweep_kernel_body<4, false, EXACT, TREES, false, false, true>(tab_g, t, nb);
 }
 // the headline instance with the ledger and count work of a step taken off a queue (pf_params.count_workers; the traced form too)
 template <bool EXACT, bool TRACE>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_sweep4q(const SweepChunk* tab_g, long long t, int nb) {
-    sweep_kernel_body<4, false, EXACT, false, TRACE, true>(tab_g, t, nb);
+    sweep_kernel_body<4, false, EXACT, false, TRACE, true, true>(tab_g, t, nb);
 }
 // the headline instance with a time stamp at either end of every workgroup (pf_set_wg_trace: where do the slots of a step go?)
 template <bool EXACT>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_sweep4t(const SweepChunk* tab_g, long long t, int nb) {
-    sweep_kernel_body<4, false, EXACT, false, true>(tab_g, t, nb);
+    sweep_kernel_body<4, false, EXACT, false, true, false, true>(tab_g, t, nb);
 }
 
 // The bookkeeping, ledger and count roles of a step as a launch of their own: what the structured models run on the counting
@@ -2648,6 +2816,8 @@ struct pf_handle {
     std::vector<hipEvent_t> ev_x, ev_blc;   // completion of the last 16 extend / bookkeeping-ledger-count launches
     bool no_spec_stage = false;   // PF_DEBUG_NO_SPEC_STAGE
     SweepChunk* d_sweep = nullptr; // device table of the chunks this handle leads through k_sweep
+    char* d_sweep_base = nullptr;  // the allocation: the chunks' row headers (SweepHead, PF_RING entries a chunk) in front of the chunk table
+    std::vector<char> h_table;     // host copy of both as uploaded
     int d_sweep_cap = 0;
     std::vector<SweepChunk> h_sweep;
     // timing
@@ -2861,7 +3031,7 @@ static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device,
     h->debug = p->debug;
     h->no_count = (p->debug & PF_DEBUG_NO_COUNT) != 0;
     h->no_spec_stage = (p->debug & PF_DEBUG_NO_SPEC_STAGE) != 0;
-    h->split_batch = (p->debug >> 16) & 15;       // (bits 16-19 of debug: tuning experiments; 0 = four with several chunks, one with one)
+    h->split_batch = (p->debug >> 16) & 15;       // (bits 16-19 of debug: tuning experiments; 0 = four)
     // What this handle is allocated for, decided here and nowhere else: the rings of a row pipeline (sixteen copies of the state, the
     // second run-list copy, the decision rings, the count columns' table, smem_pipe) and the draw table.
     const size_t nc = (size_t)((Np + 63) / 64);
@@ -3182,7 +3352,7 @@ void pf_destroy(pf_handle* h) {
     if (h->stream) hipStreamSynchronize(h->stream);
     if (h->cstream) hipStreamSynchronize(h->cstream);
     for (void* p : h->allocs) hipFree(p);
-    if (h->d_sweep) hipFree(h->d_sweep);
+    if (h->d_sweep_base) hipFree(h->d_sweep_base);
     if (h->d_trace) hipFree(h->d_trace);
     for (auto e : h->sync_ev) if (e) hipEventDestroy(e);
     for (auto e : h->ev_x) if (e) hipEventDestroy(e);

@@ -3,6 +3,10 @@
 // row taken redundantly by every workgroup, the offspring offsets in closed form, the plan of a step, the per-chunk table
 // of k_sweep.  Workgroup size is a template parameter here (PF_BS differs between the two units).
 #pragma once
+#include <cstddef>
+#include <cstring>
+#include <type_traits>
+
 #include "pf_device.h"
 #include "pf_types.h"
 
@@ -207,6 +211,95 @@ struct SweepChunk {
     int workers;                   // pf_params.count_workers (PipeLaunch::workers)
 };
 typedef const __attribute__((address_space(4))) SweepChunk SweepChunkC;
+
+// The row header of the headline row kernels (k_sweep4, k_sweep4q, k_sweep4t): what the head of an extend workgroup reads, resolved on the
+// host once per call and uploaded in front of the chunk table (sweep_head_of).  Every address the head loads from is a function of the chunk's device pointers (fixed for the life of the handle)
+// and of the ring slots of the step, and those are (s_begin + t) mod PF_RING: one entry per chunk and ring phase, PF_RING entries a chunk,
+// entry t & (PF_RING - 1) for step t.  slot_prev = (s_begin + t - 1) & (PF_RING - 1) is the row the step completes and continues from,
+// and every pointer into a ring below already points at that slot.  An extend wavefront loads its entry in one batch behind the
+// kernel arguments (five lines of 64 bytes, what is used first in the first), waits once, derives the plan of the step from t and
+// the entry without another memory access and requests everything the head needs back to back.  (The first step of a call continues
+// from the slot Ctrl::cur names, which only the device knows: the kernel moves the eight state pointers by the difference of the
+// slots, sweep_head_first.)  No arrays of pointers: a run-time index into one would put the entry on the stack.
+struct SweepHead {
+    // line 0: the plan of the step and the bounds of the requests
+    long long s_begin, s_last, Np;
+    int nc, n, E, flags, nT, split, nblk, no_count, P, slot_prev;
+    // line 1: the decision on the row in slot_prev (per-wavefront partials [nc], the scan at the last particle, the note of the extend role
+    // of the step before: Ctrl::xr of slot_prev - 1), the pilot scans [Np] the parent search stages, the slots' record counters
+    const double* cpost; const double* csq; const double* cpil; const double* cmx1;
+    const double* last1; const Ctrl::ExtendNote* xr_before; const double* scan1m; const unsigned* rg_widx;
+    // line 2: the particle's own state in slot_prev
+    const double* S; const int8_t* C; const double* w_post; const double* w_pilot;
+    const double* next_base; const double* x_mark; const int* mark_limit; const double* Ltree;
+    // line 3: what a slot owns whatever the row (dt_filled: of the parity of the row before), the row's segment
+    const unsigned* widx; const unsigned long long* rng_ctr; const double* ebuf; const unsigned long long* dt_filled;
+    const double* seg_start; const double* seg_len; const int* seg_limit; const int8_t* seg_state;
+    // line 4: the alleles, the epoch tables and the bucket table that go to LDS
+    const int8_t* seg_alleles; const double* T; const double* Hc; const double* inv2N;
+    const unsigned char* lut; const Ctrl* ctrl; const void* pad_[2];
+};
+static_assert(sizeof(SweepHead) == 5 * 64, "SweepHead: five lines of sixteen words");
+typedef const __attribute__((address_space(4))) SweepHead SweepHeadC;
+// Where the entries are: in front of the chunk table, in the same allocation, chunk 0's PF_RING entries last -- `table` is the address of
+// the chunk table (what the kernels are given), so an entry's address takes nothing from memory.
+template <class H>
+__host__ __device__ inline H* sweep_head_of(H* table, int chunk, long long t) {
+    return table - ((size_t)chunk + 1) * PF_RING + (size_t)(t & (PF_RING - 1));
+}
+
+// An entry in scalar registers: its five lines requested together (five s_load_dwordx16 behind one address) and waited for once --
+// left to itself the compiler fetches every field where it is first used, a round trip each.  Fields are read with PF_HP (pointers),
+// PF_HL (64-bit integers) and PF_HI (32-bit integers) by their names in SweepHead; the words are compile-time positions in the lines.
+typedef int pf_line16 __attribute__((ext_vector_type(16)));
+struct SweepHeadR {
+    pf_line16 l0, l1, l2, l3, l4;
+    __device__ __forceinline__ SweepHeadR() : l0(0), l1(0), l2(0), l3(0), l4(0) {}
+    __device__ __forceinline__ explicit SweepHeadR(SweepHeadC* e) {
+        typedef const __attribute__((address_space(4))) pf_line16 LineC;
+        LineC* q = (LineC*)e;
+        l0 = q[0]; l1 = q[1]; l2 = q[2]; l3 = q[3]; l4 = q[4];
+        asm volatile("" : "+s"(l0), "+s"(l1), "+s"(l2), "+s"(l3), "+s"(l4));
+    }
+    template <int OFF> __device__ __forceinline__ unsigned word() const {
+        static_assert(OFF % 4 == 0 && OFF >= 0 && OFF < (int)sizeof(SweepHead), "a word of the entry");
+        constexpr int L = OFF / 64, K = (OFF % 64) / 4;
+        if constexpr (L == 0) return (unsigned)l0[K];
+        else if constexpr (L == 1) return (unsigned)l1[K];
+        else if constexpr (L == 2) return (unsigned)l2[K];
+        else if constexpr (L == 3) return (unsigned)l3[K];
+        else return (unsigned)l4[K];
+    }
+    template <int OFF> __device__ __forceinline__ unsigned long long dword() const {
+        return ((unsigned long long)word<OFF + 4>() << 32) | (unsigned long long)word<OFF>();
+    }
+};
+// (pointers come out in the global address space: one put together from two words would otherwise be a flat pointer, whose loads count
+// against both wait counters)
+#define PF_HP(R, f) ((__attribute__((address_space(1))) std::remove_pointer_t<decltype(SweepHead::f)>*)(R).template dword<(int)offsetof(SweepHead, f)>())
+#define PF_HL(R, f) ((long long)(R).template dword<(int)offsetof(SweepHead, f)>())
+#define PF_HI(R, f) ((int)(R).template word<(int)offsetof(SweepHead, f)>())
+
+// entry `phase` of chunk A for a call that starts at row s_begin (host; SweepFrame::table)
+inline SweepHead sweep_head_entry(const KArgs& A, const SweepChunk& ch, int phase) {
+    SweepHead H;
+    memset(&H, 0, sizeof(H));
+    const size_t sp = (size_t)((ch.s_begin + phase + PF_RING - 1) & (PF_RING - 1)), Np = (size_t)A.Np, nc = (size_t)A.nc;
+    H.s_begin = ch.s_begin; H.s_last = ch.s_last; H.Np = A.Np;
+    H.nc = A.nc; H.n = A.n; H.E = A.E; H.flags = A.flags; H.nT = ch.nT; H.split = ch.split; H.nblk = ch.nblk; H.no_count = ch.no_count; H.P = A.P;
+    H.slot_prev = (int)sp;
+    H.cpost = A.rg_cpost + sp * nc; H.csq = A.rg_csq + sp * nc; H.cpil = A.rg_cpil + sp * nc; H.cmx1 = A.rg_cmx1 + sp * nc;
+    H.last1 = &A.ctrl->last1[sp]; H.xr_before = &A.ctrl->xr[(sp + PF_RING - 1) & (PF_RING - 1)];
+    H.scan1m = A.rg_scan1m + sp * Np; H.rg_widx = A.rg_widx + sp * Np;
+    const DState st = state_slot(A, (int)sp);
+    H.S = st.S; H.C = st.C; H.w_post = st.w_post; H.w_pilot = st.w_pilot; H.next_base = st.next_base; H.x_mark = st.x_mark;
+    H.mark_limit = st.mark_limit; H.Ltree = st.Ltree;
+    H.widx = A.widx; H.rng_ctr = A.rng_ctr; H.ebuf = A.ebuf;
+    H.dt_filled = A.dt_filled ? A.dt_filled + (size_t)((ch.s_begin + phase + 1) & 1) * Np : nullptr;
+    H.seg_start = A.seg_start; H.seg_len = A.seg_len; H.seg_limit = A.seg_limit; H.seg_state = A.seg_state; H.seg_alleles = A.seg_alleles;
+    H.T = A.T; H.Hc = A.Hc; H.inv2N = A.inv2N; H.lut = A.lut; H.ctrl = A.ctrl;
+    return H;
+}
 
 template <class KA>
 __device__ __forceinline__ double sweep_seg_pos(const KA& A, long long s) {       // seg_pos() of the host

@@ -439,8 +439,13 @@ struct SweepFrame {
     // 1: there are steps to run, 0: none, -1: failed
     int table(long long s_end, int split) {
         if (h->d_sweep_cap < nh) {
-            if (h->d_sweep) { if (hipStreamSynchronize(h->stream) != hipSuccess || hipFree(h->d_sweep) != hipSuccess) return -1; }
-            if (hipMalloc((void**)&h->d_sweep, sizeof(SweepChunk) * (size_t)nh) != hipSuccess) { g_err = "hipMalloc of the chunk table failed"; return -1; }
+            // one allocation: the row headers of the chunks, chunk 0's last, and behind them the chunk table (sweep_head_of, pf_pipe.h)
+            if (h->d_sweep_base) { if (hipStreamSynchronize(h->stream) != hipSuccess || hipFree(h->d_sweep_base) != hipSuccess) return -1; }
+            h->d_sweep_base = nullptr; h->d_sweep = nullptr; h->d_sweep_cap = 0;
+            if (hipMalloc((void**)&h->d_sweep_base, (sizeof(SweepHead) * PF_RING + sizeof(SweepChunk)) * (size_t)nh) != hipSuccess) {
+                h->d_sweep_base = nullptr; g_err = "hipMalloc of the chunk table failed"; return -1;
+            }
+            h->d_sweep = (SweepChunk*)(h->d_sweep_base + sizeof(SweepHead) * PF_RING * (size_t)nh);
             h->d_sweep_cap = nh;
         }
         // the table of the previous call may still be read by its launches: a fresh host copy per call, uploaded in stream order
@@ -467,7 +472,16 @@ struct SweepFrame {
             if (last >= s_begin) steps = std::max(steps, last - s_begin + 3);
         }
         if (steps == 0) return 0;
-        if (hipMemcpyAsync(h->d_sweep, h->h_sweep.data(), sizeof(SweepChunk) * (size_t)nh, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+        // the row headers of the call (SweepHead, pf_pipe.h): PF_RING entries a chunk, from the chunk's pointers and s_begin / s_last
+        // (read by k_sweep4, k_sweep4q and k_sweep4t only: launch_sweep), uploaded with the chunk table in one copy
+        const size_t head_bytes = sizeof(SweepHead) * PF_RING * (size_t)nh, chunk_bytes = sizeof(SweepChunk) * (size_t)nh;
+        h->h_table.assign(head_bytes + chunk_bytes, 0);
+        SweepHead* heads_end = (SweepHead*)(h->h_table.data() + head_bytes);
+        if (h->P == 1 && h->n <= 4 && !is_biased(h))
+            for (int k = 0; k < nh; ++k)
+                for (int j = 0; j < PF_RING; ++j) *sweep_head_of(heads_end, k, j) = sweep_head_entry(h->h_sweep[k].A, h->h_sweep[k], j);
+        memcpy(h->h_table.data() + head_bytes, h->h_sweep.data(), chunk_bytes);
+        if (hipMemcpyAsync((char*)h->d_sweep - head_bytes, h->h_table.data(), head_bytes + chunk_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
             g_err = "upload of the chunk table failed"; return -1;
         }
         hipLaunchKernelGGL(k_sweep_seed, dim3(nh), dim3(PF_BS), 0, h->stream, h->d_sweep);
@@ -582,8 +596,9 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
     if (const int rc = F.table(s_end, 2); rc <= 0) return rc;
     const dim3 gx((unsigned)(nb + 1 + h->h_sweep[0].nT), (unsigned)nh), blk(PF_BS);
     // (at most four: the second launch of step t - 7 must be enqueued when step t waits for it.  Several chunks: eight 20 Mb chunks 1.205e5 ->
-    // 1.248e5 segments/s with two, 1.272e5 with four; one chunk is the same with any)
-    const long long batch = std::max(1, std::min(4, h->split_batch > 0 ? h->split_batch : (nh > 1 ? 4 : 1)));
+    // 1.248e5 segments/s with two, 1.272e5 with four.  One chunk was the same with any while its extend launch took 26 us; at 23 us the
+    // completion signal on every extend launch is what a row waits for -- 20 Mb, round 12: 4.00e4 segments/s with one, 4.27e4 with two or four)
+    const long long batch = std::max(1, std::min(4, h->split_batch > 0 ? h->split_batch : 4));
     std::vector<unsigned> pending_grid((size_t)batch, 1u);
     const bool queue = h->h_sweep[0].workers > 0;          // pf_params.count_workers: the second launch takes its items off a queue
     hipStreamWaitEvent(h->cstream, F.seeded, 0);
