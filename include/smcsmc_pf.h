@@ -337,6 +337,14 @@ int pf_test_uniform(uint64_t seed, uint32_t slot, uint32_t stream, uint64_t firs
                     int device);
 int pf_test_reduce(const double* x, int64_t n, double* out_sum, double* out_incl_scan, int device);
 int pf_test_systematic(const double* pilot, int64_t n, double u, int32_t* lo, int device);
+/* Device memory held by the library in this process, in bytes: the arrays of every open handle and the temporaries of a running call.
+ * 0 once every handle is destroyed, whatever the calls before returned. */
+int64_t pf_test_live_bytes(void);
+/* The first two steps of pf_create -- the refusals that need no device, then the plan of the handle -- without a device.  Returns -1 with
+ * pf_last_error() set to the refusal, or the number of values written to out[0..n_out): rings (0 none, 1 Reg: one population, at most 8
+ * haplotypes; 2 Xmp: structured, at most 8; 3 Xl: one population, 9 to 16), nslots, draw_table, smem, smem_pipe, ledger_wgs, ncw, workers,
+ * split_batch, mcap, dcap, pcap, RS, ncol, max_trace_events, E, and then cw_off[0..E]: 16 + E + 1 values. */
+int pf_test_plan(const pf_model* model, const pf_params* params, int32_t* out, int32_t n_out);
 
 #ifdef __cplusplus
 }

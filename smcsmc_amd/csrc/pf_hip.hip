@@ -2759,1606 +2759,10 @@ __global__ __launch_bounds__(PF_BS) void k_simulate(KArgs A, unsigned long long 
     simulate_lds_body(A, seed, nchunks, max_sites, pos_out, mask_out, n_out, smem);
 }
 
-// ------------------------------------------------------------------ host side
-static thread_local std::string g_err;
-const char* pf_last_error(void) { return g_err.c_str(); }
-
-#define HIPCHK(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            g_err = std::string(#call) + ": " + hipGetErrorString(e_);                    \
-            return -1;                                                                    \
-        }                                                                                 \
-    } while (0)
-
-// The row pipeline a handle's rings were allocated for at creation (create_impl); run_path() (pf_run.h) picks the runner from this, the debug
-// switches and the look-ahead.  None: two copies of the state, the general kernels or k_row.  Reg: one population, n <= 8, tree in registers
-// (k_sweep*).  Xmp: two to four populations, n <= 8 (k_sweep_xmp).  Xl: one population, 9 <= n <= 16, tree in LDS (k_sweep_xl, pf_run_many only).
-enum class Rings { None, Reg, Xmp, Xl };
-
-struct pf_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;      // filter stream: k_extend, k_decide, k_resample
-    hipStream_t cstream = nullptr;     // counting stream: k_count, k_ledger (off the critical path)
-    std::vector<hipEvent_t> sync_ev;   // ring of events ordering the two streams
-    size_t sync_next = 0;
-    hipEvent_t ev_dec = nullptr, ev_cnt = nullptr;   // last decide / last count+ledger
-    KArgs A;
-    std::vector<void*> allocs;
-    std::vector<double> h_lags, h_counted_to;
-    double h_L = 0;
-    std::vector<double> h_seg_start, h_seg_len;
-    long long n_segs = 0;
-    long long seg_done = 0;
-    int E = 0, n = 0, P = 1;
-    long long Np = 0;
-    int nblocks = 0;
-    size_t smem = 0, smem_la = 0;
-    int max_trace_events = 0;
-    bool finished = false;
-    bool fin_pending = false;     // k_count partials not yet folded into the totals
-    Windows step_windows;         // windows of the step being processed
-    int debug = 0;                // pf_params.debug: the PF_DEBUG_* switches that select a path are read from here (run_path)
-    Rings rings = Rings::None;
-    bool wide = false;            // one population on the wide kernels of pf_wide.hip: nsam > PF_NMAX, or PF_DEBUG_FORCE_WIDE (testing)
-    bool no_count = false;        // PF_DEBUG_NO_COUNT: no lagged counting, no ledger upkeep (profiling)
-    size_t smem_pipe = 0;         // dynamic LDS of the row pipeline's launches (rings != None)
-    int ncw = 0;                  // count workgroups per epoch in the row pipeline (pf_params.count_wgs): the most a column gets
-    int ledger_wgs = 192;         // workgroups per step that re-base the older generations' run lists after a resampling (beside one per particle block)
-    int workers = 0;              // pf_params.count_workers: workgroups per step that take the ledger and count items off a queue (0: one workgroup per item)
-    std::vector<int> cw_off;      // [E + 1] first count workgroup of the j-th column, oldest epoch first (KArgs::cw_off)
-    int split_batch = 0;          // run_sweep_split: the second launches enqueued in batches of this many steps behind one completion signal (0: chosen by the runner)
-    unsigned long long* d_trace = nullptr;   // pf_set_wg_trace (leader of a pf_run_many call): four words per workgroup and step
-    size_t trace_words = 0;
-    int trace_t0 = 0, trace_n = 0, trace_stride = 0, trace_grid[3] = {0, 0, 0};
-    size_t smem_sweep_x = 0;      // dynamic LDS of the extend launch of run_sweep_x (rings Xmp, Xl)
-    std::vector<hipEvent_t> ev_x, ev_blc;   // completion of the last 16 extend / bookkeeping-ledger-count launches
-    bool no_spec_stage = false;   // PF_DEBUG_NO_SPEC_STAGE
-    SweepChunk* d_sweep = nullptr; // device table of the chunks this handle leads through k_sweep
-    char* d_sweep_base = nullptr;  // the allocation: the chunks' row headers (SweepHead, PF_RING entries a chunk) in front of the chunk table
-    std::vector<char> h_table;     // host copy of both as uploaded
-    int d_sweep_cap = 0;
-    std::vector<SweepChunk> h_sweep;
-    // timing
-    int timing_period = 0;
-    struct Span { hipEvent_t a, b; int k; };
-    std::vector<Span> spans;
-    std::vector<hipEvent_t> ev_pool;
-    double span_overhead_ms = 0;  // what a pair of HIP events brackets when nothing is between them (subtracted from every span)
-    double k_ms[4] = {0, 0, 0, 0};
-    long long k_launches[4] = {0, 0, 0, 0};
-    long long k_timed[4] = {0, 0, 0, 0};
-};
-
-template <class T>
-static int dalloc(pf_handle* h, T** p, size_t count) {
-    void* q = nullptr;
-    HIPCHK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-    HIPCHK(hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), h->stream));
-    h->allocs.push_back(q);
-    *p = (T*)q;
-    return 0;
-}
-
-// Bucket table of r_search_lut for an ascending table tab[0..E) with tab[0] = 0: lut[j] = the largest e with tab[e] <= the
-// lower edge of bucket j, bucket j = the doubles whose upper sixteen bits are kbase + j (bucket 0 also takes everything
-// below, the last bucket everything above).  Returns false when the table spans more buckets than PF_LUT_N, when a bucket
-// holds more than two entries (the two probes of the device would not finish the search) or when the probes could leave
-// the padded table.
-static bool lut_build(const double* tab, int E, unsigned char* lut, int* kbase) {
-    auto key = [](double v) { uint64_t b; memcpy(&b, &v, 8); return (int)(b >> 48); };
-    auto edge = [](int k) { uint64_t b = (uint64_t)k << 48; double v; memcpy(&v, &b, 8); return v; };
-    if (E + 2 > PF_EPAD) return false;
-    for (int e = 0; e < E; ++e) if (!(tab[e] >= 0.0) || !std::isfinite(tab[e]) || (e > 0 && tab[e] < tab[e - 1])) return false;
-    if (E == 1 || !(tab[E - 1] > 0.0)) { memset(lut, 0, PF_LUT_N); *kbase = 0x3ff0; return E == 1; }
-    int first = 1;
-    while (first < E && tab[first] == 0.0) ++first;              // entries equal to tab[0] (an epoch of zero intensity at the start)
-    const int kb = key(tab[first]) - 1;
-    if (kb < 1 || key(tab[E - 1]) > kb + PF_LUT_N - 2) return false;
-    *kbase = kb;
-    for (int j = 0; j < PF_LUT_N; ++j) {
-        const double lo = j == 0 ? 0.0 : edge(kb + j);
-        int e = 0;
-        while (e + 1 < E && tab[e + 1] <= lo) ++e;
-        lut[j] = (unsigned char)e;
-        if (j + 1 < PF_LUT_N) {
-            const double hi = edge(kb + j + 1);
-            int inside = 0;
-            for (int q = e + 1; q < E && tab[q] < hi; ++q) ++inside;
-            if (inside > 2) return false;
-        } else if (e != E - 1) return false;
-    }
-    return true;
-}
-
-// cumulative coalescence intensity at the epoch starts, in exactly this order of operations on both sides of the
-// parity tests: Hc[0] = 0, Hc[e+1] = Hc[e] + (T[e+1] - T[e]) * inv2N[e]
-static std::vector<double> cumulative_intensity(const double* T, const std::vector<double>& inv2N, int E) {
-    std::vector<double> H(E, 0.0);
-    for (int e = 0; e + 1 < E; ++e) H[e + 1] = H[e] + (T[e + 1] - T[e]) * inv2N[e];
-    return H;
-}
-
-int pf_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-void pf_destroy(pf_handle* h);
-
-// per-epoch, per-population tables of a structured model (scrm Model::population_size / migration_rate /
-// single_mig_pop), prepared exactly as the oracle's fill_model does
-struct MpTables {
-    std::vector<double> inv2Np, mrate, mtot;
-    std::vector<double> cum_coal, cum_mig;     // [E*P] integrals of 1/2N_p and of the total emigration rate of p from 0 to the epoch start
-    std::vector<double> next_join;             // [E] start of the next epoch after e that moves a whole population (-ej), +inf if none
-    std::vector<int> jmap, spop, next_join_epoch;
-};
-static int build_mp_tables(const pf_model* m, MpTables& t) {
-    const int E = m->n_epochs, P = m->n_pops, n = m->nsam;
-    t.inv2Np.resize((size_t)E * P);
-    for (int i = 0; i < E * P; ++i) t.inv2Np[i] = 1.0 / (2.0 * m->pop_sizes[i]);
-    t.mrate.assign((size_t)E * P * P, 0.0);
-    if (m->mig_rates) t.mrate.assign(m->mig_rates, m->mig_rates + (size_t)E * P * P);
-    t.mtot.assign((size_t)E * P, 0.0);
-    for (int e = 0; e < E; ++e)
-        for (int a = 0; a < P; ++a) {
-            double sum = 0.0;
-            for (int b = 0; b < P; ++b) if (b != a) sum += t.mrate[((size_t)e * P + a) * P + b];
-            t.mtot[(size_t)e * P + a] = sum;
-        }
-    t.jmap.resize((size_t)E * P);
-    for (int e = 0; e < E; ++e)
-        for (int a = 0; a < P; ++a) {
-            int cur = a;
-            for (int step = 0; step <= P && m->single_mig; ++step) {
-                int nxt = cur;
-                for (int b = 0; b < P; ++b) {
-                    double pr = m->single_mig[((size_t)e * P + cur) * P + b];
-                    if (pr != 0.0 && pr != 1.0) { g_err = "partial single migration events (-es/-eps style) are not supported"; return -1; }
-                    if (pr == 1.0 && b != cur) { nxt = b; break; }
-                }
-                if (nxt == cur) break;
-                if (step == P) { g_err = "Cycle detected when moving individuals between populations"; return -1; }
-                cur = nxt;
-            }
-            t.jmap[(size_t)e * P + a] = cur;
-        }
-    // Tables of the structured walk (pf_mp.h mp_coalesce): the hazard of a lineage over a stretch that spans epochs is
-    // a difference of these; accumulated in this order, which the oracle restates.
-    t.cum_coal.assign((size_t)E * P, 0.0);
-    t.cum_mig.assign((size_t)E * P, 0.0);
-    for (int e = 0; e + 1 < E; ++e)
-        for (int a = 0; a < P; ++a) {
-            const double dt = m->change_times[e + 1] - m->change_times[e];
-            t.cum_coal[(size_t)(e + 1) * P + a] = t.cum_coal[(size_t)e * P + a] + dt * t.inv2Np[(size_t)e * P + a];
-            t.cum_mig[(size_t)(e + 1) * P + a] = t.cum_mig[(size_t)e * P + a] + dt * t.mtot[(size_t)e * P + a];
-        }
-    t.next_join.assign(E, INFINITY);
-    t.next_join_epoch.assign(E, E);
-    for (int e = E - 2; e >= 0; --e) {
-        bool moves = false;
-        for (int a = 0; a < P; ++a) moves |= t.jmap[(size_t)(e + 1) * P + a] != a;
-        t.next_join[e] = moves ? m->change_times[e + 1] : t.next_join[e + 1];
-        t.next_join_epoch[e] = moves ? e + 1 : t.next_join_epoch[e + 1];
-    }
-    t.spop.assign(n, 0);
-    if (m->sample_pops) t.spop.assign(m->sample_pops, m->sample_pops + n);
-    for (int v : t.spop) if (v < 0 || v >= P) { g_err = "sample population out of range"; return -1; }
-    return 0;
-}
-
-static int upload_mp_tables(const MpTables& t, KArgs& A, std::vector<void*>& allocs) {
-    double *d1, *d2, *d3, *d4, *d5, *d6; int *i1, *i2, *i3;
-    HIPCHK(hipMalloc(&i3, t.next_join_epoch.size() * 4)); allocs.push_back(i3);
-    HIPCHK(hipMemcpy(i3, t.next_join_epoch.data(), t.next_join_epoch.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&d4, t.cum_coal.size() * 8)); allocs.push_back(d4);
-    HIPCHK(hipMalloc(&d5, t.cum_mig.size() * 8)); allocs.push_back(d5);
-    HIPCHK(hipMalloc(&d6, t.next_join.size() * 8)); allocs.push_back(d6);
-    HIPCHK(hipMemcpy(d4, t.cum_coal.data(), t.cum_coal.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d5, t.cum_mig.data(), t.cum_mig.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d6, t.next_join.data(), t.next_join.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&d1, t.inv2Np.size() * 8)); allocs.push_back(d1);
-    HIPCHK(hipMalloc(&d2, t.mrate.size() * 8)); allocs.push_back(d2);
-    HIPCHK(hipMalloc(&d3, t.mtot.size() * 8)); allocs.push_back(d3);
-    HIPCHK(hipMalloc(&i1, t.jmap.size() * 4)); allocs.push_back(i1);
-    HIPCHK(hipMalloc(&i2, t.spop.size() * 4)); allocs.push_back(i2);
-    HIPCHK(hipMemcpy(d1, t.inv2Np.data(), t.inv2Np.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d2, t.mrate.data(), t.mrate.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d3, t.mtot.data(), t.mtot.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(i1, t.jmap.data(), t.jmap.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(i2, t.spop.data(), t.spop.size() * 4, hipMemcpyHostToDevice));
-    A.inv2Np = d1; A.mig_rate = d2; A.mig_tot = d3; A.join_map = i1; A.sample_pop = i2;
-    A.cum_coal = d4; A.cum_mig = d5; A.next_join = d6; A.next_join_epoch = i3;
-    return 0;
-}
-
-static pf_handle* create_impl(const pf_model* m, const pf_params* p, int device, long long log_cap, long long gen_cap) {
-    auto fail = [&](const std::string& msg) -> pf_handle* { g_err = msg; return nullptr; };
-    int ndev = pf_device_count();
-    if (ndev <= 0) return fail("pf_create: no HIP device available (there is no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail("pf_create: device index out of range");
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX) return fail("pf_create: n_pops must be in 1..4");
-    if (m->nsam < 2 || m->nsam > PF_NMAX_WIDE) return fail("pf_create: nsam must be in 2..64");
-    const bool wide = m->n_pops == 1 && (m->nsam > PF_NMAX || (p->debug & PF_DEBUG_FORCE_WIDE));
-    if (m->nsam > PF_NMAX && m->n_pops > 1) return fail("pf_create: more than 16 haplotypes need one population (structured models take nsam <= 16)");
-    if ((p->debug & PF_DEBUG_FORCE_WIDE) && m->n_pops > 1) return fail("pf_create: PF_DEBUG_FORCE_WIDE applies to one population only");
-    if (wide && (p->flags & 2)) return fail("pf_create: tree recording (-arg) needs nsam <= 16 (its descendant masks are 32 bits wide)");
-    if (m->n_epochs < 1 || m->n_epochs > PF_EMAX) return fail("pf_create: n_epochs must be in 1..64");
-    if (p->np < 1 || p->np > 262144) return fail("pf_create: np must be in 1..262144");
-    if (m->n_bias_heights < 0 || m->n_bias_heights > PF_BIAS_MAX) return fail("pf_create: at most 8 bias heights are supported");
-    if (m->n_bias_heights > 0 && (!m->bias_heights || !m->bias_strengths || !m->application_delays))
-        return fail("pf_create: bias_heights, bias_strengths and application_delays must all be given");
-    if (m->n_rate_segments > 0) {
-        if (!m->rate_positions || !m->rate_values || !m->leaf_rel_rates || !m->application_delays)
-            return fail("pf_create: rate_positions, rate_values, leaf_rel_rates and application_delays must all be given with a guide");
-        if (m->rate_positions[0] != 0.0) return fail("pf_create: the recombination guide must start at position 0");
-        for (int k = 0; k < m->n_rate_segments; ++k) {
-            if (k && !(m->rate_positions[k] > m->rate_positions[k - 1])) return fail("pf_create: guide segment starts must increase");
-            if (!(m->rate_values[k] > 0)) return fail("pf_create: guide recombination rates must be positive");
-            for (int i = 0; i < m->nsam; ++i)
-                if (!(m->leaf_rel_rates[(size_t)k * m->nsam + i] > 0)) return fail("pf_create: relative leaf rates of the guide must be positive");
-        }
-    }
-    pf_handle* h = new pf_handle();
-    h->device = device;
-    if (hipSetDevice(device) != hipSuccess) { delete h; return fail("hipSetDevice failed"); }
-    // (no stream priorities: a high-priority filter stream per handle gains nothing for one chunk and costs 30 % of the
-    // throughput when several chunks share the device -- priority streams share fewer hardware queues)
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail("hipStreamCreate failed"); }
-    if (hipStreamCreateWithFlags(&h->cstream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail("hipStreamCreate failed"); }
-    h->sync_ev.resize(512);
-    for (auto& e : h->sync_ev) if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) { delete h; return fail("hipEventCreate failed"); }
-    const int E = m->n_epochs, n = m->nsam;
-    const long long Np = p->np;
-    const int P = m->n_pops;
-    h->E = E; h->n = n; h->Np = Np; h->P = P;
-    h->wide = wide;
-    h->nblocks = (int)((Np + PF_BS - 1) / PF_BS);
-    const int mcap = p->mig_cap > 0 ? p->mig_cap : PF_MMAX;
-    if (mcap > 4096) { delete h; return fail("pf_create: mig_cap out of range"); }
-    h->smem = P > 1 ? pf_mp_smem_bytes(n, E, P, mcap) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
-    h->max_trace_events = std::max(0, p->max_trace_events);
-    if (p->flags & 2) {
-        // -arg: the parent table of every resampling is kept (it is the ancestry the tree dump walks back through).
-        // Structured models record trees on either row kernel: the register tree (nsam <= 8) or the LDS tree (any nsam
-        // they take, i.e. up to 16 -- the width of the descendant sets in a record -- and PF_DEBUG_FORCE_LDS).
-        if (gen_cap > 0x7fffffffLL / 2) gen_cap = 0x7fffffffLL / 2;
-        h->max_trace_events = (int)gen_cap;
-    }
-    h->debug = p->debug;
-    h->no_count = (p->debug & PF_DEBUG_NO_COUNT) != 0;
-    h->no_spec_stage = (p->debug & PF_DEBUG_NO_SPEC_STAGE) != 0;
-    h->split_batch = (p->debug >> 16) & 15;       // (bits 16-19 of debug: tuning experiments; 0 = four)
-    // What this handle is allocated for, decided here and nowhere else: the rings of a row pipeline (sixteen copies of the state, the
-    // second run-list copy, the decision rings, the count columns' table, smem_pipe) and the draw table.
-    const size_t nc = (size_t)((Np + 63) / 64);
-    const bool fits = Np <= 131072 && !wide;      // beyond that the decision tables outgrow the default dynamic LDS
-    const bool plain = !(p->flags & 2) && !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE));     // no -arg, no switch to another path
-    if (P == 1 && n <= 8 && fits) h->rings = Rings::Reg;      // (with a switch or a look-ahead that takes the rows elsewhere the rings are there, unused)
-    // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_x)
-    else if (P > 1 && n <= 8 && fits && plain) h->rings = Rings::Xmp;
-    // one population on the LDS tree, several chunks in lockstep (pf_run_many): the same rings, the extend role k_sweep_xl.  Not with a
-    // generation ring too short for an extend role that runs ahead of the counts (what pf_create refuses for structured models; here the
-    // general kernels serve such a handle as before)
-    else if (P == 1 && n > 8 && n <= PF_NMAX && fits && plain && gen_cap >= PF_RING + 4 && !(p->debug & PF_DEBUG_TWO_LAUNCH) && lds_pipe_tables_fit(n, (int)nc))
-        h->rings = Rings::Xl;
-    const bool has_rings = h->rings != Rings::None;
-    // draw table of k_sweep (draw_role)
-    const bool draw_table = h->rings == Rings::Reg && !(p->debug & (PF_DEBUG_K_PIPE | PF_DEBUG_NO_DRAW_TABLE));
-    if (has_rings) h->smem_pipe = ((size_t)(2 * PF_EPAD + E + 2 * PF_BIAS_MAX + 3) + pipe_lds_doubles((int)nc)) * 8;
-    // (several chunks per GPU -- the caller set count_wgs -- : on the rows that do not resample, nine in ten, these workgroups find nothing to do and
-    // leave after 2 us of a slot each; with 32 instead of 192 eight chunks gain 3 %, one chunk is the same either way: 28.7 us per row)
-    h->ledger_wgs = p->count_wgs > 0 ? 32 : std::max(16, std::min(PF_LEDGER_BLOCKS, 192));
-    h->h_lags.assign(m->lags, m->lags + E);
-    h->h_counted_to.assign(E, 0.0);
-    h->h_L = m->loci_length;
-    KArgs& A = h->A;
-    memset(&A, 0, sizeof(A));
-    A.E = E; A.n = n; A.flags = m->flags | (h->no_spec_stage ? 256 : 0);
-    A.flags |= p->debug & (7 << 20);        // profiling probes of the count role (bits 20, 21: the sums are then wrong on purpose)
-    A.L = m->loci_length; A.mu = m->mutation_rate; A.rho = m->recombination_rate;
-    A.Np = Np;
-    A.mcap = mcap;
-    A.ess_threshold = (double)Np * p->ess_fraction;
-    A.seed = p->seed;
-    int rc = 0;
-    double *dT, *dI, *dlag, *dHc; int* dRF;
-    rc |= dalloc(h, &dT, E); rc |= dalloc(h, &dI, E); rc |= dalloc(h, &dlag, E); rc |= dalloc(h, &dRF, E); rc |= dalloc(h, &dHc, E);
-    if (rc) { pf_destroy(h); return nullptr; }
-    std::vector<double> inv2N(E);
-    for (int e = 0; e < E; ++e) inv2N[e] = 1.0 / (2.0 * m->pop_sizes[(size_t)e * P]);
-    A.P = P;
-    {
-        const int PT = P <= 2 ? P : PF_PMAX;     // k_count is instantiated for 1, 2 and PF_PMAX populations
-        A.ncol = PT == 1 ? 6 : 3 * PT + 3 + PT * PT + 2 * PT;
-    }
-    if (P > 1) {
-        MpTables tb;
-        if (build_mp_tables(m, tb) || upload_mp_tables(tb, A, h->allocs)) { pf_destroy(h); return nullptr; }
-    }
-    if (m->vb_coal_counts) {
-        const size_t nc = (size_t)E * P, nm = (size_t)E * P * P;
-        double *cin, *cout_, *mout;
-        if (dalloc(h, &cin, nc + nm) || dalloc(h, &cout_, nc) || dalloc(h, &mout, nm)) { pf_destroy(h); return nullptr; }
-        std::vector<double> cnt(nc + nm, 1e10);
-        for (size_t i = 0; i < nc; ++i) cnt[i] = m->vb_coal_counts[i];
-        if (m->vb_mig_counts) for (size_t i = 0; i < nm; ++i) cnt[nc + i] = m->vb_mig_counts[i];
-        for (double v : cnt) if (!(v > 0)) { pf_destroy(h); return fail("pf_create: variational-Bayes event counts must be positive"); }
-        hipMemcpyAsync(cin, cnt.data(), cnt.size() * 8, hipMemcpyHostToDevice, h->stream);
-        hipLaunchKernelGGL(k_vb_table, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream, cin, (long long)nc, cout_);
-        hipLaunchKernelGGL(k_vb_table, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, h->stream, cin + nc, (long long)nm, mout);
-        hipStreamSynchronize(h->stream);
-        A.vb_coal = cout_; A.vb_mig = mout;
-    }
-    hipMemcpyAsync(dT, m->change_times, E * 8, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(dI, inv2N.data(), E * 8, hipMemcpyHostToDevice, h->stream);
-    const std::vector<double> Hc = cumulative_intensity(m->change_times, inv2N, E);
-    hipMemcpyAsync(dHc, Hc.data(), E * 8, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(dlag, m->lags, E * 8, hipMemcpyHostToDevice, h->stream);
-    hipMemcpyAsync(dRF, m->record_flags, E * 4, hipMemcpyHostToDevice, h->stream);
-    hipStreamSynchronize(h->stream);
-    A.T = dT; A.inv2N = dI; A.Hc = dHc; A.lags = dlag; A.recflags = dRF;
-    A.lut = nullptr; A.lut_kbT = 0; A.lut_kbH = 0;
-    if (!(p->debug & PF_DEBUG_NO_SEARCH_LUT)) {
-        unsigned char lut[2 * PF_LUT_N];
-        if (lut_build(m->change_times, E, lut, &A.lut_kbT) && lut_build(Hc.data(), E, lut + PF_LUT_N, &A.lut_kbH)) {
-            unsigned char* dl;
-            rc |= dalloc(h, &dl, 2 * PF_LUT_N);
-            // on the handle's stream, behind the memset of dalloc (a plain hipMemcpy is not ordered with a non-blocking stream)
-            if (!rc) { hipMemcpyAsync(dl, lut, sizeof(lut), hipMemcpyHostToDevice, h->stream); hipStreamSynchronize(h->stream); A.lut = dl; }
-        }
-    }
-    A.n_bias = m->n_bias_heights;
-    A.delay_type = m->delay_type;
-    A.dcap = p->delay_cap > 0 ? p->delay_cap : PF_DCAP_DEFAULT;
-    A.delay_evict = (p->flags & 4) ? 1 : 0;
-    for (int k = 0; k < PF_BIAS_MAX + 2; ++k) A.bias_H[k] = HUGE_VAL;
-    for (int k = 0; k < PF_BIAS_MAX + 1; ++k) A.bias_S[k] = 1.0;
-    A.bias_H[0] = 0.0;
-    if (A.n_bias > 0 || m->n_rate_segments > 0) {
-        for (int k = 0; k < A.n_bias; ++k) A.bias_H[k + 1] = m->bias_heights[k];
-        for (int k = 0; k <= A.n_bias && A.n_bias > 0; ++k) A.bias_S[k] = m->bias_strengths[k];
-        double* dad;
-        if (dalloc(h, &dad, E)) { pf_destroy(h); return nullptr; }
-        // on the handle's stream, behind the memset of dalloc: a plain hipMemcpy is not ordered with a non-blocking stream, and
-        // the memset, queued behind those of the state arrays, could land after it and leave every delay at zero
-        hipMemcpyAsync(dad, m->application_delays, E * 8, hipMemcpyHostToDevice, h->stream);
-        hipStreamSynchronize(h->stream);
-        A.app_delays = dad;
-    }
-    A.blk_gran = h->rings == Rings::Xmp ? 4 : 1;
-    {
-        const size_t K = has_rings ? PF_RING : 2;               // copies of the particle state (KArgs::st0)
-        A.nslots = (int)K;
-        DState& st = A.st0;
-        rc |= dalloc(h, &st.S, K * (size_t)(n - 1) * Np);
-        rc |= dalloc(h, &st.C, K * (size_t)2 * (n - 1) * Np);
-        rc |= dalloc(h, &st.w_post, K * Np);
-        rc |= dalloc(h, &st.w_pilot, K * Np);
-        rc |= dalloc(h, &st.next_base, K * Np);
-        rc |= dalloc(h, &st.x_mark, K * Np);
-        rc |= dalloc(h, &st.Ltree, K * Np);
-        rc |= dalloc(h, &st.mark_limit, K * Np);
-        if (P > 1) {
-            rc |= dalloc(h, &st.Pn, K * (size_t)(n - 1) * Np);
-            rc |= dalloc(h, &st.nm, K * Np);
-            rc |= dalloc(h, &st.Mt, K * (size_t)A.mcap * Np);
-            rc |= dalloc(h, &st.Mb, K * (size_t)A.mcap * Np);
-            rc |= dalloc(h, &st.Mq, K * (size_t)A.mcap * Np);
-        }
-        if (m->n_rate_segments > 0) rc |= dalloc(h, &st.ridx, K * Np);
-        if (m->n_bias_heights > 0 || m->n_rate_segments > 0) {
-            rc |= dalloc(h, &st.total_delayed, K * Np);
-            rc |= dalloc(h, &st.dcount, K * Np);
-            rc |= dalloc(h, &st.dpos, K * (size_t)A.dcap * Np);
-            rc |= dalloc(h, &st.dfac, K * (size_t)A.dcap * Np);
-            rc |= dalloc(h, &st.ddelta, K * (size_t)A.dcap * Np);
-            rc |= dalloc(h, &st.dk, K * (size_t)A.dcap * Np);
-        }
-    }
-    if (p->flags & 1) {
-        // 100-bp local recombination map (count.hpp:101-102, 115)
-        A.lmap_bins = (long long)(m->loci_length / 100.0) + 4;
-        rc |= dalloc(h, &A.lmap_opp, (size_t)A.lmap_bins);
-        rc |= dalloc(h, &A.lmap_cnt, (size_t)(n + 2) * A.lmap_bins);
-    }
-    if (m->n_rate_segments > 0) {
-        // RecombinationBias::set_model_rates (pfparam.hpp:199-211): the segments that start inside the locus
-        int K = 0;
-        while (K < m->n_rate_segments && m->rate_positions[K] < m->loci_length) ++K;
-        double *gp, *gr, *gl;
-        rc |= dalloc(h, &gp, K); rc |= dalloc(h, &gr, K); rc |= dalloc(h, &gl, (size_t)K * n);
-        if (!rc) {
-            hipMemcpyAsync(gp, m->rate_positions, (size_t)K * 8, hipMemcpyHostToDevice, h->stream);
-            hipMemcpyAsync(gr, m->rate_values, (size_t)K * 8, hipMemcpyHostToDevice, h->stream);
-            hipMemcpyAsync(gl, m->leaf_rel_rates, (size_t)K * n * 8, hipMemcpyHostToDevice, h->stream);
-            hipStreamSynchronize(h->stream);
-        }
-        A.g_K = K; A.g_pos = gp; A.g_rho = gr; A.g_leaf = gl;
-    }
-    rc |= dalloc(h, &A.rng_ctr, Np);
-    A.dt_tab = nullptr; A.dt_filled = nullptr; A.dt_ctr = nullptr;
-    if (draw_table) {
-        // 512 bytes per slot
-        rc |= dalloc(h, &A.dt_tab, (size_t)2 * PF_DRAW_RING * Np);
-        rc |= dalloc(h, &A.dt_filled, (size_t)2 * Np);
-        rc |= dalloc(h, &A.dt_ctr, (size_t)2 * Np);
-    }
-    rc |= dalloc(h, &A.ebuf, Np);
-    rc |= dalloc(h, &A.widx, Np);
-    A.cap = (unsigned)log_cap;
-    A.rec_trees = (p->flags & 2) ? 1 : 0;
-    A.RS = 5 + (n - 1) + (wide ? 1 : 0);          // the wide kernels' records: the cut branch's samples in a 64-bit word behind the heights
-    A.Gcap = (int)gen_cap;
-    rc |= dalloc(h, &A.log, (size_t)Np * A.cap * A.RS);
-    if (P > 1) {
-        // a genealogy update leaves one piece per (epoch, population) stretch of its path: a handful per record
-        A.pcap = (unsigned)(p->piece_cap > 0 ? p->piece_cap : 4 * log_cap);
-        rc |= dalloc(h, &A.plog, (size_t)Np * A.pcap * 3);
-        rc |= dalloc(h, &A.pidx, Np);
-    }
-    rc |= dalloc(h, &A.gstart, (size_t)A.Gcap * Np);
-    rc |= dalloc(h, &A.lo, (size_t)A.Gcap * (Np + 1));
-    rc |= dalloc(h, &A.gen_x0, A.Gcap);
-    rc |= dalloc(h, &A.parent, Np);
-    rc |= dalloc(h, &A.blkcnt2[0], (size_t)h->nblocks); rc |= dalloc(h, &A.blkcnt2[1], (size_t)h->nblocks);
-    rc |= dalloc(h, &A.run_st, (size_t)A.Gcap * Np);
-    rc |= dalloc(h, &A.run_anc, (size_t)A.Gcap * Np);
-    rc |= dalloc(h, &A.nruns, A.Gcap);
-    A.nc = (int)nc;
-    if (has_rings) {
-        rc |= dalloc(h, &A.run_st2, (size_t)A.Gcap * Np);
-        rc |= dalloc(h, &A.run_anc2, (size_t)A.Gcap * Np);
-        rc |= dalloc(h, &A.nruns2, A.Gcap);
-        rc |= dalloc(h, &A.rg_scan1, PF_RING * (size_t)Np); rc |= dalloc(h, &A.rg_scan1m, PF_RING * (size_t)Np);
-        rc |= dalloc(h, &A.rg_scanp, PF_RING * (size_t)Np); rc |= dalloc(h, &A.rg_widx, PF_RING * (size_t)Np);
-        rc |= dalloc(h, &A.rg_cpost, PF_RING * nc); rc |= dalloc(h, &A.rg_csq, PF_RING * nc); rc |= dalloc(h, &A.rg_cpil, PF_RING * nc);
-        rc |= dalloc(h, &A.rg_cpp, PF_RING * nc); rc |= dalloc(h, &A.rg_cmx1, PF_RING * nc); rc |= dalloc(h, &A.rg_coffp, PF_RING * nc);
-        rc |= dalloc(h, &A.rg_dpend, PF_RING * nc); rc |= dalloc(h, &A.rg_blkcnt, PF_RING * (size_t)h->nblocks * 4);
-    }
-    rc |= dalloc(h, &A.chunk_post, nc); rc |= dalloc(h, &A.chunk_sq, nc); rc |= dalloc(h, &A.chunk_pil, nc);
-    rc |= dalloc(h, &A.scan1, Np); rc |= dalloc(h, &A.chunk_off, nc); rc |= dalloc(h, &A.l2scan, nc);
-    rc |= dalloc(h, &A.scan1m, Np); rc |= dalloc(h, &A.chunk_mx1, nc);
-    rc |= dalloc(h, &A.chunk_dpend, nc);
-    rc |= dalloc(h, &A.chunk_pp, nc); rc |= dalloc(h, &A.l2scanp, nc);
-    for (int b = 0; b < 2; ++b) {
-        rc |= dalloc(h, &A.scanp2[b], Np); rc |= dalloc(h, &A.chunk_offp2[b], nc);
-        rc |= dalloc(h, &A.snap_w[b], Np); rc |= dalloc(h, &A.snap_S[b], (size_t)(n - 1) * Np);
-        rc |= dalloc(h, &A.snap_xm[b], Np); rc |= dalloc(h, &A.snap_ml[b], Np); rc |= dalloc(h, &A.snap_widx[b], Np);
-    }
-    // accumulators of the count workgroups per epoch (measured: four times as many count workgroups per epoch in the row
-    // pipeline made a row 15 % slower -- the launch then holds 5 000 workgroups of 30 KB LDS each, four rounds of the chip)
-    // per-epoch accumulators: one per count workgroup of a column (count_body)
-    A.nbx = h->nblocks;
-    // the row pipeline spreads an epoch's count tasks (the ancestor runs of the generations in its window: for the old epochs,
-    // whose lag is a few rows, nearly one per particle) over this many workgroups; fewer is slower (C3 shape, one chunk: 40
-    // workgroups 32.9 us per row, 16: 38.7, 8: 53.7, 4: 91.4, 2: 168 -- profiles/round3/count_wgs.md)
-    h->ncw = p->count_wgs > 0 ? std::min<int>(p->count_wgs, h->nblocks) : h->nblocks;
-    // (the queue has one kernel instance so far: one population, at most four haplotypes, no focused sampling, no -arg, single launch per step)
-    h->workers = (h->rings == Rings::Reg && !(p->debug & PF_DEBUG_K_PIPE) && n <= 4 && !(m->n_bias_heights > 0 || m->n_rate_segments > 0) && !(p->flags & 2)) ? std::max(0, std::min(p->count_workers, 4096)) : 0;
-    {
-        // count workgroups per epoch column of the row pipeline: the tasks of an epoch are the live ancestors of the generations in its
-        // window, about Np / (1 + depth), depth = generations between window and front, i.e. in proportion to its lag: a column whose
-        // lag is a few rows long gets all h->ncw workgroups, the young epochs' columns, whose workgroups mostly found nothing to do
-        // and left after their prologue, as few as two.  (What a workgroup finds it strides over: any number is correct.)
-        h->cw_off.assign(E + 1, 0);
-        for (int j = 0; j < E; ++j) {
-            const double lag = m->lags[E - 1 - j];
-            int w = (int)std::ceil((double)h->ncw * std::min(1.0, 2500.0 / std::max(lag, 1.0)));
-            // (a higher minimum -- 4, 8, 12, 15 -- changes nothing: the long count workgroups of a step are not those of narrow columns)
-            w = std::max(std::min(2, h->ncw), std::min(w, h->ncw));
-            // (only when the caller set count_wgs, i.e. runs several chunks side by side and wants fewer workgroups: a single chunk
-            // leaves most of the chip idle, and there every column is shortest with all the workgroups it can get)
-            if (p->count_wgs <= 0) w = h->ncw;
-            h->cw_off[j + 1] = h->cw_off[j] + w;
-        }
-        int* dcw = nullptr;
-        if (has_rings) {
-            rc |= dalloc(h, &dcw, E + 1);
-            if (!rc) { hipMemcpyAsync(dcw, h->cw_off.data(), (size_t)(E + 1) * 4, hipMemcpyHostToDevice, h->stream); hipStreamSynchronize(h->stream); }
-            // (with every column at full width the kernels compute column and workgroup from the index: no table)
-            A.cw_off = p->count_wgs <= 0 ? nullptr : dcw;
-        }
-    }
-    rc |= dalloc(h, &A.totals, (size_t)A.ncol * E);
-    rc |= dalloc(h, &A.partial, (size_t)E * A.nbx * A.ncol);
-    A.max_trace_events = h->max_trace_events;
-    rc |= dalloc(h, &A.ev_seg, (size_t)std::max(1, h->max_trace_events));
-    rc |= dalloc(h, &A.ev_parents, (size_t)std::max(1, h->max_trace_events) * Np);
-    rc |= dalloc(h, &A.ctrl, 1);
-    if (rc) { pf_destroy(h); return nullptr; }
-    if (wide && pf_wide_prepare(h->smem)) {
-        pf_destroy(h);
-        return fail("pf_create: the local-tree state does not fit the LDS of one workgroup");
-    }
-    if (P == 1 && !wide && h->smem > 64 * 1024) {
-        hipFuncSetAttribute((const void*)k_extend, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem);
-        hipFuncSetAttribute((const void*)k_init, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem);
-    }
-    // structured models: the LDS-tree kernels serve the prior tree and calibration for every n, the row kernel is the
-    // register-tree one for n <= 8
-    const bool lds_rows = P > 1 && (n > 8 || (p->debug & PF_DEBUG_FORCE_LDS));
-    if (h->smem > 160 * 1024 || (P > 1 && pf_mp_prepare(h->smem, A.mcap)) ||
-        (P > 1 && !lds_rows && pf_mp_reg_smem_bytes(E, P, A.mcap) > 160 * 1024)) {
-        pf_destroy(h);
-        return fail(P > 1 ? "pf_create: the local-tree state (tree, epoch tables and pf_params.mig_cap migration events per lane) does not fit the LDS of one workgroup"
-                          : "pf_create: the local-tree state does not fit the LDS of one workgroup");
-    }
-    // a row pipeline the device then refuses: the rings stay, the general kernels take the rows (and pf_run_many refuses)
-    auto demote = [&] { h->rings = Rings::None; };
-    if (h->rings == Rings::Xmp) {
-        h->smem_sweep_x = pf_mp_sweep_smem_bytes(E, P, A.mcap, A.nc);
-        if (pf_mp_sweep_prepare(h->smem_sweep_x)) demote();                  // the event lists and the decision tables do not fit together: the two-stream path
-    }
-    if (h->rings == Rings::Xl) {
-        // k_sweep_xl: the LDS of k_extend (the decision tables lie in the tree columns)
-        h->smem_sweep_x = h->smem;
-        // (the attribute belongs to the kernel, not to the handle: the largest any handle of the process has asked for, so that a
-        // handle of twelve haplotypes made after one of sixteen does not lower it)
-        static std::atomic<int> xl_smem{0};
-        int most = xl_smem.load();
-        while (most < (int)h->smem && !xl_smem.compare_exchange_weak(most, (int)h->smem)) {}
-        most = std::max(most, (int)h->smem);
-        if (most > 64 * 1024 &&
-            (hipFuncSetAttribute((const void*)k_sweep_xl<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
-             hipFuncSetAttribute((const void*)k_sweep_xl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)) {
-            (void)hipGetLastError();
-            demote();
-        }
-    }
-    return h;
-}
-
-pf_handle* pf_create(const pf_model* m, const pf_params* p, int device) {
-    // with -arg (flags bit 1) nothing may be overwritten: rings sized for a whole chunk by default
-    const bool trees = p && (p->flags & 2);
-    if (!m || !p) { g_err = "pf_create: null model or parameters"; return nullptr; }
-    // switches of launch arrangements that were removed: a stale caller is told so, it does not silently get the default
-    static const struct { int bit; const char* what; } removed[] = {
-        {64, "one population as two launches on two streams"}, {512, "count workgroups in ascending epoch order"},
-        {1024, "the two streams on disjoint compute units"}, {8192, "hand-off between launches through counters in memory"}};
-    for (const auto& r : removed)
-        if (p->debug & r.bit) { g_err = "pf_create: pf_params.debug bit " + std::to_string(r.bit) + " (" + r.what + ") selected a launch arrangement that has been removed"; return nullptr; }
-    if (p->log_cap < 0 || p->gen_cap < 0 || p->piece_cap < 0 || p->log_cap > 0x7fffffffLL || p->piece_cap > 0x7fffffffLL) {
-        g_err = "pf_create: ring capacities out of range";
-        return nullptr;
-    }
-    if ((p->gen_cap > 0 && p->gen_cap < 4) || (p->log_cap > 0 && p->log_cap < 4)) {
-        g_err = "pf_create: log_cap and gen_cap must be at least 4";
-        return nullptr;
-    }
-    if (p->gen_cap > 0 && p->gen_cap < PF_RING + 4 && m->n_pops > 1) {
-        g_err = "pf_create: gen_cap must be at least 20 when the extend role runs ahead of the counts (structured models)";
-        return nullptr;
-    }
-    // (more than 16 haplotypes: a record is 8 (n + 5) bytes, 552 at n = 64; the default ring then holds as many bytes per particle as
-    // the 16 384 records of n = 16 do, rounded down to a power of two: 8192 records up to n = 35, 4096 up to n = 64)
-    long long log_def = trees ? 131072 : 16384;
-    if (!trees && m->nsam > PF_NMAX) {
-        const long long fit = 16384LL * (5 + PF_NMAX - 1) / (5 + m->nsam);
-        log_def = 1;
-        while (log_def * 2 <= fit) log_def *= 2;
-    }
-    return create_impl(m, p, device, p->log_cap > 0 ? p->log_cap : log_def,
-                       p->gen_cap > 0 ? p->gen_cap : (trees ? 131072 : 8192));
-}
-
-void pf_destroy(pf_handle* h) {
-    if (!h) return;
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->cstream) hipStreamSynchronize(h->cstream);
-    for (void* p : h->allocs) hipFree(p);
-    if (h->d_sweep_base) hipFree(h->d_sweep_base);
-    if (h->d_trace) hipFree(h->d_trace);
-    for (auto e : h->sync_ev) if (e) hipEventDestroy(e);
-    for (auto e : h->ev_x) if (e) hipEventDestroy(e);
-    for (auto e : h->ev_blc) if (e) hipEventDestroy(e);
-    if (h->cstream) hipStreamDestroy(h->cstream);
-    for (auto& sp : h->spans) { hipEventDestroy(sp.a); hipEventDestroy(sp.b); }
-    for (auto e : h->ev_pool) hipEventDestroy(e);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
-}
-
-static int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string(what) + ": " + hipGetErrorString(e); return -1; }
-    return 0;
-}
-
-static int harvest_spans(pf_handle* h) {
-    for (auto& sp : h->spans) {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, sp.a, sp.b));
-        h->k_ms[sp.k] += std::max(0.0, (double)ms - h->span_overhead_ms);
-        h->k_timed[sp.k] += 1;
-        h->ev_pool.push_back(sp.a);
-        h->ev_pool.push_back(sp.b);
-    }
-    h->spans.clear();
-    return 0;
-}
-
-static hipEvent_t get_event(pf_handle* h) {
-    if (!h->ev_pool.empty()) { hipEvent_t e = h->ev_pool.back(); h->ev_pool.pop_back(); return e; }
-    hipEvent_t e;
-    hipEventCreate(&e);
-    return e;
-}
-
-struct Timed {
-    pf_handle* h; int k; bool on; hipEvent_t a, b; hipStream_t st;
-    Timed(pf_handle* h_, int k_, bool on_, hipStream_t st_ = nullptr) : h(h_), k(k_), on(on_), st(st_ ? st_ : h_->stream) {
-        h->k_launches[k] += 1;
-        if (on) { a = get_event(h); b = get_event(h); hipEventRecord(a, st); }
-    }
-    ~Timed() {
-        if (on) { hipEventRecord(b, st); h->spans.push_back({a, b, k}); }
-    }
-};
-
-static hipEvent_t next_sync_event(pf_handle* h) {
-    hipEvent_t e = h->sync_ev[h->sync_next];
-    h->sync_next = (h->sync_next + 1) % h->sync_ev.size();
-    return e;
-}
-
-int pf_sync(pf_handle* h) {
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->cstream));
-    if (h->fin_pending) {
-        hipLaunchKernelGGL(k_count_fin, dim3(1), dim3(256), 0, h->stream, h->A);
-        h->fin_pending = false;
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (harvest_spans(h)) return -1;
-    Ctrl c;
-    HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-    if (c.err) {
-        const char* msg = "unknown device error";
-        if (c.err == ERR_LOG_OVERFLOW) msg = "event log ring overflow (raise pf_params.log_cap)";
-        if (c.err == ERR_GEN_OVERFLOW) msg = "generation ledger overflow (raise pf_params.gen_cap)";
-        if (c.err == ERR_ZERO_PROB) msg = "Zero or negative probabilities";   /* pc.cpp:428-429 */
-        if (c.err == ERR_MIG_OVERFLOW) msg = "too many migration events on one local tree";
-        if (c.err == ERR_MP_INTERNAL) msg = "structured-model genealogy update: coalescence partners inconsistent";
-        if (c.err == ERR_NO_COALESCENCE) msg = "No final coalescence event was sampled!";   /* particle.cpp:1383 */
-        if (c.err == ERR_DELAY_OVERFLOW) msg = "delayed-factor store overflow (raise pf_params.delay_cap)";
-        g_err = msg;
-        return -2;
-    }
-    return 0;
-}
-
-int pf_init_prior(pf_handle* h, double initial_position) {
-    HIPCHK(hipSetDevice(h->device));
-    if (h->P > 1)
-        pf_mp_launch_init(h->A, initial_position, h->smem, h->stream);
-    else if (h->wide)
-        pf_wide_launch_init(h->A, initial_position, h->smem, h->stream);
-    else
-        hipLaunchKernelGGL(k_init, dim3(h->nblocks), dim3(PF_BS), h->smem, h->stream, h->A, initial_position);
-    if (check_launch("k_init")) return -1;
-    if (h->A.lmap_opp) {
-        HIPCHK(hipMemsetAsync(h->A.lmap_opp, 0, (size_t)h->A.lmap_bins * 8, h->stream));
-        HIPCHK(hipMemsetAsync(h->A.lmap_cnt, 0, (size_t)(h->n + 2) * h->A.lmap_bins * 8, h->stream));
-    }
-    std::fill(h->h_counted_to.begin(), h->h_counted_to.end(), 0.0);
-    HIPCHK(hipMemsetAsync(h->A.partial, 0, (size_t)h->E * h->A.nbx * h->A.ncol * 8, h->stream));
-    h->fin_pending = false;
-    h->ev_dec = nullptr; h->ev_cnt = nullptr;
-    h->seg_done = 0;
-    h->finished = false;
-    return 0;
-}
-
-int pf_load_segments(pf_handle* h, const pf_segments* sg) {
-    HIPCHK(hipSetDevice(h->device));
-    const long long S = sg->n;
-    double *ds, *dl; int8_t *dst, *dal; int* dlim;
-    int rc = 0;
-    rc |= dalloc(h, &ds, S); rc |= dalloc(h, &dl, S); rc |= dalloc(h, &dst, S);
-    rc |= dalloc(h, &dal, (size_t)S * h->n); rc |= dalloc(h, &dlim, S);
-    rc |= dalloc(h, &h->A.tr_T, S); rc |= dalloc(h, &h->A.tr_ess, S); rc |= dalloc(h, &h->A.tr_logl, S);
-    rc |= dalloc(h, &h->A.tr_flag, S);
-    if (rc) return -1;
-    HIPCHK(hipMemcpyAsync(ds, sg->start, S * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dl, sg->length, S * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dst, sg->state, S, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dal, sg->alleles, (size_t)S * h->n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(dlim, sg->max_record_epoch, S * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->A.seg_start = ds; h->A.seg_len = dl; h->A.seg_state = dst; h->A.seg_alleles = dal; h->A.seg_limit = dlim;
-    h->h_seg_start.assign(sg->start, sg->start + S);
-    h->h_seg_len.assign(sg->length, sg->length + S);
-    h->n_segs = S;
-    return 0;
-}
-
+// ------------------------------------------------------------------ host side: the C-ABI, in the headers below and nowhere above
+#include "pf_devmem.h"
+#include "pf_handle.h"
+#include "pf_create.h"
 #include "pf_run.h"
-
-int pf_finish(pf_handle* h) {
-    HIPCHK(hipSetDevice(h->device));
-    // smcsmc.cpp:371: normalize_probability once more, then the lag-free flush (373)
-    h->A.sp = (int)(h->seg_done & 1);
-    if (h->ev_cnt) hipStreamWaitEvent(h->stream, h->ev_cnt, 0);     // k_partials rewrites the parity buffers
-    hipLaunchKernelGGL(k_partials, dim3(h->nblocks), dim3(PF_BS), 0, h->stream, h->A);
-    h->step_windows = host_windows(h, h->h_L, true);
-    if (launch_decide(h, 0, 1, h->step_windows)) return -1;
-    if (launch_resample(h, 0)) return -1;    // flag == 0 in mode 1: in-place normalisation
-    if (launch_count(h, 0, h->step_windows)) return -1;
-    if (launch_ledger(h, 0)) return -1;
-    h->finished = true;
-    return pf_sync(h);
-}
-
-int64_t pf_num_segments_done(pf_handle* h) { return h->seg_done; }
-
-double pf_logl(pf_handle* h) {
-    if (pf_sync(h)) return NAN;
-    Ctrl c;
-    if (hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost) != hipSuccess) return NAN;
-    return c.logl;
-}
-
-int pf_get_counts(pf_handle* h, double* out, int32_t n) {
-    if (pf_sync(h)) return -1;
-    const int E = h->E, P = h->P;
-    if (n < PF_COUNTS_LEN2(E, P)) { g_err = "count buffer too small"; return -1; }
-    Ctrl c;
-    HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-    double* tail;
-    if (P == 1) {
-        HIPCHK(hipMemcpy(out, h->A.totals, (size_t)6 * E * 8, hipMemcpyDeviceToHost));
-        tail = out + 6 * E;
-    } else {
-        // device layout: totals[column][epoch]; columns as AccT<P>.  A kernel compiled for PF_PMAX populations
-        // (P == 3) still uses the column numbering of its template parameter.
-        const int PT = P == 2 ? 2 : PF_PMAX;
-        const int ncol = h->A.ncol;
-        std::vector<double> tot((size_t)ncol * E);
-        HIPCHK(hipMemcpy(tot.data(), h->A.totals, tot.size() * 8, hipMemcpyDeviceToHost));
-        auto col = [&](int k, int e) { return tot[(size_t)k * E + e]; };
-        double* o = out;
-        for (int stat = 0; stat < 3; ++stat) {                 // coal count, opp, weight [E][P]
-            for (int e = 0; e < E; ++e) for (int a = 0; a < P; ++a) o[e * P + a] = col(stat * PT + a, e);
-            o += E * P;
-        }
-        for (int stat = 0; stat < 3; ++stat) {                 // recomb count, opp, weight [E]
-            for (int e = 0; e < E; ++e) o[e] = col(3 * PT + stat, e);
-            o += E;
-        }
-        for (int e = 0; e < E; ++e) for (int a = 0; a < P; ++a) for (int b = 0; b < P; ++b)
-            o[(e * P + a) * P + b] = col(3 * PT + 3 + a * PT + b, e);
-        o += E * P * P;
-        for (int e = 0; e < E; ++e) for (int a = 0; a < P; ++a) o[e * P + a] = col(3 * PT + 3 + PT * PT + a, e);
-        o += E * P;
-        for (int e = 0; e < E; ++e) for (int a = 0; a < P; ++a) o[e * P + a] = col(3 * PT + 3 + PT * PT + PT + a, e);
-        o += E * P;
-        tail = o;
-    }
-    tail[0] = c.delayed_opp;
-    tail[1] = c.delayed_count;
-    tail[2] = (double)c.n_resample;
-    tail[3] = c.logl;
-    return 0;
-}
-
-int pf_get_local_recomb(pf_handle* h, double* opp_diff, double* counts, int64_t nbins) {
-    if (pf_sync(h)) return -1;
-    if (!h->A.lmap_opp) { g_err = "pf_get_local_recomb: the map was not recorded (pf_params.flags bit 0)"; return -1; }
-    const long long nb = h->A.lmap_bins;
-    std::vector<double> o(nb), c((size_t)(h->n + 2) * nb);
-    HIPCHK(hipMemcpy(o.data(), h->A.lmap_opp, o.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(c.data(), h->A.lmap_cnt, c.size() * 8, hipMemcpyDeviceToHost));
-    for (long long b = 0; b < nbins; ++b) {
-        opp_diff[b] = b < nb ? o[b] : 0.0;
-        for (int k = 0; k < h->n + 2; ++k) counts[(size_t)k * nbins + b] = b < nb ? c[(size_t)k * nb + b] : 0.0;
-    }
-    return 0;
-}
-
-int pf_get_migrations(pf_handle* h, int32_t* n_events, double* times, int8_t* branch, int8_t* newpop, int8_t* node_pops,
-                      int32_t cap) {
-    if (pf_sync(h)) return -1;
-    if (h->P < 2) { g_err = "pf_get_migrations: the model has one population"; return -1; }
-    Ctrl c;
-    HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-    const DState st = state_slot(h->A, c.cur);
-    const long long Np = h->Np;
-    const int n = h->n;
-    std::vector<int> nm(Np);
-    HIPCHK(hipMemcpy(nm.data(), st.nm, Np * 4, hipMemcpyDeviceToHost));
-    const int mcap = h->A.mcap;
-    std::vector<double> mt((size_t)mcap * Np);
-    std::vector<int8_t> mb((size_t)mcap * Np), mq((size_t)mcap * Np), pn((size_t)(n - 1) * Np);
-    HIPCHK(hipMemcpy(mt.data(), st.Mt, mt.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(mb.data(), st.Mb, mb.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(mq.data(), st.Mq, mq.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(pn.data(), st.Pn, pn.size(), hipMemcpyDeviceToHost));
-    for (long long p = 0; p < Np; ++p) {
-        if (n_events) n_events[p] = nm[p];
-        for (int k = 0; k < cap; ++k) {
-            bool ok = k < nm[p] && k < mcap;
-            if (times) times[p * cap + k] = ok ? mt[(size_t)k * Np + p] : 0.0;
-            if (branch) branch[p * cap + k] = ok ? mb[(size_t)k * Np + p] : 0;
-            if (newpop) newpop[p * cap + k] = ok ? (mq[(size_t)k * Np + p] & 3) : 0;      // the upper bits hold the event's epoch
-        }
-        if (node_pops) for (int r = 0; r < n - 1; ++r) node_pops[p * (n - 1) + r] = pn[(size_t)r * Np + p];
-    }
-    return 0;
-}
-
-int pf_get_trace(pf_handle* h, double* T, double* ess, int32_t* resampled, double* logl, int64_t n) {
-    if (pf_sync(h)) return -1;
-    long long m = std::min<long long>(n, h->seg_done);
-    if (m <= 0) return 0;
-    if (T) HIPCHK(hipMemcpy(T, h->A.tr_T, m * 8, hipMemcpyDeviceToHost));
-    if (ess) HIPCHK(hipMemcpy(ess, h->A.tr_ess, m * 8, hipMemcpyDeviceToHost));
-    if (logl) HIPCHK(hipMemcpy(logl, h->A.tr_logl, m * 8, hipMemcpyDeviceToHost));
-    if (resampled) HIPCHK(hipMemcpy(resampled, h->A.tr_flag, m * 4, hipMemcpyDeviceToHost));
-    return (int)m;
-}
-
-int pf_get_resample_events(pf_handle* h, int32_t* seg_idx, int32_t* parents, int32_t max_events) {
-    if (pf_sync(h)) return -1;
-    Ctrl c;
-    HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-    int nev = (int)std::min<long long>(std::min<long long>(c.n_resample, h->max_trace_events), max_events);
-    if (nev <= 0) return 0;
-    if (seg_idx) HIPCHK(hipMemcpy(seg_idx, h->A.ev_seg, (size_t)nev * 4, hipMemcpyDeviceToHost));
-    if (parents) HIPCHK(hipMemcpy(parents, h->A.ev_parents, (size_t)nev * h->Np * 4, hipMemcpyDeviceToHost));
-    return nev;
-}
-
-int pf_get_particles(pf_handle* h, double* w_post, double* w_pilot, double* heights, int8_t* children, double* next_base) {
-    if (pf_sync(h)) return -1;
-    Ctrl c;
-    HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-    const DState st = state_slot(h->A, c.cur);
-    const long long Np = h->Np;
-    const int n = h->n;
-    if (w_post) HIPCHK(hipMemcpy(w_post, st.w_post, Np * 8, hipMemcpyDeviceToHost));
-    if (w_pilot) HIPCHK(hipMemcpy(w_pilot, st.w_pilot, Np * 8, hipMemcpyDeviceToHost));
-    if (next_base) HIPCHK(hipMemcpy(next_base, st.next_base, Np * 8, hipMemcpyDeviceToHost));
-    if (heights) {
-        std::vector<double> tmp((size_t)(n - 1) * Np);
-        HIPCHK(hipMemcpy(tmp.data(), st.S, tmp.size() * 8, hipMemcpyDeviceToHost));
-        for (long long p = 0; p < Np; ++p)
-            for (int r = 0; r < n - 1; ++r) heights[p * (n - 1) + r] = tmp[(size_t)r * Np + p];
-    }
-    if (children) {
-        std::vector<int8_t> tmp((size_t)2 * (n - 1) * Np);
-        HIPCHK(hipMemcpy(tmp.data(), st.C, tmp.size(), hipMemcpyDeviceToHost));
-        for (long long p = 0; p < Np; ++p)
-            for (int k = 0; k < 2 * (n - 1); ++k) children[p * 2 * (n - 1) + k] = tmp[(size_t)k * Np + p];
-    }
-    return 0;
-}
-
-// Philox4x32-10 on the host (the same stream definition as philox_uniform in pf_device.h): the final one-particle draw
-// needs a single uniform
-static double philox_uniform_host(unsigned long long seed, unsigned slot, unsigned stream, unsigned long long draw) {
-    unsigned c0 = (unsigned)draw, c1 = (unsigned)(draw >> 32), c2 = slot, c3 = stream;
-    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned hi0 = (unsigned)(p0 >> 32), lo0 = (unsigned)p0, hi1 = (unsigned)(p1 >> 32), lo1 = (unsigned)p1;
-        const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const unsigned long long bits = (((unsigned long long)c0 << 32) | c1) >> 11;
-    return ((double)bits + 0.5) * 1.1102230246251565e-16;
-}
-
-// ------------------------------------------------------------------ -arg: the history of one particle
-// ParticleContainer::printTrees (pc.cpp:515-555) prints the tree-modifying events of the particle left by the final
-// one-particle draw (smcsmc.cpp:395).  Here: walk back through the generations (the parent tables of all resamplings
-// are kept with -arg), collect the record ranges of every ancestor, copy them out.
-__global__ void k_trace_ancestry(KArgs A, int G, int slot, int* out_slot, unsigned* out_k0, unsigned* out_k1) {
-    if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    long long a = slot;
-    for (int g = G; g >= 0; --g) {
-        out_slot[g] = (int)a;
-        out_k0[g] = A.gstart[(size_t)(g % A.Gcap) * A.Np + a];
-        out_k1[g] = g == G ? A.widx[a] : A.gstart[(size_t)((g + 1) % A.Gcap) * A.Np + a];
-        if (g > 0) a = A.ev_parents[(size_t)(g - 1) * A.Np + a];
-    }
-}
-__global__ void k_gather_records(KArgs A, int ngen, const int* slot, const unsigned* k0, const unsigned* k1, const long long* off,
-                                 double* out) {
-    const int g = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (g >= ngen) return;
-    double* o = out + (size_t)off[g] * A.RS;
-    for (unsigned k = k0[g]; k < k1[g]; ++k) {
-        const double* rec = rec_ptr(A, slot[g], k);
-        for (int j = 0; j < A.RS; ++j) *o++ = rec[j];
-    }
-}
-
-// pieces of the records gathered by k_gather_records (structured models): entry i copies np[i] pieces of slot[i] from pstart[i]
-__global__ void k_gather_pieces(KArgs A, int nrec, const int* slot, const unsigned* pstart, const unsigned* np, const long long* off,
-                                double* out) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= nrec) return;
-    double* o = out + (size_t)off[i] * 3;
-    for (unsigned j = 0; j < np[i]; ++j) {
-        const double* q = A.plog + ((size_t)slot[i] * A.pcap + ((pstart[i] + j) % A.pcap)) * 3;
-        *o++ = q[0]; *o++ = q[1]; *o++ = q[2];
-    }
-}
-
-int64_t pf_sample_tree_events(pf_handle* h, int32_t* kind, double* pos, double* height, uint32_t* desc, int64_t max_events,
-                              int64_t* particle_out) {
-    return pf_sample_tree_events_pops(h, kind, pos, height, desc, nullptr, nullptr, max_events, particle_out);
-}
-
-int64_t pf_sample_tree_events_pops(pf_handle* h, int32_t* kind, double* pos, double* height, uint32_t* desc, int32_t* from_pop,
-                                   int32_t* to_pop, int64_t max_events, int64_t* particle_out) {
-    if (!h->A.rec_trees) { g_err = "pf_sample_tree_events: the handle was not created with tree recording (pf_params.flags bit 1)"; return -1; }
-    if (pf_sync(h)) return -1;
-    Ctrl c;
-    HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-    const long long Np = h->Np;
-    // the one-particle systematic draw of resample(..., NULL, 1): the particle whose cumulative pilot weight
-    // (pilotWeight(), pc.cpp:256-262) passes U * total
-    std::vector<double> w(Np);
-    HIPCHK(hipMemcpy(w.data(), state_slot(h->A, c.cur).w_pilot, Np * 8, hipMemcpyDeviceToHost));
-    double total = 0.0;
-    for (double v : w) total += v;
-    const double u = philox_uniform_host((unsigned long long)h->A.seed, 0xFFFFFFFFu, 1, (unsigned long long)c.n_resample);
-    long long j = 0;
-    double acc = 0.0;
-    for (; j < Np - 1; ++j) { acc += w[j]; if (acc > u * total) break; }
-    if (particle_out) *particle_out = j;
-    const int G = c.gen;
-    int* dslot; unsigned *dk0, *dk1; long long* doff;
-    HIPCHK(hipMalloc(&dslot, (size_t)(G + 1) * 4)); HIPCHK(hipMalloc(&dk0, (size_t)(G + 1) * 4)); HIPCHK(hipMalloc(&dk1, (size_t)(G + 1) * 4));
-    HIPCHK(hipMalloc(&doff, (size_t)(G + 1) * 8));
-    hipLaunchKernelGGL(k_trace_ancestry, dim3(1), dim3(1), 0, h->stream, h->A, G, (int)j, dslot, dk0, dk1);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::vector<unsigned> k0(G + 1), k1(G + 1);
-    HIPCHK(hipMemcpy(k0.data(), dk0, (size_t)(G + 1) * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(k1.data(), dk1, (size_t)(G + 1) * 4, hipMemcpyDeviceToHost));
-    std::vector<long long> off(G + 1);
-    long long nrec = 0;
-    for (int g = 0; g <= G; ++g) { off[g] = nrec; nrec += (long long)(k1[g] - k0[g]); }
-    HIPCHK(hipMemcpy(doff, off.data(), (size_t)(G + 1) * 8, hipMemcpyHostToDevice));
-    const int RS = h->A.RS;
-    double* drec;
-    HIPCHK(hipMalloc(&drec, std::max<size_t>(1, (size_t)nrec * RS) * 8));
-    hipLaunchKernelGGL(k_gather_records, dim3((unsigned)((G + 1 + 255) / 256)), dim3(256), 0, h->stream, h->A, G + 1, dslot, dk0, dk1, doff, drec);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::vector<double> rec((size_t)nrec * RS);
-    if (nrec) HIPCHK(hipMemcpy(rec.data(), drec, rec.size() * 8, hipMemcpyDeviceToHost));
-    // structured models: the migrations and the coalescence of an update are in its pieces (pf_mp.h PLog)
-    std::vector<double> pieces;
-    std::vector<long long> poff((size_t)nrec + 1, 0);
-    if (h->P > 1 && nrec) {
-        std::vector<int> gslot(G + 1);
-        HIPCHK(hipMemcpy(gslot.data(), dslot, (size_t)(G + 1) * 4, hipMemcpyDeviceToHost));
-        std::vector<int> rslot((size_t)nrec);
-        std::vector<unsigned> rstart((size_t)nrec), rnp((size_t)nrec);
-        for (int g = 0; g <= G; ++g)
-            for (long long r = off[g]; r < off[g] + (long long)(k1[g] - k0[g]); ++r) rslot[(size_t)r] = gslot[g];
-        for (long long r = 0; r < nrec; ++r) {
-            const double* q = &rec[(size_t)r * RS];
-            unsigned long long meta, ref;
-            memcpy(&meta, &q[4], 8);
-            memcpy(&ref, &q[3], 8);
-            const int type = (int)(meta & 0xff);
-            const bool has = type == 0 || type == 2;
-            rstart[(size_t)r] = has ? (unsigned)(ref & 0xffffffffu) : 0u;
-            rnp[(size_t)r] = has ? (unsigned)(ref >> 32) : 0u;
-            poff[(size_t)r + 1] = poff[(size_t)r] + rnp[(size_t)r];
-        }
-        const long long npieces = poff[(size_t)nrec];
-        int* d_s; unsigned *d_p0, *d_np; long long* d_off; double* d_out;
-        HIPCHK(hipMalloc(&d_s, (size_t)nrec * 4)); HIPCHK(hipMalloc(&d_p0, (size_t)nrec * 4)); HIPCHK(hipMalloc(&d_np, (size_t)nrec * 4));
-        HIPCHK(hipMalloc(&d_off, (size_t)nrec * 8)); HIPCHK(hipMalloc(&d_out, std::max<size_t>(1, (size_t)npieces * 3) * 8));
-        HIPCHK(hipMemcpy(d_s, rslot.data(), (size_t)nrec * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_p0, rstart.data(), (size_t)nrec * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_np, rnp.data(), (size_t)nrec * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_off, poff.data(), (size_t)nrec * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_gather_pieces, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, h->stream, h->A, (int)nrec, d_s, d_p0, d_np, d_off, d_out);
-        HIPCHK(hipStreamSynchronize(h->stream));
-        pieces.resize((size_t)npieces * 3);
-        if (npieces) HIPCHK(hipMemcpy(pieces.data(), d_out, pieces.size() * 8, hipMemcpyDeviceToHost));
-        hipFree(d_s); hipFree(d_p0); hipFree(d_np); hipFree(d_off); hipFree(d_out);
-    }
-    hipFree(dslot); hipFree(dk0); hipFree(dk1); hipFree(doff); hipFree(drec);
-    // last position first; within an update the R line precedes the C line, which precedes the M lines of the walk that
-    // led to it, latest first (the reference prepends every event to one list and prints from its head, pc.cpp:527-551)
-    int64_t nout = 0;
-    auto emit = [&](int kd, double x, double t, unsigned d, int from, int to) {
-        if (nout < max_events) {
-            if (kind) kind[nout] = kd;
-            if (pos) pos[nout] = x;
-            if (height) height[nout] = t;
-            if (desc) desc[nout] = d;
-            if (from_pop) from_pop[nout] = from;
-            if (to_pop) to_pop[nout] = to;
-        }
-        ++nout;
-    };
-    const unsigned full = (1u << h->n) - 1u;
-    for (long long r = nrec - 1; r >= 0; --r) {
-        const double* q = &rec[(size_t)r * RS];
-        unsigned long long meta;
-        memcpy(&meta, &q[4], 8);
-        const int type = (int)(meta & 0xff);
-        if (type != 0 && type != 2) continue;
-        const unsigned cut = (unsigned)((meta >> 32) & 0xffff), below = (unsigned)((meta >> 48) & 0xffff);
-        if (type == 0) emit(0, q[1], q[2], cut, -1, -1);
-        if (h->P == 1) { emit(1, q[1], q[3], below, 0, -1); continue; }
-        // the floating lineage is the cut branch (an update) or leaf i on its way into the partial tree (initial tree:
-        // n_eff = i); the other active lineage is the root's own, above everything that is not the floating lineage
-        const int leaf = (int)((meta >> 24) & 0xff);
-        const unsigned fl = type == 0 ? cut : (1u << leaf);
-        const unsigned rt = type == 0 ? (full & ~cut) : ((1u << leaf) - 1u);
-        for (long long j = poff[(size_t)r + 1] - 1; j >= poff[(size_t)r]; --j) {
-            long long tag;
-            memcpy(&tag, &pieces[(size_t)j * 3], 8);
-            const int pop = (int)(tag & 0xff), kd = (int)((tag >> 8) & 0xff), to = (int)((tag >> 16) & 0xff);
-            const double t1 = pieces[(size_t)j * 3 + 2];
-            if (kd & 1) emit(1, q[1], t1, below, pop, -1);
-            if (kd & 2) emit(2, q[1], t1, (kd & 4) ? rt : fl, pop, to);
-        }
-    }
-    return nout;
-}
-
-int pf_set_timing(pf_handle* h, int period) {
-    h->timing_period = period;
-    if (period > 0 && h->span_overhead_ms == 0) {
-        // A span is two event records around one launch; what the pair measures with nothing in between is not kernel
-        // time.  Median of 64 empty spans, subtracted from every span, so that the per-launch figure agrees with the
-        // kernel durations a profiler reports.
-        HIPCHK(hipSetDevice(h->device));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        std::vector<float> empty;
-        for (int i = 0; i < 64; ++i) {
-            hipEvent_t a = get_event(h), b = get_event(h);
-            hipEventRecord(a, h->stream); hipEventRecord(b, h->stream);
-            HIPCHK(hipEventSynchronize(b));
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, a, b));
-            empty.push_back(ms);
-            h->ev_pool.push_back(a); h->ev_pool.push_back(b);
-        }
-        std::sort(empty.begin(), empty.end());
-        h->span_overhead_ms = empty[empty.size() / 2];
-    }
-    return 0;
-}
-
-// profiling builds (-DPF_STAMPS): wall-clock stamps (100 MHz) of the phases of the extend workgroups, one set per row and
-// wavefront; a regular build records nothing
-int pf_test_search_lut(const double* tab, int32_t n, uint8_t* lut, int32_t* kbase) {
-    int kb = 0;
-    if (n < 1 || n > PF_EMAX || !lut_build(tab, n, lut, &kb)) return 0;
-    *kbase = kb;
-    return 1;
-}
-
-int pf_debug_stamps(pf_handle* h, int64_t rows, uint64_t* out) {
-    HIPCHK(hipSetDevice(h->device));
-    if (rows > 0 && !out) {
-        unsigned long long* buf = nullptr;
-        if (dalloc(h, &buf, (size_t)rows * h->A.nc * PF_STAMP_W)) return -1;
-        HIPCHK(hipMemset(buf, 0, (size_t)rows * h->A.nc * PF_STAMP_W * 8));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->A.stamps = buf; h->A.stamp_rows = rows;
-        return 0;
-    }
-    if (!h->A.stamps) { g_err = "pf_debug_stamps: not enabled"; return -1; }
-    if (pf_sync(h)) return -1;
-    HIPCHK(hipMemcpy(out, h->A.stamps, (size_t)std::min<long long>(rows, h->A.stamp_rows) * h->A.nc * PF_STAMP_W * 8, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int pf_get_kernel_time(pf_handle* h, int k, double* ms, int64_t* launches) {
-    if (k < 0 || k > 3) return -1;
-    if (pf_sync(h)) return -1;
-    // mean duration of the timed launches, scaled to all launches of this class
-    double mean = h->k_timed[k] ? h->k_ms[k] / (double)h->k_timed[k] : 0.0;
-    if (ms) *ms = mean * (double)h->k_launches[k];
-    if (launches) *launches = h->k_launches[k];
-    return 0;
-}
-
-// Measurement aid: steps [first_step, first_step + n_steps) of the next pf_run / pf_run_many calls led by this handle run the traced
-// instance of the row kernel (k_sweep4t: at most four haplotypes, no focused sampling; other shapes ignore the request).
-int pf_set_wg_trace(pf_handle* h, int64_t first_step, int32_t n_steps) {
-    HIPCHK(hipSetDevice(h->device));
-    if (pf_sync(h)) return -1;
-    if (h->d_trace) { hipFree(h->d_trace); h->d_trace = nullptr; }
-    h->trace_t0 = (int)std::max<int64_t>(0, first_step);
-    h->trace_n = std::max(0, n_steps);
-    h->trace_stride = 0; h->trace_words = 0;
-    return 0;
-}
-
-// The trace: four 64-bit words per workgroup slot of every traced step -- start and end (100 MHz clock; 0 0: slot not used by that step's
-// grid), HW_ID | XCC_ID << 32, index within the chunk | chunk << 32.  Returns the number of words (0: nothing traced yet); copies at most
-// cap_words of them; info = {steps, workgroup slots per step}.
-int64_t pf_get_wg_trace(pf_handle* h, uint64_t* out, int64_t cap_words, int32_t* info) {
-    if (hipSetDevice(h->device) != hipSuccess || pf_sync(h)) return -1;
-    if (info) { info[0] = h->d_trace ? h->trace_n : 0; info[1] = h->trace_stride; }
-    if (!h->d_trace) return 0;
-    const size_t nw = std::min<size_t>(h->trace_words, (size_t)std::max<int64_t>(0, cap_words));
-    if (out && nw && hipMemcpy(out, h->d_trace, nw * 8, hipMemcpyDeviceToHost) != hipSuccess) { g_err = "copy of the workgroup trace failed"; return -1; }
-    return (int64_t)h->trace_words;
-}
-
-int pf_get_delay_stats(pf_handle* h, int64_t* n_forced, int32_t* peak_pending) {
-    if (pf_sync(h)) return -1;
-    Ctrl c;
-    HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-    if (n_forced) *n_forced = (int64_t)c.n_delay_evict;
-    if (peak_pending) *peak_pending = c.delay_peak;
-    return 0;
-}
-
-int pf_get_stats(pf_handle* h, int64_t* n_records, int64_t* state_bytes, int64_t* n_resamples) {
-    if (pf_sync(h)) return -1;
-    if (n_records) {
-        std::vector<unsigned> w(h->Np);
-        HIPCHK(hipMemcpy(w.data(), h->A.widx, h->Np * 4, hipMemcpyDeviceToHost));
-        long long t = 0;
-        for (unsigned v : w) t += v;
-        *n_records = t;
-    }
-    if (state_bytes) *state_bytes = (int64_t)(h->n - 1) * 8 + 2 * (h->n - 1) + 5 * 8 + 4 + 8 + 8 + 4;
-    if (n_resamples) {
-        Ctrl c;
-        HIPCHK(hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost));
-        *n_resamples = c.n_resample;
-    }
-    return 0;
-}
-
-// ------------------------------------------------------------------ unit-level test entry points
-static int test_setup(int device) {
-    if (pf_device_count() <= 0) { g_err = "no HIP device"; return -1; }
-    HIPCHK(hipSetDevice(device));
-    return 0;
-}
-
-int pf_test_math(const double* x, int64_t n, double* oe, double* ol, double* of, int device) {
-    if (test_setup(device)) return -1;
-    double *dx, *de, *dl, *df;
-    HIPCHK(hipMalloc(&dx, n * 8)); HIPCHK(hipMalloc(&de, n * 8)); HIPCHK(hipMalloc(&dl, n * 8)); HIPCHK(hipMalloc(&df, n * 8));
-    HIPCHK(hipMemcpy(dx, x, n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_test_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, (long long)n, de, dl, df);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(oe, de, n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ol, dl, n * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(of, df, n * 8, hipMemcpyDeviceToHost));
-    hipFree(dx); hipFree(de); hipFree(dl); hipFree(df);
-    return 0;
-}
-
-int pf_test_div(const double* a, const double* b, int64_t n, double* out, int device) {
-    if (test_setup(device)) return -1;
-    double *da, *db, *dout;
-    HIPCHK(hipMalloc(&da, n * 8)); HIPCHK(hipMalloc(&db, n * 8)); HIPCHK(hipMalloc(&dout, n * 8));
-    HIPCHK(hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_test_div, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, da, db, (long long)n, dout);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
-    hipFree(da); hipFree(db); hipFree(dout);
-    return 0;
-}
-
-int pf_test_uniform(uint64_t seed, uint32_t slot, uint32_t stream, uint64_t first_draw, int64_t n, double* out, int device) {
-    if (test_setup(device)) return -1;
-    double* d;
-    HIPCHK(hipMalloc(&d, n * 8));
-    hipLaunchKernelGGL(k_test_uniform, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (unsigned long long)seed, slot, stream,
-                       (unsigned long long)first_draw, (long long)n, d);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, d, n * 8, hipMemcpyDeviceToHost));
-    hipFree(d);
-    return 0;
-}
-
-// canonical sum / scan / systematic table through the production kernels (k_partials + k_decide)
-static int test_reduce_impl(const double* x, int64_t n, double* out_sum, double* out_scan, double u, int32_t* lo, int device) {
-    if (test_setup(device)) return -1;
-    pf_model m;
-    memset(&m, 0, sizeof(m));
-    double ct = 0.0, ps = 1e4, lag = 1e30;
-    int rf = 3;
-    m.n_epochs = 1; m.n_pops = 1; m.nsam = 2; m.loci_length = 1e6; m.mutation_rate = 1e-8; m.recombination_rate = 1e-8;
-    m.change_times = &ct; m.pop_sizes = &ps; m.record_flags = &rf; m.lags = &lag;
-    pf_params p;
-    memset(&p, 0, sizeof(p));
-    p.np = n; p.ess_fraction = lo ? 2.0 : 0.0; p.seed = 1; p.max_trace_events = 0;   // ESS < 2N always -> forces the table
-    pf_handle* h = create_impl(&m, &p, device, 8, 4);
-    if (!h) return -1;
-    int rc = 0;
-    double s0 = 0.0, l0 = 1.0; int8_t st0 = 1; int8_t al[2] = {-1, -1}; int lim0 = 0;
-    pf_segments sg = {1, &s0, &l0, &st0, al, &lim0};
-    rc |= pf_load_segments(h, &sg);
-    rc |= pf_init_prior(h, 0.0);
-    if (!rc) {
-        hipMemcpyAsync(h->A.st0.w_post, x, n * 8, hipMemcpyHostToDevice, h->stream);
-        hipMemcpyAsync(h->A.st0.w_pilot, x, n * 8, hipMemcpyHostToDevice, h->stream);
-        hipLaunchKernelGGL(k_partials, dim3(h->nblocks), dim3(PF_BS), 0, h->stream, h->A);
-        // override u by running k_decide in mode 0 and then patching: simpler -- write u after the fact
-        hipLaunchKernelGGL(k_decide, dim3(h->nblocks + 1), dim3(PF_BS), 0, h->stream, h->A, (long long)0, lo ? 0 : 1, no_windows(h), h->nblocks);
-        hipStreamSynchronize(h->stream);
-        Ctrl c;
-        hipMemcpy(&c, h->A.ctrl, sizeof(Ctrl), hipMemcpyDeviceToHost);
-        if (out_sum) *out_sum = c.T;
-        if (out_scan) {
-            std::vector<double> s1(n), off((n + 63) / 64);
-            hipMemcpy(s1.data(), h->A.scan1, n * 8, hipMemcpyDeviceToHost);
-            hipMemcpy(off.data(), h->A.chunk_off, off.size() * 8, hipMemcpyDeviceToHost);
-            for (int64_t i = 0; i < n; ++i) out_scan[i] = off[i >> 6] + s1[i];
-        }
-        if (lo) {
-            (void)u;
-            hipMemcpy(lo, h->A.lo, (n + 1) * 4, hipMemcpyDeviceToHost);
-        }
-    }
-    pf_destroy(h);
-    return rc ? -1 : 0;
-}
-
-int pf_test_reduce(const double* x, int64_t n, double* out_sum, double* out_incl_scan, int device) {
-    return test_reduce_impl(x, n, out_sum, out_incl_scan, 0.0, nullptr, device);
-}
-
-int pf_test_systematic(const double* pilot, int64_t n, double u, int32_t* lo, int device) {
-    // the production kernel draws u from the resampler stream (seed 1, event 0); the caller
-    // obtains the same u through pf_test_uniform(1, 0xFFFFFFFF, 1, 0, ...)
-    return test_reduce_impl(pilot, n, nullptr, nullptr, u, lo, device);
-}
-
-int pf_load_lookahead(pf_handle* h, const pf_lookahead* la) {
-    HIPCHK(hipSetDevice(h->device));
-    if (la->level < 0 || la->level > 4) { g_err = "-apf must be in 0..4"; return -1; }
-    if (la->n != h->n_segs) { g_err = "pf_load_lookahead: one look-ahead record per segment expected"; return -1; }
-    if (la->level == 0) { h->A.apf = 0; return 0; }
-    if (h->wide) { g_err = "-apf (the auxiliary particle filter) needs nsam <= 16"; return -1; }
-    const long long S = la->n;
-    const int n = h->n, D = la->max_doubletons, Q = la->n_quantiles;
-    KArgs& A = h->A;
-    double *fsd, *rmr, *ddist, *split, *q, *tbl; int8_t *unph, *didx, *sal; int *nd, *sk;
-    int rc = 0;
-    rc |= dalloc(h, &fsd, (size_t)S * n); rc |= dalloc(h, &rmr, (size_t)S * n); rc |= dalloc(h, &unph, (size_t)S * n);
-    rc |= dalloc(h, &nd, S); rc |= dalloc(h, &didx, (size_t)S * D * 4); rc |= dalloc(h, &ddist, (size_t)S * D * 2);
-    rc |= dalloc(h, &split, S); rc |= dalloc(h, &sal, (size_t)S * n); rc |= dalloc(h, &sk, S);
-    rc |= dalloc(h, &q, Q); rc |= dalloc(h, &tbl, (size_t)n * Q);
-    if (!A.st0.lookahead) rc |= dalloc(h, &A.st0.lookahead, (size_t)A.nslots * h->Np);
-    if (rc) return -1;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(fsd, la->first_singleton_distance, (size_t)S * n * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(rmr, la->relative_mutation_rate, (size_t)S * n * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(unph, la->is_singleton_unphased, (size_t)S * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(nd, la->n_doubletons, (size_t)S * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(didx, la->doubleton_idx, (size_t)S * D * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(ddist, la->doubleton_dist, (size_t)S * D * 2 * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(split, la->first_split_distance, (size_t)S * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(sal, la->split_alleles, (size_t)S * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(sk, la->split_count, (size_t)S * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(q, la->quantiles, (size_t)Q * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(tbl, la->tbl_lengths, (size_t)n * Q * 8, hipMemcpyHostToDevice));
-    std::vector<double> ones((size_t)A.nslots * h->Np, 1.0);
-    HIPCHK(hipMemcpy(A.st0.lookahead, ones.data(), ones.size() * 8, hipMemcpyHostToDevice));
-    A.apf = la->level; A.la_D = D; A.la_Q = Q;
-    A.la_fsd = fsd; A.la_rmr = rmr; A.la_unph = unph; A.la_nd = nd; A.la_didx = didx; A.la_ddist = ddist;
-    A.la_split = split; A.la_salleles = sal; A.la_sk = sk; A.la_q = q; A.la_tbl = tbl;
-    A.la_mean_tbl = la->mean_total_branch_length;
-    h->smem_la = smem_bytes_la(n, h->E);
-    if (h->smem_la > 64 * 1024) hipFuncSetAttribute((const void*)k_lookahead, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_la);
-    return 0;
-}
-
-int pf_terminal_branch_quantiles(const pf_model* m, uint64_t seed, int64_t n_trees, const double* quantiles, int32_t nq,
-                                 double* lengths_out, double* mean_total_out, int device) {
-    if (test_setup(device)) return -1;
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX || n_trees < 1) {
-        g_err = "pf_terminal_branch_quantiles: unsupported model";
-        return -1;
-    }
-    const int E = m->n_epochs, n = m->nsam, P = m->n_pops;
-    KArgs A;
-    memset(&A, 0, sizeof(A));
-    A.E = E; A.n = n; A.P = P; A.L = m->loci_length; A.mu = m->mutation_rate; A.rho = m->recombination_rate; A.mcap = PF_MMAX;
-    double *dT, *dI, *dh, *dl; int *dRF, *derr;
-    std::vector<void*> mp_allocs;
-    HIPCHK(hipMalloc(&dT, E * 8)); HIPCHK(hipMalloc(&dI, E * 8)); HIPCHK(hipMalloc(&dRF, E * 4)); HIPCHK(hipMalloc(&derr, 4));
-    HIPCHK(hipMemset(derr, 0, 4));
-    HIPCHK(hipMalloc(&dh, (size_t)n * n_trees * 8)); HIPCHK(hipMalloc(&dl, (size_t)n_trees * 8));
-    std::vector<double> inv2N(E);
-    for (int e = 0; e < E; ++e) inv2N[e] = 1.0 / (2.0 * m->pop_sizes[(size_t)e * P]);
-    std::vector<int> rf(E, 3);
-    HIPCHK(hipMemcpy(dT, m->change_times, E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dI, inv2N.data(), E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dRF, rf.data(), E * 4, hipMemcpyHostToDevice));
-    double* dHc;
-    HIPCHK(hipMalloc(&dHc, E * 8));
-    {
-        const std::vector<double> Hc = cumulative_intensity(m->change_times, inv2N, E);
-        HIPCHK(hipMemcpy(dHc, Hc.data(), E * 8, hipMemcpyHostToDevice));
-    }
-    A.T = dT; A.inv2N = dI; A.Hc = dHc; A.recflags = dRF;
-    int tbl_err = 0;
-    if (P > 1) {
-        MpTables tb;
-        if (build_mp_tables(m, tb) || upload_mp_tables(tb, A, mp_allocs)) return -1;
-        const size_t smem = pf_mp_smem_bytes(n, E, P, PF_MMAX);
-        if (pf_mp_prepare(smem, PF_MMAX)) { g_err = "pf_terminal_branch_quantiles: the local-tree state does not fit the LDS"; return -1; }
-        pf_mp_launch_tbl(A, (unsigned long long)seed, (long long)n_trees, dh, dl, derr, smem, 0);
-    } else {
-        const size_t smem = smem_bytes(n, E);
-        if (smem > 64 * 1024) hipFuncSetAttribute((const void*)k_tbl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k_tbl, dim3((unsigned)((n_trees + PF_BS - 1) / PF_BS)), dim3(PF_BS), smem, 0, A, (unsigned long long)seed,
-                           (long long)0, (long long)n_trees, dh, dl);
-    }
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(&tbl_err, derr, 4, hipMemcpyDeviceToHost));
-    std::vector<double> hh((size_t)n * n_trees), ll(n_trees);
-    HIPCHK(hipMemcpy(hh.data(), dh, hh.size() * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(ll.data(), dl, ll.size() * 8, hipMemcpyDeviceToHost));
-    hipFree(dT); hipFree(dI); hipFree(dHc); hipFree(dRF); hipFree(dh); hipFree(dl); hipFree(derr);
-    for (void* q : mp_allocs) hipFree(q);
-    if (tbl_err) {
-        g_err = tbl_err == 1 ? "too many migration events on one local tree" : "No final coalescence event was sampled!";
-        return -1;
-    }
-    for (int i = 0; i < n; ++i) {
-        double* row = hh.data() + (size_t)i * n_trees;
-        std::sort(row, row + n_trees);
-        for (int q = 0; q < nq; ++q) lengths_out[i * nq + q] = row[(long long)(quantiles[q] * (double)n_trees)];
-    }
-    double total = 0.0;
-    for (long long r = 0; r < n_trees; ++r) total += ll[r];      // serial, in tree order (smcsmc.cpp:145)
-    *mean_total_out = total / (double)n_trees;
-    return 0;
-}
-
-// ------------------------------------------------------------------ lag calibration (host driver)
-// calculate_median_survival_distances (smcsmc.cpp:169-263).  The reference grows its sample one
-// tree at a time with a shared RNG; here trees are simulated in fixed batches of PF_CAL_BATCH
-// independent Philox streams until every epoch has min_events samples (or max_trees is reached),
-// then the same median / fallback rules are applied (smcsmc.cpp:235-262).
-#define PF_CAL_BATCH 16384
-
-static int median_survival_impl(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
-                                int64_t* trees_used, int32_t debug, int device) {
-    if (test_setup(device)) return -1;
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > (m->n_pops == 1 ? PF_NMAX_WIDE : PF_NMAX) || m->n_epochs < 1 ||
-        m->n_epochs > PF_EMAX) {
-        g_err = "pf_median_survival: unsupported model (nsam 2..64 with one population, 2..16 with several)";
-        return -1;
-    }
-    // one population beyond 16 haplotypes (or PF_DEBUG_FORCE_WIDE): the wide kernel, same trees and walk
-    const bool wide = m->n_pops == 1 && (m->nsam > PF_NMAX || (debug & PF_DEBUG_FORCE_WIDE));
-    const int E = m->n_epochs, n = m->nsam, P = m->n_pops;
-    KArgs A;
-    memset(&A, 0, sizeof(A));
-    A.E = E; A.n = n; A.P = P; A.L = m->loci_length; A.mu = m->mutation_rate; A.rho = m->recombination_rate; A.mcap = PF_MMAX;
-    double *dT, *dI; int *dRF, *dep, *derr; double* ddist;
-    std::vector<void*> mp_allocs;
-    HIPCHK(hipMalloc(&dT, E * 8)); HIPCHK(hipMalloc(&dI, E * 8)); HIPCHK(hipMalloc(&dRF, E * 4)); HIPCHK(hipMalloc(&derr, 4));
-    HIPCHK(hipMemset(derr, 0, 4));
-    // The stopping rule is evaluated batch by batch (D8), but PF_CAL_GROUP batches are simulated per launch: a batch of
-    // 16 384 trees fills a quarter of the SIMDs and takes as long as four.  Batches behind the one at which the rule
-    // fires are discarded, so the result is that of one launch per batch.
-    constexpr int PF_CAL_GROUP = 4;
-    const size_t per_batch = (size_t)PF_CAL_BATCH * (n - 1);
-    HIPCHK(hipMalloc(&dep, PF_CAL_GROUP * per_batch * 4)); HIPCHK(hipMalloc(&ddist, PF_CAL_GROUP * per_batch * 8));
-    std::vector<double> inv2N(E);
-    for (int e = 0; e < E; ++e) inv2N[e] = 1.0 / (2.0 * m->pop_sizes[(size_t)e * P]);
-    std::vector<int> rf(E, 3);
-    HIPCHK(hipMemcpy(dT, m->change_times, E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dI, inv2N.data(), E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dRF, rf.data(), E * 4, hipMemcpyHostToDevice));
-    double* dHc;
-    HIPCHK(hipMalloc(&dHc, E * 8));
-    {
-        const std::vector<double> Hc = cumulative_intensity(m->change_times, inv2N, E);
-        HIPCHK(hipMemcpy(dHc, Hc.data(), E * 8, hipMemcpyHostToDevice));
-    }
-    A.T = dT; A.inv2N = dI; A.Hc = dHc; A.recflags = dRF;
-    if (P > 1) {
-        MpTables tb;
-        if (build_mp_tables(m, tb) || upload_mp_tables(tb, A, mp_allocs)) return -1;
-    }
-    std::vector<std::vector<double>> surv(E);
-    std::vector<int> hep(PF_CAL_GROUP * per_batch);
-    std::vector<double> hdist(PF_CAL_GROUP * per_batch);
-    long long trees = 0;
-    const size_t smem = P > 1 ? pf_mp_smem_bytes(n, E, P, PF_MMAX) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
-    if (P > 1 && pf_mp_prepare(smem, PF_MMAX)) { g_err = "pf_median_survival: the local-tree state does not fit the LDS"; return -1; }
-    if (wide && pf_wide_prepare(smem)) { g_err = "pf_median_survival: the local-tree state does not fit the LDS"; return -1; }
-    const size_t smem_cal = smem + (size_t)(2 * PF_EPAD + E) * 8;          // + the padded epoch tables of the register path
-    if (P == 1 && !wide && smem_cal > 64 * 1024) {
-        hipFuncSetAttribute((const void*)k_calibrate<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_cal);
-        hipFuncSetAttribute((const void*)k_calibrate<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_cal);
-        hipFuncSetAttribute((const void*)k_calibrate<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_cal);
-    }
-    int cal_err = 0;
-    auto finished = [&]() {
-        int not_done = 0;
-        for (int e = 0; e < E; ++e) not_done += (int)surv[e].size() < min_events;
-        return not_done == 0 || trees >= max_trees;
-    };
-    while (!finished()) {
-        const long long nrep = (long long)PF_CAL_GROUP * PF_CAL_BATCH;
-        if (P > 1)
-            pf_mp_launch_calibrate(A, (unsigned long long)seed, trees, nrep, dep, ddist, derr, smem, 0);
-        else if (wide)
-            pf_wide_launch_calibrate(A, (unsigned long long)seed, trees, nrep, dep, ddist, smem, 0);
-        else
-        {
-            const dim3 grid((unsigned)(nrep / PF_BS)), blk(PF_BS);
-            if (n <= 4) hipLaunchKernelGGL(k_calibrate<4>, grid, blk, smem_cal, 0, A, (unsigned long long)seed, trees, nrep, dep, ddist);
-            else if (n <= 8) hipLaunchKernelGGL(k_calibrate<8>, grid, blk, smem_cal, 0, A, (unsigned long long)seed, trees, nrep, dep, ddist);
-            else hipLaunchKernelGGL(k_calibrate<0>, grid, blk, smem_cal, 0, A, (unsigned long long)seed, trees, nrep, dep, ddist);
-        }
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipMemcpy(&cal_err, derr, 4, hipMemcpyDeviceToHost));
-        if (cal_err) break;
-        HIPCHK(hipMemcpy(hep.data(), dep, hep.size() * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(hdist.data(), ddist, hdist.size() * 8, hipMemcpyDeviceToHost));
-        for (int b = 0; b < PF_CAL_GROUP && !finished(); ++b) {
-            for (size_t i = b * per_batch; i < (b + 1) * per_batch; ++i)
-                if (hdist[i] >= 0) surv[hep[i]].push_back(hdist[i]);
-            trees += PF_CAL_BATCH;
-        }
-    }
-    hipFree(dT); hipFree(dI); hipFree(dHc); hipFree(dRF); hipFree(dep); hipFree(ddist); hipFree(derr);
-    for (void* q : mp_allocs) hipFree(q);
-    if (cal_err) {
-        g_err = cal_err == 1 ? "too many migration events on one local tree"
-              : cal_err == 3 ? "No final coalescence event was sampled!" : "structured-model genealogy update failed";
-        return -1;
-    }
-    if (trees_used) *trees_used = trees;
-    // smcsmc.cpp:235-262
-    double earliest = -1;
-    for (int e = 0; e < E; ++e) {
-        std::sort(surv[e].begin(), surv[e].end());
-        int median_idx = ((int)surv[e].size() - 1) / 2;
-        if (median_idx < 10) median_out[e] = -1;
-        else {
-            median_out[e] = surv[e][median_idx];
-            if (earliest < 0) earliest = median_out[e];
-        }
-    }
-    for (int e = 0; e < E; ++e)
-        if (median_out[e] < 0) median_out[e] = e > 0 ? median_out[e - 1] : earliest;
-    return 0;
-}
-
-int pf_median_survival(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
-                       int64_t* trees_used, int device) {
-    return median_survival_impl(m, seed, min_events, max_trees, median_out, trees_used, 0, device);
-}
-
-int pf_median_survival_opts(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
-                            int64_t* trees_used, int32_t debug, int device) {
-    return median_survival_impl(m, seed, min_events, max_trees, median_out, trees_used, debug, device);
-}
-
-// One population, 2..64 haplotypes, 64-bit carrier masks: the wide kernel (k_simulate_wide, the body of k_simulate).
-int pf_simulate_sites_wide(const pf_model* m, uint64_t seed, int32_t nchunks, int64_t max_sites, double* pos, uint64_t* masks,
-                        int64_t* n_sites, int device) {
-    if (test_setup(device)) return -1;
-    if (m->n_pops != 1 || m->nsam < 2 || m->nsam > PF_NMAX_WIDE || m->n_epochs < 1 || m->n_epochs > PF_EMAX || nchunks < 1 || max_sites < 1) {
-        g_err = "pf_simulate_sites_wide: one population, 2..64 haplotypes, 1..64 epochs";
-        return -1;
-    }
-    const int E = m->n_epochs, n = m->nsam;
-    KArgs A;
-    memset(&A, 0, sizeof(A));
-    A.E = E; A.n = n; A.P = 1; A.L = m->loci_length; A.mu = m->mutation_rate; A.rho = m->recombination_rate; A.mcap = PF_MMAX;
-    struct Bufs { std::vector<void*> v; ~Bufs() { for (void* q : v) hipFree(q); } } bufs;
-    auto dmalloc = [&](auto** q, size_t bytes) { void* r = nullptr; hipError_t e = hipMalloc(&r, bytes); if (e == hipSuccess) bufs.v.push_back(r); *q = (std::remove_reference_t<decltype(**q)>*)r; return e; };
-    double *dT, *dI, *dHc, *dpos; int* dRF; unsigned long long* dmask; long long* dn;
-    HIPCHK(dmalloc(&dT, E * 8)); HIPCHK(dmalloc(&dI, E * 8)); HIPCHK(dmalloc(&dHc, E * 8)); HIPCHK(dmalloc(&dRF, E * 4));
-    HIPCHK(dmalloc(&dpos, (size_t)nchunks * max_sites * 8)); HIPCHK(dmalloc(&dmask, (size_t)nchunks * max_sites * 8));
-    HIPCHK(dmalloc(&dn, (size_t)nchunks * 8));
-    std::vector<double> inv2N(E);
-    for (int e = 0; e < E; ++e) inv2N[e] = 1.0 / (2.0 * m->pop_sizes[e]);
-    std::vector<int> rf(E, 3);
-    const std::vector<double> Hc = cumulative_intensity(m->change_times, inv2N, E);
-    HIPCHK(hipMemcpy(dT, m->change_times, E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dI, inv2N.data(), E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dHc, Hc.data(), E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dRF, rf.data(), E * 4, hipMemcpyHostToDevice));
-    A.T = dT; A.inv2N = dI; A.Hc = dHc; A.recflags = dRF;
-    const size_t smem = pf_wide_smem_bytes(n, E);
-    if (pf_wide_prepare(smem)) { g_err = "pf_simulate_sites_wide: the local-tree state does not fit the LDS"; return -1; }
-    pf_wide_launch_simulate(A, (unsigned long long)seed, (int)nchunks, (long long)max_sites, dpos, dmask, dn, smem, 0);
-    if (check_launch("k_simulate_wide")) return -1;
-    if (hipDeviceSynchronize() != hipSuccess) { g_err = "k_simulate_wide failed"; return -1; }
-    std::vector<long long> hn(nchunks);
-    HIPCHK(hipMemcpy(hn.data(), dn, (size_t)nchunks * 8, hipMemcpyDeviceToHost));
-    for (int c = 0; c < nchunks; ++c) {
-        n_sites[c] = hn[c];
-        const long long k = std::min<long long>(std::llabs(hn[c]), max_sites);
-        HIPCHK(hipMemcpy(pos + (size_t)c * max_sites, dpos + (size_t)c * max_sites, (size_t)k * 8, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(masks + (size_t)c * max_sites, dmask + (size_t)c * max_sites, (size_t)k * 8, hipMemcpyDeviceToHost));
-    }
-    return 0;
-}
-
-// Synthetic data for `nchunks` independent chunks of the model's length (one population): site positions and carrier
-// masks per chunk (k_simulate).  n_sites[c] < 0: more than max_sites sites (the first max_sites are valid).
-int pf_simulate_sites(const pf_model* m, uint64_t seed, int32_t nchunks, int64_t max_sites, double* pos, uint32_t* masks,
-                      int64_t* n_sites, int device) {
-    if (test_setup(device)) return -1;
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX || nchunks < 1 || max_sites < 1) {
-        g_err = "pf_simulate_sites: 1..4 populations, 2..16 haplotypes, 1..64 epochs";
-        return -1;
-    }
-    const int E = m->n_epochs, n = m->nsam, P = m->n_pops;
-    KArgs A;
-    memset(&A, 0, sizeof(A));
-    A.E = E; A.n = n; A.P = P; A.L = m->loci_length; A.mu = m->mutation_rate; A.rho = m->recombination_rate; A.mcap = PF_MMAX;
-    // every exit path frees what was allocated so far
-    struct Bufs { std::vector<void*> v; ~Bufs() { for (void* q : v) hipFree(q); } } bufs;
-    auto dmalloc = [&](auto** q, size_t bytes) { void* r = nullptr; hipError_t e = hipMalloc(&r, bytes); if (e == hipSuccess) bufs.v.push_back(r); *q = (std::remove_reference_t<decltype(**q)>*)r; return e; };
-    double *dT, *dI, *dHc, *dpos; int* dRF; unsigned* dmask; long long* dn;
-    HIPCHK(dmalloc(&dT, E * 8)); HIPCHK(dmalloc(&dI, E * 8)); HIPCHK(dmalloc(&dHc, E * 8)); HIPCHK(dmalloc(&dRF, E * 4));
-    HIPCHK(dmalloc(&dpos, (size_t)nchunks * max_sites * 8)); HIPCHK(dmalloc(&dmask, (size_t)nchunks * max_sites * 4));
-    HIPCHK(dmalloc(&dn, (size_t)nchunks * 8));
-    std::vector<double> inv2N(E);
-    for (int e = 0; e < E; ++e) inv2N[e] = 1.0 / (2.0 * m->pop_sizes[(size_t)e * P]);
-    std::vector<int> rf(E, 3);
-    const std::vector<double> Hc = cumulative_intensity(m->change_times, inv2N, E);
-    HIPCHK(hipMemcpy(dT, m->change_times, E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dI, inv2N.data(), E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dHc, Hc.data(), E * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dRF, rf.data(), E * 4, hipMemcpyHostToDevice));
-    A.T = dT; A.inv2N = dI; A.Hc = dHc; A.recflags = dRF;
-    std::vector<void*> mp_allocs;
-    int* derr = nullptr;
-    int rc = 0;
-    if (P > 1) {
-        // structured model: the LDS-tree walk of pf_mp.h, one lane per chunk
-        MpTables tb;
-        const int up = build_mp_tables(m, tb) || upload_mp_tables(tb, A, mp_allocs);
-        for (void* q : mp_allocs) bufs.v.push_back(q);
-        if (up) return -1;
-        HIPCHK(dmalloc(&derr, 4));
-        HIPCHK(hipMemset(derr, 0, 4));
-        const size_t smem = pf_mp_smem_bytes(n, E, P, PF_MMAX);
-        if (pf_mp_prepare(smem, PF_MMAX)) { g_err = "pf_simulate_sites: the local-tree state does not fit the LDS"; return -1; }
-        pf_mp_launch_simulate(A, (unsigned long long)seed, (int)nchunks, (long long)max_sites, dpos, dmask, dn, derr, smem, 0);
-    } else {
-        const size_t smem = smem_bytes(n, E);
-        if (smem > 64 * 1024) hipFuncSetAttribute((const void*)k_simulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(k_simulate, dim3((unsigned)((nchunks + PF_BS - 1) / PF_BS)), dim3(PF_BS), smem, 0, A, (unsigned long long)seed,
-                           (int)nchunks, (long long)max_sites, dpos, dmask, dn);
-    }
-    rc = check_launch("k_simulate");
-    if (!rc && hipDeviceSynchronize() != hipSuccess) { g_err = "k_simulate failed"; rc = -1; }
-    if (!rc && derr) {
-        int herr = 0;
-        HIPCHK(hipMemcpy(&herr, derr, 4, hipMemcpyDeviceToHost));
-        if (herr) { g_err = herr == 1 ? "too many migration events on one local tree" : (herr == 3 ? "No final coalescence event was sampled!" : "structured simulation: internal error"); rc = -1; }
-    }
-    if (!rc) {
-        std::vector<long long> hn(nchunks);
-        HIPCHK(hipMemcpy(hn.data(), dn, (size_t)nchunks * 8, hipMemcpyDeviceToHost));
-        for (int c = 0; c < nchunks; ++c) {
-            n_sites[c] = hn[c];
-            const long long k = std::min<long long>(std::llabs(hn[c]), max_sites);
-            HIPCHK(hipMemcpy(pos + (size_t)c * max_sites, dpos + (size_t)c * max_sites, (size_t)k * 8, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(masks + (size_t)c * max_sites, dmask + (size_t)c * max_sites, (size_t)k * 4, hipMemcpyDeviceToHost));
-        }
-    }
-    return rc;
-}
+#include "pf_get.h"
+#include "pf_tools.h"

@@ -440,9 +440,10 @@ struct SweepFrame {
     int table(long long s_end, int split) {
         if (h->d_sweep_cap < nh) {
             // one allocation: the row headers of the chunks, chunk 0's last, and behind them the chunk table (sweep_head_of, pf_pipe.h)
-            if (h->d_sweep_base) { if (hipStreamSynchronize(h->stream) != hipSuccess || hipFree(h->d_sweep_base) != hipSuccess) return -1; }
+            if (h->d_sweep_base && hipStreamSynchronize(h->stream) != hipSuccess) return -1;
+            h->sweep_mem.clear();
             h->d_sweep_base = nullptr; h->d_sweep = nullptr; h->d_sweep_cap = 0;
-            if (hipMalloc((void**)&h->d_sweep_base, (sizeof(SweepHead) * PF_RING + sizeof(SweepChunk)) * (size_t)nh) != hipSuccess) {
+            if (h->sweep_mem.reserve(&h->d_sweep_base, (sizeof(SweepHead) * PF_RING + sizeof(SweepChunk)) * (size_t)nh)) {
                 h->d_sweep_base = nullptr; g_err = "hipMalloc of the chunk table failed"; return -1;
             }
             h->d_sweep = (SweepChunk*)(h->d_sweep_base + sizeof(SweepHead) * PF_RING * (size_t)nh);
@@ -561,8 +562,7 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
         const int nT = (h->A.dt_tab && h->P == 1) ? nb : 0;
         h->trace_stride = nh * (nb + 1 + nT + F.nL_full + h->cw_off[E]);
         h->trace_words = (size_t)h->trace_n * (size_t)h->trace_stride * 4;
-        if (hipMalloc((void**)&h->d_trace, h->trace_words * 8) != hipSuccess) { h->d_trace = nullptr; g_err = "hipMalloc of the workgroup trace failed"; return -1; }
-        hipMemsetAsync(h->d_trace, 0, h->trace_words * 8, h->stream);
+        if (h->trace_mem.alloc(&h->d_trace, h->trace_words, h->stream)) { h->d_trace = nullptr; g_err = "hipMalloc of the workgroup trace failed"; return -1; }
     }
     if (const int rc = F.table(s_end, 0); rc <= 0) return rc;
     for (long long t = 0; t < F.steps; ++t) {

@@ -162,7 +162,7 @@ __device__ __forceinline__ void r_search4_batch(const double* tab, const double 
 }
 // The same answer from a bucket table: the upper sixteen bits of a non-negative double (exponent and four bits of the
 // mantissa: sixteen buckets per octave) grow with the number, so `lut[key - kbase]` = the answer at the bucket's lower edge is
-// a lower bound, and the host only supplies the table when no bucket holds more than two table entries (lut_build, pf_hip.hip):
+// a lower bound, and the host only supplies the table when no bucket holds more than two table entries (lut_build, pf_handle.h):
 // two probes finish the search.  One byte and two doubles from LDS in two round trips and a dozen instructions, where the
 // four-way search takes nine doubles in three round trips and thirty instructions.
 #define PF_LUT_N 256

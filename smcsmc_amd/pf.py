@@ -99,6 +99,7 @@ EXPORTS = [
     "pf_num_segments_done", "pf_logl", "pf_get_counts", "pf_get_trace", "pf_get_resample_events",
     "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_probe_tree_edit", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
     "pf_simulate_sites_wide", "pf_median_survival", "pf_median_survival_opts", "pf_test_math", "pf_test_div", "pf_test_uniform", "pf_test_reduce", "pf_test_systematic",
+    "pf_test_live_bytes", "pf_test_plan",
 ]
 
 
@@ -163,6 +164,9 @@ def load_library(path=None):
     L.pf_test_uniform.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int64, vp, C.c_int]
     L.pf_test_reduce.argtypes = [vp, C.c_int64, vp, vp, C.c_int]
     L.pf_test_systematic.argtypes = [vp, C.c_int64, C.c_double, vp, C.c_int]
+    L.pf_test_live_bytes.restype = C.c_int64
+    L.pf_test_live_bytes.argtypes = []
+    L.pf_test_plan.argtypes = [C.POINTER(_Model), C.POINTER(_Params), vp, C.c_int32]
     if path == LIB_PATH:
         _LIB = L
     return L
@@ -296,6 +300,16 @@ class ParticleFilter:
                  record_trees=False, log_cap=0, gen_cap=0, piece_cap=0, debug=0, mig_cap=0, count_wgs=0, delay_cap=0,
                  delay_evict=False, count_workers=0):
         self.L = load_library()
+        self._pack(model, np_particles, ess_fraction, seed, max_trace_events, local_recomb, record_trees, log_cap, gen_cap, piece_cap, debug,
+                   mig_cap, count_wgs, delay_cap, delay_evict, count_workers)
+        self.h = self.L.pf_create(C.byref(self._model), C.byref(self._params), int(device))
+        if not self.h:
+            raise PfError(_err(self.L))
+        self.n_segs = 0
+
+    def _pack(self, model, np_particles, ess_fraction=0.5, seed=1, max_trace_events=64, local_recomb=False, record_trees=False, log_cap=0,
+              gen_cap=0, piece_cap=0, debug=0, mig_cap=0, count_wgs=0, delay_cap=0, delay_evict=False, count_workers=0):
+        """the pf_model and pf_params of a filter, and the arrays behind them"""
         m = model
         self._ct = np.ascontiguousarray(m["change_times"], dtype=np.float64)
         E = len(self._ct)
@@ -316,10 +330,6 @@ class ParticleFilter:
                                (1 if local_recomb else 0) | (2 if record_trees else 0) | (4 if delay_evict else 0),
                                int(log_cap), int(gen_cap), int(piece_cap), int(debug), int(mig_cap), int(count_wgs), int(delay_cap), int(count_workers), 0)
         self.mig_cap = int(mig_cap) if mig_cap else 96
-        self.h = self.L.pf_create(C.byref(self._model), C.byref(self._params), int(device))
-        if not self.h:
-            raise PfError(_err(self.L))
-        self.n_segs = 0
 
     def _chk(self, rc):
         if rc < 0:
@@ -598,6 +608,38 @@ def calibrated_lags(model, lag_fraction=2.0, seed=1, device=0, debug=0):
     """CountModel::reset_lag (count.cpp:261-265) with the calibrated survival distances."""
     med, _ = median_survival(model, seed=seed, device=device, debug=debug)
     return med * lag_fraction
+
+
+# ---- what pf_create refuses and plans, without a device (pf_test_plan) ----
+PLAN_FIELDS = ("rings", "nslots", "draw_table", "smem", "smem_pipe", "ledger_wgs", "ncw", "workers", "split_batch", "mcap", "dcap", "pcap", "RS",
+               "ncol", "max_trace_events", "E")
+RINGS = (None, "Reg", "Xmp", "Xl")
+
+
+def plan(model, np_particles, tweak=None, **kw):
+    """The first two steps of pf_create for ParticleFilter(model, np_particles, **kw), on any machine: raises PfError with the refusal, or
+    returns the plan as a dict of PLAN_FIELDS (rings as in RINGS) and cw_off[E + 1].  tweak(cmodel, cparams) edits the packed structs first."""
+    L = load_library()
+    kw.pop("device", None)
+    f = ParticleFilter.__new__(ParticleFilter)
+    f.h = None
+    f._pack(model, np_particles, **kw)
+    if tweak is not None:
+        tweak(f._model, f._params)
+    out = np.zeros(len(PLAN_FIELDS) + 64 + 1, np.int32)
+    n = L.pf_test_plan(C.byref(f._model), C.byref(f._params), out.ctypes.data, len(out))
+    if n < 0:
+        raise PfError(_err(L))
+    d = dict(zip(PLAN_FIELDS, (int(v) for v in out)))
+    d["rings"] = RINGS[d["rings"]]
+    d["draw_table"] = bool(d["draw_table"])
+    d["cw_off"] = [int(v) for v in out[len(PLAN_FIELDS):n]]
+    return d
+
+
+def live_bytes():
+    """bytes of device memory the library holds in this process (pf_test_live_bytes)"""
+    return int(load_library().pf_test_live_bytes())
 
 
 # ---- unit-level device entry points (parity tests) ----
