@@ -294,6 +294,11 @@ int pf_probe_handoff(int32_t mode, int32_t rows, int32_t nw, int64_t spin_ticks,
  * the six children after the edit, changed; out_d[2][ncases][4] = the three heights after the edit, the height of the removed node. */
 int pf_probe_tree_edit(int32_t ncases, const double* S, const int32_t* C, const double* h, const int32_t* lin, const int32_t* rp,
                         const int32_t* sb, const double* tc, const double* u_attach, int32_t* out_i, double* out_d, int32_t device);
+/* testing probe (pf_probe.hip; not part of the filter, no timing): the wavefront primitives of pf_device.h on `nwaves` wavefronts of 64
+ * doubles xd and 64 integers xi, by the form that moves operands through __shfl (form 0) and by the form without LDS (form 1).
+ * out_d[2][4][nwaves * 64] = wave_tree_sum, wave_hs_scan, wave_max_scan_d, the value of the lane before (lane 0: its own);
+ * out_i[2][4][nwaves * 64] = wave_max_scan_i, the minimum and the maximum of wave_minmax, the value of the lane before. */
+int pf_probe_wave_prims(int32_t nwaves, const double* xd, const int32_t* xi, double* out_d, int32_t* out_i, int32_t device);
 /* measurement aid: time stamps of every workgroup of the row kernel (k_sweep4t, pf_hip.hip; at most four haplotypes, no focused sampling)
  * for steps [first_step, first_step + n_steps) of the following pf_run / pf_run_many calls led by `h`.  pf_get_wg_trace copies four
  * 64-bit words per workgroup slot and traced step -- start, end (100 MHz clock; 0 0: the step's grid did not use the slot),

@@ -204,15 +204,101 @@ __device__ __forceinline__ int pf_bx() { return (int)blockIdx.x; }
 __device__ __forceinline__ int pf_chunk() { return (int)blockIdx.y; }
 
 // ------------------------------------------------------------------ wavefront (64-lane) primitives
+// Two forms of each.  The *_lds forms move operands with __shfl_xor / __shfl_up (ds_bpermute_b32: an LDS round trip per step); they
+// work under any execution mask whose lanes only read one another, and are what pf_probe_wave_prims holds the other form to.  The
+// forms without a suffix compute the same operand pairs in the same order (the association is part of the
+// canonical arithmetic) and move the operands with the data-parallel primitives (v_mov_b32_dpp) and the two lane swaps of gfx950
+// (v_permlane16_swap_b32, v_permlane32_swap_b32): no LDS, no lgkmcnt wait.  Those read active lanes only, so they REQUIRE A FULL
+// WAVEFRONT: a call under a lane-dependent condition has to use the *_lds form.  NaN operands are out of scope for both (which
+// payload survives an addition depends on the operand order; a + b and b + a have equal bits otherwise).
+//
+// Lane maps (rows are the four groups of sixteen lanes): quad_perm inside four lanes; row_half_mirror lane j <-> 7 - j inside eight;
+// row_mirror j <-> 15 - j inside a row; row_shr:d lane j of a row reads j - d of the same row (j < d: no source, `old` stays);
+// row_ror:d reads (j - d) mod 16; wave_shr:1 lane i reads i - 1 (lane 0: `old`); permlane16_swap of (v, v) returns rows
+// [0,0,2,2] and [1,1,3,3]; permlane32_swap of (v, v) returns [lower half, lower half] and [upper half, upper half].
+constexpr int DPP_QUAD_XOR1 = 0xB1, DPP_QUAD_XOR2 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141, DPP_ROW_MIRROR = 0x140, DPP_WAVE_SHR1 = 0x138;
+constexpr int DPP_ROW_SHR = 0x110, DPP_ROW_ROR = 0x120, DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;
+
+// src moved by CTRL into the rows of ROW_MASK; every other lane, and a lane whose source lies outside its row, gets `old`
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ int dpp_mov(int old, int src) { return __builtin_amdgcn_update_dpp(old, src, CTRL, ROW_MASK, 0xf, false); }
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ double dpp_mov(double old, double src) {
+    const int lo = dpp_mov<CTRL, ROW_MASK>(__double2loint(old), __double2loint(src));
+    const int hi = dpp_mov<CTRL, ROW_MASK>(__double2hiint(old), __double2hiint(src));
+    return __hiloint2double(hi, lo);
+}
+struct WavePairI { int a, b; };
+struct WavePairD { double a, b; };
+// a = rows [0,0,2,2] of v, b = rows [1,1,3,3]
+__device__ __forceinline__ WavePairI wave_swap16(int v) {
+    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+    return {(int)r[0], (int)r[1]};
+}
+// a = [lower half, lower half] of v, b = [upper half, upper half]
+__device__ __forceinline__ WavePairI wave_swap32(int v) {
+    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+    return {(int)r[0], (int)r[1]};
+}
+__device__ __forceinline__ WavePairD wave_swap16(double v) {
+    const WavePairI lo = wave_swap16(__double2loint(v)), hi = wave_swap16(__double2hiint(v));
+    return {__hiloint2double(hi.a, lo.a), __hiloint2double(hi.b, lo.b)};
+}
+__device__ __forceinline__ WavePairD wave_swap32(double v) {
+    const WavePairI lo = wave_swap32(__double2loint(v)), hi = wave_swap32(__double2hiint(v));
+    return {__hiloint2double(hi.a, lo.a), __hiloint2double(hi.b, lo.b)};
+}
+// v of the row before: lane i of rows 1 to 3 gets v[i - 16] (row 0 gets lanes of row 1: not a source, callers mask it).  Rows 1 and 3
+// read the swap of rows, row 2 the lower half of the other product of that swap.
+template <class T>
+__device__ __forceinline__ T wave_row_up(T v, int lane) {
+    const auto r = wave_swap16(v);
+    const auto h = wave_swap32(r.b);
+    return (lane & 16) ? r.a : h.a;
+}
+
 // xor-butterfly sum: every lane ends with the same pairwise-tree total (matches oracle tree64).
-__device__ __forceinline__ double wave_tree_sum(double v) {
+__device__ __forceinline__ double wave_tree_sum_lds(double v) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
     return v;
 }
+// The same six additions per lane.  After the step with mask m the 2m lanes of a group hold equal bits (a + b == b + a bit for bit),
+// so a later step may read ANY lane of the partner group: the mirrors are such reads (the image of a lane under row_half_mirror
+// lies in the other group of four, under row_mirror in the other group of eight), and so are the swaps.
+__device__ __forceinline__ double wave_tree_sum(double v) {
+    v = v + dpp_mov<DPP_QUAD_XOR1>(v, v);
+    v = v + dpp_mov<DPP_QUAD_XOR2>(v, v);
+    v = v + dpp_mov<DPP_ROW_HALF_MIRROR>(v, v);
+    v = v + dpp_mov<DPP_ROW_MIRROR>(v, v);
+    const WavePairD r = wave_swap16(v);
+    v = r.a + r.b;
+    const WavePairD h = wave_swap32(v);
+    return h.a + h.b;
+}
+// min and max over the wavefront in every lane (exact under any association: the reads are those of wave_tree_sum)
+__device__ __forceinline__ void wave_minmax_lds(int& cmin, int& cmax) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        int o1 = __shfl_xor(cmin, m, 64), o2 = __shfl_xor(cmax, m, 64);
+        cmin = o1 < cmin ? o1 : cmin; cmax = o2 > cmax ? o2 : cmax;
+    }
+}
+__device__ __forceinline__ void wave_minmax(int& cmin, int& cmax) {
+    cmin = min(cmin, dpp_mov<DPP_QUAD_XOR1>(cmin, cmin));             cmax = max(cmax, dpp_mov<DPP_QUAD_XOR1>(cmax, cmax));
+    cmin = min(cmin, dpp_mov<DPP_QUAD_XOR2>(cmin, cmin));             cmax = max(cmax, dpp_mov<DPP_QUAD_XOR2>(cmax, cmax));
+    cmin = min(cmin, dpp_mov<DPP_ROW_HALF_MIRROR>(cmin, cmin));       cmax = max(cmax, dpp_mov<DPP_ROW_HALF_MIRROR>(cmax, cmax));
+    cmin = min(cmin, dpp_mov<DPP_ROW_MIRROR>(cmin, cmin));            cmax = max(cmax, dpp_mov<DPP_ROW_MIRROR>(cmax, cmax));
+    const WavePairI a = wave_swap16(cmin), b = wave_swap16(cmax);
+    cmin = min(a.a, a.b); cmax = max(b.a, b.b);
+    const WavePairI c = wave_swap32(cmin), e = wave_swap32(cmax);
+    cmin = min(c.a, c.b); cmax = max(e.a, e.b);
+}
 // Sum over the wavefront without LDS traffic: row shifts and row broadcasts of the data-parallel primitives (four steps inside the
-// rows of sixteen lanes, two across them), total read from lane 63.  A different association from wave_tree_sum's butterfly --
-// for sums whose grouping is not part of the canonical arithmetic (the lagged counts) -- and the same one in every run.
+// rows of sixteen lanes, two across them), total read from lane 63.  Used for sums whose grouping is not part of the canonical
+// arithmetic (the lagged counts); the same grouping in every run.  (The total in lane 63 is in fact the butterfly's balanced tree,
+// pair for pair -- tests/test_wave_prims_model_cpu.py -- only the partial sums it leaves in the other lanes are not the oracle's
+// scan; lanes without a source add +0.0 here, which the canonical forms never do.)
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double wave_dpp_add(double v) {
     const int lo = __double2loint(v), hi = __double2hiint(v);
@@ -230,8 +316,11 @@ __device__ __forceinline__ double wave_total_dpp(double v) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
     return __hiloint2double(hi, lo);
 }
+// v of the lane before (lane 0: `first`)
+template <class T>
+__device__ __forceinline__ T wave_prev_lane(T v, T first) { return dpp_mov<DPP_WAVE_SHR1>(first, v); }
 // Hillis-Steele inclusive scan across the wavefront (matches oracle hs64).
-__device__ __forceinline__ double wave_hs_scan(double v, int lane) {
+__device__ __forceinline__ double wave_hs_scan_lds(double v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         double o = __shfl_up(v, d, 64);
@@ -239,7 +328,29 @@ __device__ __forceinline__ double wave_hs_scan(double v, int lane) {
     }
     return v;
 }
-__device__ __forceinline__ double wave_max_scan_d(double v, int lane) {
+// The same: lane i >= d takes v[i - d] + v[i], so here the movement itself has to be exact.  d = 1 and 2: wave_shr:1 once and
+// twice.  d = 4 and 8: row_shr:d inside a row; the first d lanes of rows 1 to 3 read the last d lanes of the row before, which is
+// row_ror:d of wave_row_up(v).  d = 16: wave_row_up(v).  d = 32: the upper half reads the lower.  A lane below d keeps v by a
+// select, not by adding zero (-0.0 + 0.0 is +0.0).
+__device__ __forceinline__ double wave_hs_scan(double v, int lane) {
+    double o = dpp_mov<DPP_WAVE_SHR1>(v, v);
+    v = lane >= 1 ? o + v : v;
+    o = dpp_mov<DPP_WAVE_SHR1>(v, v); o = dpp_mov<DPP_WAVE_SHR1>(o, o);
+    v = lane >= 2 ? o + v : v;
+    o = dpp_mov<DPP_ROW_SHR + 4>(dpp_mov<DPP_ROW_ROR + 4>(v, wave_row_up(v, lane)), v);
+    v = lane >= 4 ? o + v : v;
+    o = dpp_mov<DPP_ROW_SHR + 8>(dpp_mov<DPP_ROW_ROR + 8>(v, wave_row_up(v, lane)), v);
+    v = lane >= 8 ? o + v : v;
+    o = wave_row_up(v, lane);
+    v = lane >= 16 ? o + v : v;
+    o = wave_swap32(v).a;
+    v = lane >= 32 ? o + v : v;
+    return v;
+}
+// Running maximum.  `o > v ? o : v` with o the earlier stretch keeps, among equal maxima (+0.0 and -0.0 compare equal), the last one
+// of the prefix under any association of contiguous stretches, so the row scan below returns the bits of the Hillis-Steele form:
+// row_shr:1/2/4/8 (a lane without a source reads itself), then lane 15 of the row before into rows 1 and 3, lane 31 into rows 2, 3.
+__device__ __forceinline__ double wave_max_scan_d_lds(double v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         double o = __shfl_up(v, d, 64);
@@ -247,7 +358,7 @@ __device__ __forceinline__ double wave_max_scan_d(double v, int lane) {
     }
     return v;
 }
-__device__ __forceinline__ int wave_max_scan_i(int v, int lane) {
+__device__ __forceinline__ int wave_max_scan_i_lds(int v, int lane) {
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         int o = __shfl_up(v, d, 64);
@@ -255,6 +366,22 @@ __device__ __forceinline__ int wave_max_scan_i(int v, int lane) {
     }
     return v;
 }
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ double wave_dpp_max(double v) { const double o = dpp_mov<CTRL, ROW_MASK>(v, v); return o > v ? o : v; }
+template <int CTRL, int ROW_MASK = 0xf>
+__device__ __forceinline__ int wave_dpp_max(int v) { return max(v, dpp_mov<CTRL, ROW_MASK>(v, v)); }
+template <class T>
+__device__ __forceinline__ T wave_max_scan(T v) {
+    v = wave_dpp_max<DPP_ROW_SHR + 1>(v);
+    v = wave_dpp_max<DPP_ROW_SHR + 2>(v);
+    v = wave_dpp_max<DPP_ROW_SHR + 4>(v);
+    v = wave_dpp_max<DPP_ROW_SHR + 8>(v);
+    v = wave_dpp_max<DPP_ROW_BCAST15, 0xa>(v);
+    v = wave_dpp_max<DPP_ROW_BCAST31, 0xc>(v);
+    return v;
+}
+__device__ __forceinline__ double wave_max_scan_d(double v, int) { return wave_max_scan(v); }
+__device__ __forceinline__ int wave_max_scan_i(int v, int) { return wave_max_scan(v); }
 
 // ------------------------------------------------------------------ per-lane state held in LDS
 // A particle's local tree lives in LDS for the duration of a kernel so that it can be indexed

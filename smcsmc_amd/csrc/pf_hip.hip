@@ -366,11 +366,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
                 }
                 PF_STAMP(17);
                 int cmin = active ? pch : 0x7fffffff, cmax = active ? pch : -1;
-#pragma unroll
-                for (int m = 1; m < 64; m <<= 1) {
-                    int o1 = __shfl_xor(cmin, m, 64), o2 = __shfl_xor(cmax, m, 64);
-                    cmin = o1 < cmin ? o1 : cmin; cmax = o2 > cmax ? o2 : cmax;
-                }
+                wave_minmax(cmin, cmax);
                 if (lane == 0) { q.wint[wave] = cmin; q.wint[PF_BS / 64 + wave] = cmax; }
                 __syncthreads();
                 if (active) lo_p1 = lo_next;
@@ -818,9 +814,9 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
     }
     PF_STAMP(7);
     const KA& A2 = pf_reopen(A);
+    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
     double sp = wave_tree_sum(w_post);
     double sq = wave_tree_sum(w_pilot * w_pilot);
-    double sc = wave_hs_scan(w_pilot, lane);
     double scp = wave_hs_scan(w_post, lane);
     double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
     long long chunk = p >> 6;
@@ -1072,7 +1068,7 @@ __device__ __forceinline__ void decide_body(const KA& A, long long s, int mode, 
         __syncthreads();
         double pre = 0.0;
         for (int w = 0; w < wave; ++w) pre = wredd[w] > pre ? wredd[w] : pre;
-        double before = __shfl_up(scd, 1, 64);
+        double before = wave_prev_lane(scd, scd);
         if (lane > 0) pre = before > pre ? before : pre;
         run = pre;                           // exclusive prefix for this thread's first chunk
         for (int ch = c0; ch < c1; ++ch) {
@@ -2501,9 +2497,9 @@ __global__ __launch_bounds__(PF_BS) void k_partials(KArgs A) {
         A.snap_w[A.sp][p] = w_post; A.snap_xm[A.sp][p] = st.x_mark[p]; A.snap_ml[A.sp][p] = st.mark_limit[p];
         A.snap_widx[A.sp][p] = A.widx[p];
     }
+    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
     double sp = wave_tree_sum(w_post);
     double sq = wave_tree_sum(w_pilot * w_pilot);
-    double sc = wave_hs_scan(w_pilot, lane);
     double scp = wave_hs_scan(w_post, lane);
     double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
     long long chunk = p >> 6;

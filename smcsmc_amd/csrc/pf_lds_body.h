@@ -299,9 +299,9 @@ __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, dou
         A.snap_w[A.sp][p] = w_post; A.snap_xm[A.sp][p] = x_mark; A.snap_ml[A.sp][p] = mark_limit; A.snap_widx[A.sp][p] = widx;
     }
     // per-wavefront canonical partials (level 1 of the radix-64 reduction / scan)
+    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
     double sp = wave_tree_sum(w_post);
     double sq = wave_tree_sum(w_pilot * w_pilot);
-    double sc = wave_hs_scan(w_pilot, lane);
     double scp = wave_hs_scan(w_post, lane);
     double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
     long long chunk = p >> 6;

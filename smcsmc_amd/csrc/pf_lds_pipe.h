@@ -148,11 +148,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
                 pch = lo_c;
             }
             int cmin = active ? pch : 0x7fffffff, cmax = active ? pch : -1;
-#pragma unroll
-            for (int k = 1; k < 64; k <<= 1) {
-                int o1 = __shfl_xor(cmin, k, 64), o2 = __shfl_xor(cmax, k, 64);
-                cmin = o1 < cmin ? o1 : cmin; cmax = o2 > cmax ? o2 : cmax;
-            }
+            wave_minmax(cmin, cmax);
             if (lane == 0) { q.wint[wave] = cmin; q.wint[PF_BS / 64 + wave] = cmax; }
             __syncthreads();
             if (active) {
@@ -458,9 +454,9 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
         }
     }
     // per-wavefront canonical partials (level 1 of the radix-64 reduction / scan) into the row's ring slot
+    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
     double sp = wave_tree_sum(w_post);
     double sq = wave_tree_sum(w_pilot * w_pilot);
-    double sc = wave_hs_scan(w_pilot, lane);
     double scp = wave_hs_scan(w_post, lane);
     double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
     const long long chunk = p >> 6;

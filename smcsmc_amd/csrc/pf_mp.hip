@@ -573,11 +573,7 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
                         pch = lo_c;
                     }
                     int cmin = qa ? pch : 0x7fffffff, cmax = qa ? pch : -1;
-#pragma unroll
-                    for (int m = 1; m < 64; m <<= 1) {
-                        int o1 = __shfl_xor(cmin, m, 64), o2 = __shfl_xor(cmax, m, 64);
-                        cmin = o1 < cmin ? o1 : cmin; cmax = o2 > cmax ? o2 : cmax;
-                    }
+                    wave_minmax(cmin, cmax);        // (the first wavefront as a whole: threadIdx.x < 64)
                     if (lane == 0) { sRange[0] = cmin; sRange[1] = cmax; }
                 }
                 __syncthreads();
@@ -598,7 +594,7 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
                 }
                 __syncthreads();
                 if (threadIdx.x < 64) {
-                    int lp = __shfl_up(lo_next, 1, 64);
+                    int lp = wave_prev_lane(lo_next, lo_next);
                     if (lane == 0) lp = qp > 0 ? pipe_lo_from(q.pmx[ch_own], dn, A.Np, d.S1, invS1, d.u) : 0;
                     const unsigned long long bal = __ballot(qa && lo_next > lp);
                     if (lane == 0) A.rg_blkcnt[(size_t)row_slot * ((A.Np + 255) / 256) * A.blk_gran + blockIdx.x] = __popcll(bal);

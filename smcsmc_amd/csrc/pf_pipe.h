@@ -139,7 +139,7 @@ __device__ __forceinline__ RowDecision decide_row(const KA& A, const PipeLds& q,
         __syncthreads();
         double pre = 0.0;
         for (int w = 0; w < wave; ++w) pre = q.wredd[w] > pre ? q.wredd[w] : pre;
-        double before = __shfl_up(scd, 1, 64);
+        double before = wave_prev_lane(scd, scd);
         if (lane > 0) pre = before > pre ? before : pre;
         run = pre;
         for (int ch = c0; ch < c1; ++ch) {

@@ -149,6 +149,37 @@ __global__ __launch_bounds__(256) void k_tree_edit4(int ncases, const double* S,
     }
 }
 
+// One wavefront per 64 values: every wavefront primitive of pf_device.h in its *_lds form (form 0) and in the form without LDS (form 1).
+// od[form][0..3][i] = wave_tree_sum, wave_hs_scan, wave_max_scan_d, the value of the lane before (shift by one, lane 0 its own);
+// oi[form][0..3][i] = wave_max_scan_i, the minimum and the maximum of wave_minmax, the value of the lane before.
+__global__ __launch_bounds__(256) void k_wave_prims(int nwaves, const double* xd, const int32_t* xi, double* od, int32_t* oi) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, n = (size_t)nwaves * 64;
+    const int lane = threadIdx.x & 63;
+    if (i >= n) return;                   // (whole wavefronts: n is a multiple of 64)
+    const double v = xd[i];
+    const int k = xi[i];
+    od[(0 * 4 + 0) * n + i] = pf::wave_tree_sum_lds(v);
+    od[(0 * 4 + 1) * n + i] = pf::wave_hs_scan_lds(v, lane);
+    od[(0 * 4 + 2) * n + i] = pf::wave_max_scan_d_lds(v, lane);
+    od[(0 * 4 + 3) * n + i] = __shfl_up(v, 1, 64);
+    od[(1 * 4 + 0) * n + i] = pf::wave_tree_sum(v);
+    od[(1 * 4 + 1) * n + i] = pf::wave_hs_scan(v, lane);
+    od[(1 * 4 + 2) * n + i] = pf::wave_max_scan_d(v, lane);
+    od[(1 * 4 + 3) * n + i] = pf::wave_prev_lane(v, v);
+    int mn = k, mx = k;
+    pf::wave_minmax_lds(mn, mx);
+    oi[(0 * 4 + 0) * n + i] = pf::wave_max_scan_i_lds(k, lane);
+    oi[(0 * 4 + 1) * n + i] = mn;
+    oi[(0 * 4 + 2) * n + i] = mx;
+    oi[(0 * 4 + 3) * n + i] = __shfl_up(k, 1, 64);
+    mn = k; mx = k;
+    pf::wave_minmax(mn, mx);
+    oi[(1 * 4 + 0) * n + i] = pf::wave_max_scan_i(k, lane);
+    oi[(1 * 4 + 1) * n + i] = mn;
+    oi[(1 * 4 + 2) * n + i] = mx;
+    oi[(1 * 4 + 3) * n + i] = pf::wave_prev_lane(k, k);
+}
+
 }  // namespace
 
 // mode 0: `rows` launches of k_handoff_launch back to back on one stream; mode 1: one launch of the resident grid, every wavefront
@@ -233,5 +264,29 @@ extern "C" int pf_probe_tree_edit(int32_t ncases, const double* S, const int32_t
     for (int k = 0; k < 8; ++k) if (d[k]) hipFree(d[k]);
     if (d_oi) hipFree(d_oi);
     if (d_od) hipFree(d_od);
+    return ok ? 0 : -2;
+}
+
+// The wavefront primitives of pf_device.h, both forms side by side (k_wave_prims above; not part of the filter, no timing): nwaves
+// wavefronts of 64 doubles xd and 64 integers xi from the host.  out_d[2][4][nwaves * 64], out_i[2][4][nwaves * 64].
+extern "C" int pf_probe_wave_prims(int32_t nwaves, const double* xd, const int32_t* xi, double* out_d, int32_t* out_i, int32_t device) {
+    if (nwaves < 1 || nwaves > (1 << 18)) return -1;
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    const size_t n = (size_t)nwaves * 64;
+    double *d_xd = nullptr, *d_od = nullptr;
+    int32_t *d_xi = nullptr, *d_oi = nullptr;
+    bool ok = hipMalloc(&d_xd, n * 8) == hipSuccess && hipMalloc(&d_xi, n * 4) == hipSuccess && hipMalloc(&d_od, n * 8 * 8) == hipSuccess &&
+              hipMalloc(&d_oi, n * 8 * 4) == hipSuccess && hipMemcpy(d_xd, xd, n * 8, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(d_xi, xi, n * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_wave_prims, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, nwaves, (const double*)d_xd, (const int32_t*)d_xi, d_od, d_oi);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(out_d, d_od, n * 8 * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(out_i, d_oi, n * 8 * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    if (d_xd) hipFree(d_xd);
+    if (d_xi) hipFree(d_xi);
+    if (d_od) hipFree(d_od);
+    if (d_oi) hipFree(d_oi);
     return ok ? 0 : -2;
 }

@@ -97,7 +97,7 @@ EXPORTS = [
     "pf_terminal_branch_quantiles",
     "pf_update_segment", "pf_count", "pf_resample", "pf_run", "pf_run_many", "pf_can_run_many", "pf_get_run_path", "pf_finish", "pf_sync",
     "pf_num_segments_done", "pf_logl", "pf_get_counts", "pf_get_trace", "pf_get_resample_events",
-    "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_probe_tree_edit", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
+    "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_probe_tree_edit", "pf_probe_wave_prims", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
     "pf_simulate_sites_wide", "pf_median_survival", "pf_median_survival_opts", "pf_test_math", "pf_test_div", "pf_test_uniform", "pf_test_reduce", "pf_test_systematic",
     "pf_test_live_bytes", "pf_test_plan",
 ]
@@ -152,6 +152,7 @@ def load_library(path=None):
     L.pf_get_delay_stats.argtypes = [vp, vp, vp]
     L.pf_probe_handoff.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32]
     L.pf_probe_tree_edit.argtypes = [C.c_int32] + [vp] * 10 + [C.c_int32]
+    L.pf_probe_wave_prims.argtypes = [C.c_int32] + [vp] * 4 + [C.c_int32]
     L.pf_set_wg_trace.argtypes = [vp, C.c_int64, C.c_int32]
     L.pf_get_wg_trace.argtypes = [vp, vp, C.c_int64, vp]
     L.pf_get_wg_trace.restype = C.c_int64
@@ -289,6 +290,25 @@ def probe_tree_edit(S, Cc, h, lin, rp, sb, tc, u_attach, device=0):
     if rc != 0:
         raise PfError("pf_probe_tree_edit failed (%d)" % rc)
     return oi, od
+
+
+WAVE_PRIMS_D = ("wave_tree_sum", "wave_hs_scan", "wave_max_scan_d", "wave_prev_lane")
+WAVE_PRIMS_I = ("wave_max_scan_i", "wave_minmax.min", "wave_minmax.max", "wave_prev_lane")
+
+
+def probe_wave_prims(xd, xi, device=0):
+    """The wavefront primitives of pf_device.h on wavefronts of 64 values (pf_probe_wave_prims): xd[K][64] doubles, xi[K][64] integers.
+    Returns (out_d[2][4][K][64], out_i[2][4][K][64]) in the order of WAVE_PRIMS_D / WAVE_PRIMS_I, form 0 = through __shfl, 1 = no LDS."""
+    L = load_library()
+    xd = np.ascontiguousarray(xd, dtype=np.float64); xi = np.ascontiguousarray(xi, dtype=np.int32)
+    if xd.ndim != 2 or xd.shape[1] != 64 or xi.shape != xd.shape:
+        raise PfError("probe_wave_prims: xd and xi must both be [K][64]")
+    k = xd.shape[0]
+    od = np.zeros((2, 4, k, 64), np.float64); oi = np.zeros((2, 4, k, 64), np.int32)
+    rc = L.pf_probe_wave_prims(k, xd.ctypes.data, xi.ctypes.data, od.ctypes.data, oi.ctypes.data, int(device))
+    if rc != 0:
+        raise PfError("pf_probe_wave_prims failed (%d)" % rc)
+    return od, oi
 
 
 # pf_get_run_path (PF_PATH_* of smcsmc_pf.h, in order)
