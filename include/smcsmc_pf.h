@@ -148,7 +148,7 @@ typedef struct pf_lookahead {
     int32_t level;                            /* -apf */
     int32_t max_doubletons;                   /* D: doubleton slots per row */
     int32_t n_quantiles;                      /* Q */
-    int32_t reserved;
+    int32_t flags;                            /* PF_LA_*; 0: the look-ahead on the general kernels, as ever */
     int64_t n;                                /* rows (= segments) */
     const double* first_singleton_distance;   /* [n*nsam] */
     const double* relative_mutation_rate;     /* [n*nsam] */
@@ -163,6 +163,12 @@ typedef struct pf_lookahead {
     const double* tbl_lengths;                /* [nsam*Q] */
     double mean_total_branch_length;
 } pf_lookahead;
+/* pf_lookahead.flags bit 0: run the look-ahead inside the extend role of the row pipeline (the LOOK instances of k_sweep, one launch per
+ * row) where the handle qualifies: one population, at most 8 haplotypes, at most 131 072 particles, no focused sampling, no guide, no
+ * -arg, no count_workers, no debug switch that selects a path.  Any other handle keeps the general kernels, without an error:
+ * pf_get_run_path tells.  Same bits either way (tests/test_gpu_lookahead_rows.py).  A later pf_load_lookahead with level 0 or without
+ * the bit returns the handle to the general kernels. */
+#define PF_LA_ROW_PIPELINE 1
 
 typedef struct pf_handle pf_handle;
 
@@ -228,7 +234,12 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * launch of the other roles (k_sweep_blc<16, 1, *>) per row for all chunks.  Such chunks must have the same number of haplotypes (the
  * width of the tree columns is the launch's LDS size: 12 does not run with 16, nor either with 8 or fewer), delay_cap and bias bands.
  * pf_run on ONE such handle keeps the general kernels (k_extend -> k_decide -> k_resample); nobody has measured one chunk on the pipeline.
- * Not taken: structured models above 8 haplotypes, -arg with structure or above 8 haplotypes, the look-ahead, more than 16 haplotypes (the wide kernels).
+ * A look-ahead (pf_load_lookahead) is taken only when it was loaded with PF_LA_ROW_PIPELINE on a handle that qualifies for it (one
+ * population, at most 8 haplotypes, no focused sampling, no -arg): k_sweep<..., LOOK>, one launch per row for pf_run and pf_run_many alike,
+ * also at four haplotypes and fewer.  The handles of a group then agree in it: all without a look-ahead, or all with the bit and the same
+ * level, max_doubletons and n_quantiles.
+ * Not taken: structured models above 8 haplotypes, -arg with structure or above 8 haplotypes, a look-ahead without that bit or on a handle
+ * that does not qualify, more than 16 haplotypes (the wide kernels).
  * The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
  * every chunk's results are bit-identical to its own pf_run.  A chunk that runs out of rows simply stops and sits later calls out.
  * Afterwards every handle's own stream continues behind the call: pf_run, pf_finish, pf_get_counts and the step API mix freely with it. */
@@ -236,17 +247,19 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
 /* 1 when pf_run_many would take these handles, 0 when the caller has to run them one after the other with pf_run (the row
  * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure
  * (at any number of haplotypes: such handles run on the general path, row kernel -> k_decide -> k_resample),
- * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path -- or they
- * differ in shape: haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks,
+ * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path, or a
+ * look-ahead loaded without PF_LA_ROW_PIPELINE or on a handle that does not qualify for it -- or they
+ * differ in shape: one with a look-ahead and one without, or look-aheads of two levels or table sizes, haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks,
  * or a tree-recording handle mixed with a plain one).  One population with at most 8 haplotypes and -arg IS taken, whatever the chunks'
  * log_cap / gen_cap. */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 /* Which runner takes the rows of this handle as it stands now (a look-ahead loaded later changes the answer): pf_run's with many == 0,
  * pf_run_many's otherwise, where -1 says that pf_run_many refuses the handle.  DESIGN.md, "Which path runs when". */
-#define PF_PATH_GENERAL     0    /* one launch per role and row, two streams (every model; the only path with a look-ahead) */
+#define PF_PATH_GENERAL     0    /* one launch per role and row, two streams (every model; a look-ahead loaded without PF_LA_ROW_PIPELINE) */
 #define PF_PATH_TWO_LAUNCH  1    /* k_row + k_decide_ledger (PF_DEBUG_TWO_LAUNCH, or more than 131 072 particles) */
 #define PF_PATH_K_PIPE      2    /* k_pipe (PF_DEBUG_K_PIPE) */
 #define PF_PATH_SWEEP       3    /* k_sweep: every role of a step in one launch */
+/*                               (also a look-ahead loaded with PF_LA_ROW_PIPELINE on a qualifying handle: k_sweep<..., LOOK>, at any n <= 8) */
 #define PF_PATH_SWEEP_SPLIT 4    /* k_sweep4 + k_sweep_blc4: one population, at most four haplotypes, the default */
 #define PF_PATH_SWEEP_XMP   5    /* k_sweep_xmp + k_sweep_blc: structured models, at most 8 haplotypes */
 #define PF_PATH_SWEEP_XL    6    /* k_sweep_xl + k_sweep_blc: one population, 9 to 16 haplotypes, pf_run_many only */

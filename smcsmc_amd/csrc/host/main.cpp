@@ -51,7 +51,7 @@ static void dump_model_json(const PfParam& p) {
     }
     cout << "], \"sample_pops\": [";
     for (size_t k = 0; k < m.sample_pops.size(); ++k) cout << (k ? ", " : "") << m.sample_pops[k];
-    cout << "], \"record_mask\": [";
+    cout << "], \"apf\": " << p.apf_level << ", \"apf_pipeline\": " << (p.apf_pipeline ? "true" : "false") << ", \"record_mask\": [";
     for (size_t k = 0; k < p.record_mask.size(); ++k) cout << (k ? ", " : "") << p.record_mask[k];
     cout << "], \"guide_positions\": [";
     for (size_t k = 0; k < p.guide_positions.size(); ++k) cout << (k ? ", " : "") << p.guide_positions[k];
@@ -302,6 +302,7 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
         pf_lookahead pl;
         memset(&pl, 0, sizeof(pl));
         pl.level = P.apf_level; pl.max_doubletons = la.max_doubletons; pl.n_quantiles = 7; pl.n = sg.n;
+        pl.flags = P.apf_pipeline ? PF_LA_ROW_PIPELINE : 0;
         pl.first_singleton_distance = la.first_singleton_distance.data();
         pl.relative_mutation_rate = la.relative_mutation_rate.data();
         pl.is_singleton_unphased = la.is_singleton_unphased.data();
@@ -616,12 +617,13 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
     std::vector<std::vector<double>> all(R, std::vector<double>((size_t)R * slots * LEN, 0.0));
     std::vector<std::string> failure(R);
     // the chunks of a rank go through the same launches, row by row, when the row pipeline applies to them (include/smcsmc_pf.h, pf_run_many):
-    // one population, at most 16 haplotypes (above 8 on the LDS tree: k_sweep_xl), no look-ahead; with -arg at most 8 haplotypes (the TREES
+    // one population, at most 16 haplotypes (above 8 on the LDS tree: k_sweep_xl), no look-ahead unless -apf_pipeline asks for it on the
+    // rows (the library then takes it at one population of at most 8 haplotypes without -arg); with -arg at most 8 haplotypes (the TREES
     // instances of k_sweep / k_sweep4 -- above 8 the library refuses tree-recording handles, and a group of -arg rings opened only to be
     // filtered one by one would hold the device's memory for nothing).  pf_can_run_many decides.  The library takes
     // the chunks of a structured model too (pf_run_many), but this binary keeps filtering those one after the other
     // until lockstep has been measured not slower than that at four chunks (section 7: not measured yet) -- npop == 1 below is the switch
-    const bool lockstep = P.model.npop == 1 && P.model.nsam <= 16 && P.apf_level == 0 && !(P.record_trees && P.model.nsam > 8);
+    const bool lockstep = P.model.npop == 1 && P.model.nsam <= 16 && (P.apf_level == 0 || P.apf_pipeline) && !(P.record_trees && P.model.nsam > 8);
     std::mutex notes_lock;
     auto rank_main = [&](int r) {
         bool entered = false;
@@ -660,7 +662,7 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
             // Side by side in groups: as many of the rank's chunks as the device has memory for are opened together (every
             // filter holds its own rings: the event log alone is Np x 16 384 records by default) and go through one launch per
             // row when the library says the group can (pf_can_run_many: the row pipeline applies to all of them -- one
-            // population, at most 16 haplotypes, no look-ahead, Np <= 131 072 -- and they share their shape); otherwise, and
+            // population, at most 16 haplotypes, no look-ahead but that of -apf_pipeline, Np <= 131 072 -- and they share their shape); otherwise, and
             // whenever a group comes down to one chunk, one after the other.
             size_t k0 = 0;
             while (k0 < my_chunks.size()) {

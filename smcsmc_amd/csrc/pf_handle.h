@@ -29,6 +29,7 @@ struct pf_handle {
     bool finished = false;
     bool fin_pending = false;     // k_count partials not yet folded into the totals
     Windows step_windows;         // windows of the step being processed
+    int la_flags = 0;             // pf_lookahead.flags of the look-ahead in force (PF_LA_ROW_PIPELINE; 0 without one)
     int debug = 0;                // pf_params.debug: the PF_DEBUG_* switches that select a path are read from here (run_path)
     Rings rings = Rings::None;
     bool wide = false;            // one population on the wide kernels of pf_wide.hip: nsam > PF_NMAX, or PF_DEBUG_FORCE_WIDE (testing)
@@ -315,7 +316,7 @@ int pf_load_lookahead(pf_handle* h, const pf_lookahead* la) {
     HIPCHK(hipSetDevice(h->device));
     if (la->level < 0 || la->level > 4) { g_err = "-apf must be in 0..4"; return -1; }
     if (la->n != h->n_segs) { g_err = "pf_load_lookahead: one look-ahead record per segment expected"; return -1; }
-    if (la->level == 0) { h->A.apf = 0; return 0; }
+    if (la->level == 0) { h->A.apf = 0; h->la_flags = 0; return 0; }
     if (h->wide) { g_err = "-apf (the auxiliary particle filter) needs nsam <= 16"; return -1; }
     const long long S = la->n;
     const int n = h->n, D = la->max_doubletons, Q = la->n_quantiles;
@@ -346,6 +347,7 @@ int pf_load_lookahead(pf_handle* h, const pf_lookahead* la) {
     A.la_fsd = fsd; A.la_rmr = rmr; A.la_unph = unph; A.la_nd = nd; A.la_didx = didx; A.la_ddist = ddist;
     A.la_split = split; A.la_salleles = sal; A.la_sk = sk; A.la_q = q; A.la_tbl = tbl;
     A.la_mean_tbl = la->mean_total_branch_length;
+    h->la_flags = la->flags & PF_LA_ROW_PIPELINE;      // (with the load: a later one without the bit returns the handle to the general kernels)
     h->smem_la = smem_bytes_la(n, h->E);
     if (h->smem_la > 64 * 1024) hipFuncSetAttribute((const void*)k_lookahead, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_la);
     return 0;

@@ -30,6 +30,7 @@
 #include "pf_types.h"
 #include "pf_lane.h"
 #include "pf_tree_reg.h"
+#include "pf_look_reg.h"
 #include "pf_lds_body.h"
 #include "pf_mp_host.h"
 #include "pf_wide_host.h"
@@ -107,6 +108,10 @@ __device__ __forceinline__ int gridDim_particles(const KA& A) { return (int)((A.
 // from one address (the note, last1, the segment) would be moved to scalar registers, behind a wait, right where it is loaded: those
 // values stay in vector registers until pf_arrive() where they are first used.  PR.pos_prev is not used: the end of row s - 1 is
 // requested with the rest.
+// LOOK (with PIPE, without HEAD, BIASED and TREES; k_sweep<..., LOOK>): the auxiliary particle filter's look-ahead factor (look_factor,
+// pf_look_reg.h = k_lookahead) enters the pilot weight here, behind the site likelihood and in front of the state stores and the wavefront
+// partials, so that the partials decide_row reads are those k_lookahead leaves.  The previous factor travels with the state: the slot's own
+// with the preload, the parent's on a resampling row.  A completion-only launch applies none and hands on the one it carried.
 __device__ __forceinline__ int pf_arrive(int v) { asm volatile("" : "+v"(v)); return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ long long pf_arrive(long long v) {
     asm volatile("" : "+v"(v));
@@ -116,9 +121,10 @@ __device__ __forceinline__ long long pf_arrive(long long v) {
 }
 __device__ __forceinline__ double pf_arrive(double v) { return __longlong_as_double(pf_arrive(__double_as_longlong(v))); }
 
-template <int NM, bool BIASED, bool EXACT = false, bool TREES = false, bool PIPE = false, bool HEAD = false, class KA>
+template <int NM, bool BIASED, bool EXACT = false, bool TREES = false, bool PIPE = false, bool HEAD = false, bool LOOK = false, class KA>
 __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fuse, PipeRow PR = PipeRow(), const SweepHeadR& H = SweepHeadR()) {
     static_assert(!HEAD || PIPE, "the row header belongs to the row pipeline");
+    static_assert(!LOOK || (PIPE && !HEAD && !BIASED && !TREES), "the look-ahead rides on the plain rows of k_sweep");
     extern __shared__ double smem[];
     int E_head; long long Np_head; int n_head;
     if constexpr (HEAD) { E_head = PF_HI(H, E); Np_head = PF_HL(H, Np); n_head = PF_HI(H, n); } else { E_head = A.E; Np_head = A.Np; n_head = A.n; }
@@ -139,6 +145,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
     RowPre pre;
     RTree<NM> t0;
     double o_wpost = 0.0, o_wpilot = 0.0, o_next = 0.0, o_xmark = 0.0, o_Ltree = 0.0, o_sm = 0.0, o_ebuf = 0.0;
+    [[maybe_unused]] double o_la = 1.0;
     int o_ml = 0;
     unsigned o_widx = 0;
     unsigned long long o_ctr = 0;
@@ -199,6 +206,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             }
             o_wpost = own.w_post[p]; o_wpilot = own.w_pilot[p]; o_next = own.next_base[p]; o_xmark = own.x_mark[p];
             o_ml = own.mark_limit[p]; o_Ltree = own.Ltree[p];
+            if constexpr (LOOK) o_la = own.lookahead[p];
             o_widx = PR.complete ? A.rg_widx[(size_t)fs * A.Np + p] : A.widx[p];
             o_ctr = A.rng_ctr[p]; o_ebuf = A.ebuf[p];
             if (PR.draws) o_tab_end = (unsigned)A.dt_filled[(size_t)((PR.draws - 1) ^ 1) * A.Np + p];
@@ -544,6 +552,8 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         } else {
             w_post = o_wpost; w_pilot = o_wpilot; next_base = o_next; x_mark = o_xmark; mark_limit = o_ml; cx.Ltree = o_Ltree;
         }
+        [[maybe_unused]] double la_prev = 1.0;
+        if constexpr (LOOK) la_prev = reload ? from.lookahead[a] : o_la;
         if constexpr (PIPE) { cx.ctr = o_ctr; cx.ebuf = o_ebuf; widx = o_widx; r_draws_prefetch(cx); }
         else { cx.ctr = A.rng_ctr[p]; cx.ebuf = A.ebuf[p]; widx = A.widx[p]; }
         if (completing) {
@@ -774,6 +784,18 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             lik *= norm;
             w_post *= lik;
             w_pilot *= lik;
+        }
+        if constexpr (LOOK) {
+            // removeLookaheadLikelihood + includeLookaheadLikelihood (particle.hpp:182, particle.cpp:614-616), as k_lookahead ends
+            double la_w = la_prev;
+            if (do_extend) {
+                const double likelihood = look_factor<NM>(A1, t, n, s, cx.Ltree);
+                w_pilot /= la_prev;
+                la_w = 1.0;
+                la_w *= likelihood;
+                w_pilot *= likelihood;
+            }
+            st1.lookahead[p] = la_w;
         }
 
         PF_STAMP(6);
@@ -2085,7 +2107,7 @@ __device__ __forceinline__ void pipe_count_item(const KA& A, const PipeLaunch& P
 }
 
 // (NO_EXTEND: the caller has run the extend role itself -- sweep_kernel_body with the row header)
-template <int NM, bool BIASED, bool EXACT, bool TREES, int P = 1, bool BLC = false, bool QUEUE = false, bool LEAN = false, bool NO_EXTEND = false, class KA>
+template <int NM, bool BIASED, bool EXACT, bool TREES, int P = 1, bool BLC = false, bool QUEUE = false, bool LEAN = false, bool NO_EXTEND = false, bool LOOK = false, class KA>
 __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeLaunch& PL, const Windows& Wb) {
     const int bx = pf_bx();
     const int nb = PL.nb;
@@ -2093,7 +2115,7 @@ __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeL
     // are what would keep it from four workgroups per compute unit)
     if constexpr (!LEAN) {
         if (bx < nb) {
-            if constexpr (P == 1 && !BLC && !NO_EXTEND) { if (PL.row.extend || PL.row.complete) extend_reg_body<NM, BIASED, EXACT, TREES, true>(A, s, 0, PL.row); }
+            if constexpr (P == 1 && !BLC && !NO_EXTEND) { if (PL.row.extend || PL.row.complete) extend_reg_body<NM, BIASED, EXACT, TREES, true, false, LOOK>(A, s, 0, PL.row); }
             return;
         }
         if (bx == nb) {
@@ -2205,7 +2227,7 @@ __device__ __forceinline__ unsigned long long* wg_trace_slot(SweepChunkC& ch, lo
 // pf_pipe.h): entry t & (PF_RING - 1), which lies in front of the chunk table at an address the kernel arguments give (sweep_head_of),
 // loaded in one batch -- two dependent scalar round trips in front of the first request where sweep_plan and the argument block had
 // ten.  The other roles plan as before.
-template <int NM, bool BIASED, bool EXACT, bool TREES, bool TRACE = false, bool QUEUE = false, bool HEAD = false>
+template <int NM, bool BIASED, bool EXACT, bool TREES, bool TRACE = false, bool QUEUE = false, bool HEAD = false, bool LOOK = false>
 __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long long t, int nb) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[pf_chunk()];
@@ -2245,7 +2267,7 @@ __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long 
         if (sweep_plan(ch, s, nb, PL)) {
             if (ch.split == 2) PL.nL = -3;                 // extend, bookkeeping and draw roles only: ledger and counts are k_sweep_blc's (run_sweep_split)
             if (pf_bx() == nb && PL.b_slot >= 0) sweep_windows(A, A.ctrl, PL.b_pos, W);
-            pipe_roles<NM, BIASED, EXACT, TREES, 1, false, QUEUE, false, HEAD>(A, s, PL, W);
+            pipe_roles<NM, BIASED, EXACT, TREES, 1, false, QUEUE, false, HEAD, LOOK>(A, s, PL, W);
         }
     }
     if constexpr (TRACE) {
@@ -2253,9 +2275,10 @@ __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long 
         if (threadIdx.x == 0) if (unsigned long long* w = wg_trace_slot(ch, t)) w[1] = wall_clock64();
     }
 }
-template <int NM, bool BIASED, bool EXACT, bool TREES>
+// (LOOK: with the look-ahead factor in the extend role -- pf_lookahead.flags bit 0; BIASED = TREES = false, NM 4 and 8)
+template <int NM, bool BIASED, bool EXACT, bool TREES, bool LOOK = false>
 __global__ __launch_bounds__(PF_BS) void k_sweep(const SweepChunk* tab_g, long long t, int nb) {
-    sweep_kernel_body<NM, BIASED, EXACT, TREES>(tab_g, t, nb);
+    sweep_kernel_body<NM, BIASED, EXACT, TREES, false, false, false, LOOK>(tab_g, t, nb);
 }
 // The headline instance (at most four haplotypes, no focused sampling) with the occupancy stated: three workgroups per compute
 // unit, i.e. at most 168 registers a thread -- several chunks per GPU lose 15 % with two.  Left to itself
@@ -2526,6 +2549,8 @@ __global__ __launch_bounds__(PF_BS) void k_calibrate(KArgs A, unsigned long long
 // the previous look-ahead factor leaves the pilot weight, the new one enters it.  Runs after k_extend (the pilot
 // weight is a product of the same factors in either order) and rewrites the pilot part of the per-wavefront
 // partials that k_decide consumes.  One population.
+// The same arithmetic on the register tree, inside the extend role of k_sweep<..., LOOK>, is look_factor (pf_look_reg.h): a fix to one of
+// them belongs in both; tests/test_gpu_lookahead_rows.py holds the two to the same bits.
 static size_t smem_bytes_la(int n, int E) { return smem_bytes(n, E) + (size_t)PF_BS * (2 * n * 8 + n * 4); }
 
 __global__ __launch_bounds__(PF_BS) void k_lookahead(KArgs A, long long row) {
