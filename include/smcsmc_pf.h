@@ -129,6 +129,7 @@ typedef struct pf_params {
                                   * and draw roles; the ledger and count roles on the counting stream, four workgroups to a compute unit
                                   * (run_sweep_split).  A/B, same bits */
 
+#define PF_DEBUG_NO_PAIR 4096     /* RunPath SweepSplit: the row kernel's one-wavefront form (k_sweep4) also where the paired form (k_sweep4p) would run (A/B) */
 #define PF_DEBUG_FORCE_WIDE 2048  /* one population: run the wide kernels of nsam > 16 (64-lane workgroups, 64-bit masks, the records' extra
                                    * descendant word, k_count<64>) whatever nsam is -- how that path is pinned against the oracle at n <= 16 */
 
@@ -184,6 +185,7 @@ typedef struct pf_handle pf_handle;
 
 const char* pf_last_error(void);
 int pf_device_count(void);
+int pf_device_cus(int device);     /* compute units of a device (0: unknown): what the choice of pf_get_row_form goes by */
 
 pf_handle* pf_create(const pf_model* model, const pf_params* params, int device);
 void pf_destroy(pf_handle* h);
@@ -264,6 +266,13 @@ int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 #define PF_PATH_SWEEP_XMP   5    /* k_sweep_xmp + k_sweep_blc: structured models, at most 8 haplotypes */
 #define PF_PATH_SWEEP_XL    6    /* k_sweep_xl + k_sweep_blc: one population, 9 to 16 haplotypes, pf_run_many only */
 int pf_get_run_path(pf_handle* h, int many);
+/* Which form of the row kernel the last pf_run / pf_run_many call ran for this handle's rows on PF_PATH_SWEEP_SPLIT: the paired form (a weight
+ * wavefront beside each tree wavefront, 128 particles a workgroup) runs when every extend workgroup of the call can have a compute unit of its
+ * own, chunks * ceil(np / 128) <= compute units, without vb_coal and PF_DEBUG_NO_PAIR.  Same bits either way (tests/test_gpu_pair_rows.py). */
+#define PF_ROW_FORM_NONE    0    /* no call yet, or a call on another path */
+#define PF_ROW_FORM_SINGLE  1    /* k_sweep4: tree and weights of a particle in one wavefront */
+#define PF_ROW_FORM_PAIRED  2    /* k_sweep4p */
+int pf_get_row_form(pf_handle* h);
 int pf_finish(pf_handle* h);
 int pf_sync(pf_handle* h);
 

@@ -91,3 +91,36 @@ ci = st_all[:, :, 8].argmax(axis=1)
 ct = trips[np.arange(len(ci)), ci]
 cl = (st_all[:, :, 5] - st_all[:, :, 4])[np.arange(len(ci)), ci]
 print("wavefront that ends the launch: %.2f trips, %.2f us in the loop; wavefront with most trips: %.2f" % (ct.mean(), cl.mean(), trips.max(axis=1).mean()))
+
+# The paired form of the row kernel (k_sweep4p, pf_pair.h): the words above are the TREE wavefronts' (stamp 8 there: the tree's stores are out);
+# the WEIGHT wavefront beside each leaves three stamps in words 29-31 and the pair's hardware ids share word 15 (tree low, weight high).
+wt = out[5:, :, 29:32].astype(np.int64) * 10.0 / 1000.0
+if wt.max() > 0:
+    print("paired form: the row ends with the weight wavefronts (row_form %s)" % f.row_form())
+    wrel = wt - t0[:, :, None]
+    wend = wrel[:, :, 2].max(axis=1)
+    print("   kernel span (first wave start -> last weight wave scans done): mean %.2f us" % wend.mean())
+    wn = ["offsets / old slot done", "last factor applied", "scans done"]
+    for sel, nm in ((np.ones(len(wend), bool), "all rows"), (selr, "rows after a resampling row"), (~selr, "rows after a plain row")):
+        print("  ", nm, int(sel.sum()))
+        for k in range(3):
+            col = wrel[sel][:, :, k]
+            print("      weight: %-24s mean over waves %6.2f   max over waves (mean over rows) %6.2f" % (wn[k], col.mean(), col.max(axis=1).mean()))
+        # the pair that ends the launch: the tree wavefront's phases beside its weight wavefront's
+        wi = wrel[sel][:, :, 2].argmax(axis=1)
+        tr = rel[sel][np.arange(len(wi)), wi, :]
+        wv = wrel[sel][np.arange(len(wi)), wi, :]
+        print("      last pair, tree phase durations:", " ".join("%.2f" % v for v in np.diff(tr, axis=1).mean(axis=0)), " start offset %.2f" % tr[:, 0].mean())
+        print("      last pair, weight: offsets done at %.2f, last factor at %.2f (tree's loop done at %.2f, site likelihood at %.2f), scans done at %.2f"
+              % (wv[:, 0].mean(), wv[:, 1].mean(), tr[:, 5].mean(), tr[:, 6].mean(), wv[:, 2].mean()))
+        print("      the weight wavefront holds up the tail by %.2f us (last factor applied behind the tree's site likelihood; negative: it waited)"
+              % (wv[:, 1] - tr[:, 6]).mean())
+    st0 = rel[:, :, 0]
+    print("   spread of `start` over wavefronts: mean %.2f us, max over waves (mean over rows) %.2f us" % (st0.mean(), st0.max(axis=1).mean()))
+    hw = out[5:, : (nc // 2) * 2, 15]
+    simd_t, simd_w = (hw >> np.uint64(4)) & np.uint64(3), (hw >> np.uint64(36)) & np.uint64(3)
+    cu_t, cu_w = hw & np.uint64(0xff00), (hw >> np.uint64(32)) & np.uint64(0xff00)
+    four = np.stack([simd_t[:, 0::2], simd_t[:, 1::2], simd_w[:, 0::2], simd_w[:, 1::2]], axis=-1)
+    distinct = np.array([[len(set(x)) == 4 for x in row] for row in four[:200]])
+    print("   SIMD placement (first 200 rows): workgroups whose four wavefronts sit on four SIMDs %.4f; tree and weight wavefront on one compute unit %.4f"
+          % (distinct.mean(), (cu_t == cu_w).mean()))

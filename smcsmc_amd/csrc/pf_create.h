@@ -255,7 +255,10 @@ static int create_allocate(pf_handle* h, const pf_model* m, const pf_params* p, 
         for (int k = 0; k <= A.n_bias && A.n_bias > 0; ++k) A.bias_S[k] = m->bias_strengths[k];
         rc |= h->mem.upload(&A.app_delays, m->application_delays, E, h->stream);
     }
-    A.blk_gran = h->rings == Rings::Xmp ? 4 : 1;
+    // one entry of rg_blkcnt per wavefront where the extend workgroups own fewer than 256 particles: the structured models (64), and the handles
+    // RunPath::SweepSplit takes (split_shape, pf_handle.h), whose paired form owns 128 -- whichever form of the row kernel then runs
+    const bool split = split_shape(h->rings == Rings::Reg, m->n_pops, n, m->n_bias_heights > 0 || m->n_rate_segments > 0, (p->flags & 2) != 0, p->debug);
+    A.blk_gran = (h->rings == Rings::Xmp || split) ? 4 : 1;
     {
         const size_t K = (size_t)pl.nslots;
         A.nslots = pl.nslots;

@@ -22,6 +22,7 @@ int pf_sync(pf_handle* h) {
         if (c.err == ERR_MP_INTERNAL) msg = "structured-model genealogy update: coalescence partners inconsistent";
         if (c.err == ERR_NO_COALESCENCE) msg = "No final coalescence event was sampled!";   /* particle.cpp:1383 */
         if (c.err == ERR_DELAY_OVERFLOW) msg = "delayed-factor store overflow (raise pf_params.delay_cap)";
+        if (c.err == ERR_PAIR_STALL) msg = "row kernel, paired form: a wavefront waited 0.1 s for its partner (PF_DEBUG_NO_PAIR runs the other form)";
         g_err = msg;
         return -2;
     }

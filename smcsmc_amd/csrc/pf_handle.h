@@ -6,6 +6,13 @@
 // switches and the look-ahead.  None: two copies of the state, the general kernels or k_row.  Reg: one population, n <= 8, tree in registers
 // (k_sweep*).  Xmp: two to four populations, n <= 8 (k_sweep_xmp).  Xl: one population, 9 <= n <= 16, tree in LDS (k_sweep_xl, pf_run_many only).
 enum class Rings { None, Reg, Xmp, Xl };
+// The shape RunPath::SweepSplit takes -- run_path (pf_run.h) asks here, and so does create_impl, which gives these handles one entry of rg_blkcnt
+// per wavefront: one population of at most four haplotypes on the rings of the row pipeline, no focused sampling or guide, no -arg, no switch
+// to another path.  (A look-ahead loaded later takes the handle off the path; every writer and reader of rg_blkcnt goes by KArgs::blk_gran.)
+static bool split_shape(bool reg_rings, int P, int n, bool biased, bool rec_trees, int debug) {
+    return reg_rings && P == 1 && n <= 4 && !biased && !rec_trees &&
+           !(debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_K_PIPE | PF_DEBUG_ONE_LAUNCH | PF_DEBUG_FORCE_WIDE));
+}
 
 struct pf_handle {
     int device = 0;
@@ -30,6 +37,8 @@ struct pf_handle {
     bool fin_pending = false;     // k_count partials not yet folded into the totals
     Windows step_windows;         // windows of the step being processed
     int la_flags = 0;             // pf_lookahead.flags of the look-ahead in force (PF_LA_ROW_PIPELINE; 0 without one)
+    bool pair_lds_set = false;    // the LDS limit of k_sweep4p has been raised for this handle's instance (run_sweep_split)
+    int row_form = 0;             // PF_ROW_FORM_*: what the last call ran (pf_get_row_form)
     int debug = 0;                // pf_params.debug: the PF_DEBUG_* switches that select a path are read from here (run_path)
     Rings rings = Rings::None;
     bool wide = false;            // one population on the wide kernels of pf_wide.hip: nsam > PF_NMAX, or PF_DEBUG_FORCE_WIDE (testing)
@@ -133,6 +142,17 @@ int pf_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
+}
+
+// compute units of a device (asked once; 0: unknown)
+int pf_device_cus(int device) {
+    static std::vector<int> cus;
+    static std::mutex mu;             // (handles on several devices may be driven from several threads)
+    if (device < 0) return 0;
+    std::lock_guard<std::mutex> lock(mu);
+    if ((int)cus.size() <= device) cus.resize((size_t)device + 1, 0);
+    if (cus[(size_t)device] == 0 && hipDeviceGetAttribute(&cus[(size_t)device], hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus[(size_t)device] = 0;
+    return cus[(size_t)device];
 }
 
 // per-epoch, per-population tables of a structured model (scrm Model::population_size / migration_rate /

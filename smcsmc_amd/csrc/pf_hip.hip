@@ -22,6 +22,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -68,6 +69,9 @@ __device__ __forceinline__ void pf_acc_trip(unsigned long long* a) { a[5] += 1; 
 #define PF_TICK(var) unsigned long long var = wall_clock64()
 #define PF_ACC(slot, t0, t1) pf_acc[slot] += (t1) - (t0)
 #define PF_ACC_DECL unsigned long long pf_acc[6] = {0, 0, 0, 0, 0, 0}, pf_acc2[8] = {0, 0, 0, 0, 0, 0, 0, 0}
+// (what row_update_trip takes of them)
+#define PF_ACC_PARAMS , unsigned long long* pf_acc, unsigned long long* pf_acc2, unsigned long long tk1
+#define PF_ACC_ARGS , pf_acc, pf_acc2, tk1
 // the finer split of a trip (words 21-28): [0] no-mutation weight up to the factor, [1] its two products, [2..7] the genealogy update
 // between the marks of PF_GTICK (pf_tree_reg.h): draws, cut point, descendant mask, node searches, walk and inverse, tree edit
 #define PF_ACC2(slot, t0, t1) pf_acc2[slot] += (t1) - (t0)
@@ -82,6 +86,8 @@ __device__ __forceinline__ void pf_acc_trip(unsigned long long* a) { a[5] += 1; 
 #define PF_ACC(slot, t0, t1) do {} while (0)
 #define PF_ACC2(slot, t0, t1) do {} while (0)
 #define PF_ACC_DECL do {} while (0)
+#define PF_ACC_PARAMS
+#define PF_ACC_ARGS
 #define PF_ACC_STORE do {} while (0)
 #endif
 
@@ -120,6 +126,388 @@ __device__ __forceinline__ long long pf_arrive(long long v) {
     return (long long)(((unsigned long long)hi << 32) | lo);
 }
 __device__ __forceinline__ double pf_arrive(double v) { return __longlong_as_double(pf_arrive(__double_as_longlong(v))); }
+
+// ---- parts of a row that extend_reg_body and the paired form of the row kernel (extend_pair_body, pf_pair.h) share ----
+// the window of pilot scans a workgroup requests ahead of the parent search: PF_PIPE_STAGE wavefronts centred on its own `own`, which
+// start at wavefront `first`
+__device__ __forceinline__ int row_spec_lo(int first, int own, int nc, int flags) {
+    int spec_lo = first - (PF_PIPE_STAGE - own) / 2;
+    if (spec_lo > nc - PF_PIPE_STAGE) spec_lo = nc - PF_PIPE_STAGE;
+    if (spec_lo < 0) spec_lo = 0;
+    if (flags & 256) spec_lo = -0x40000000;              // PF_DEBUG_NO_SPEC_STAGE (A/B): never covers the range
+    return spec_lo;
+}
+// parent search, first level: the wavefront the parent of a slot sits in (lhs = (p + u) * S1)
+__device__ __forceinline__ int row_parent_chunk(const PipeLds& q, int nc, double lhs, double dn) {
+    int lo_c = 0, hi_c = nc - 1;
+    while (lo_c < hi_c) {
+        int mid = (lo_c + hi_c) >> 1;
+        if (lhs < dn * q.pmx[mid + 1]) hi_c = mid; else lo_c = mid + 1;
+    }
+    return lo_c;
+}
+// parent search, second level: the parent a of slot p inside wavefront pch, from the staged scans where they cover it, and whether p
+// is a's first copy
+// (found(): called between the two, where the profiling build has a stamp)
+template <class KA, class MARK>
+__device__ __forceinline__ void row_parent_in_chunk(const KA& A, const PipeLds& q, const double* sm, int pch, int stage_lo, int nst, double lhs, double dn,
+                                                    long long p, const RowDecision& d, long long& a, bool& first_copy, MARK&& found) {
+    const double coff_p = pipe_chunk_offset(q, pch);
+    const double pm_p = q.pmx[pch];
+    const bool staged = pch >= stage_lo && pch - stage_lo < nst;
+    auto val_at = [&](int l) -> double {           // largest prefix sum up to particle pch*64 + l
+        long long idx = (long long)pch * 64 + l;
+        double smv = staged ? q.stage[(pch - stage_lo) * 64 + l] : (idx < A.Np ? sm[idx] : PF_INF);
+        double w = coff_p + smv;
+        return pm_p > w ? pm_p : w;
+    };
+    int lo_l = 0, hi_l = 63;
+    while (lo_l < hi_l) {
+        int mid = (lo_l + hi_l) >> 1;
+        if (lhs < dn * val_at(mid)) hi_l = mid; else lo_l = mid + 1;
+    }
+    a = (long long)pch * 64 + lo_l;
+    found();
+    if (a > A.Np - 1) a = A.Np - 1;
+    // slot p is the first copy of a (it keeps a's next recombination position) iff it equals a's offset
+    const int la = (int)(a & 63);
+    if (p == 0 || a == 0) first_copy = (p == 0);
+    else {
+        double vprev = la > 0 ? val_at(la - 1) : pm_p;      // largest prefix sum up to a - 1
+        if (a != (long long)pch * 64 + lo_l) {             // clamped: recompute on the true chunk of a - 1
+            long long am = a - 1;
+            int chm = (int)(am >> 6);
+            double w = pipe_chunk_offset(q, chm) + sm[am];
+            vprev = q.pmx[chm] > w ? q.pmx[chm] : w;
+        }
+        first_copy = ((((double)(p - 1)) + d.u) * d.S1 < dn * vprev);
+    }
+}
+// the record that closes the stretch of an old slot with offspring: everything but the heights
+__device__ __forceinline__ void row_close_record(double* rec, double x_mark, double pos, int mark_limit, int n) {
+    rec[0] = x_mark;
+    rec[1] = pos;
+    rec[2] = 0.0; rec[3] = 0.0;
+    rec[4] = __longlong_as_double((long long)make_meta(1, mark_limit, -1, n));
+}
+// the alleles of a row as masks over the haplotypes
+struct RowMasks { unsigned one = 0, zero = 0, present = 0, two = 0; int missing = 0; };
+template <int NM, class F>
+__device__ __forceinline__ RowMasks row_masks(int n, F&& allele) {
+    RowMasks m;
+#pragma unroll
+    for (int i = 0; i < NM; ++i) if (i < n) {
+        int d = allele(i);
+        m.missing += d == -1;
+        if (d == 1) m.one |= 1u << i;
+        if (d == 0) m.zero |= 1u << i;
+        if (d == 2) m.two |= 1u << i;
+        if (d >= 0) m.present |= 1u << i;
+    }
+    return m;
+}
+// the likelihood of a row's site under the tree, averaged over the phasings of its unphased pairs
+template <int NM>
+__device__ __forceinline__ double row_site_lik(const RTree<NM>& t, int n, double v_mu, unsigned one_mask, unsigned zero_mask, unsigned two_mask, bool dephase, bool anc) {
+    unsigned het_pairs = 0;
+    int ncfg = 1;
+    for (int i = 0; i + 1 < n; i += 2) {
+        bool d0_two = (two_mask >> i) & 1u;
+        bool one0 = (one_mask >> i) & 1u, one1 = (one_mask >> (i + 1)) & 1u;
+        bool zero0 = (zero_mask >> i) & 1u, zero1 = (zero_mask >> (i + 1)) & 1u;
+        bool het = d0_two || (dephase && ((one0 && zero1) || (zero0 && one1)));
+        if (het) {
+            ncfg *= 2;
+            het_pairs |= 1u << i;
+            one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
+            zero_mask |= 1u << i;
+            one_mask |= 1u << (i + 1);
+        }
+    }
+    double norm = 1.0 / (double)ncfg;
+    RBranchP<NM> bprob;
+    r_site_branch_probs(t, n, v_mu, bprob);     // once per row: the phasing configurations share them
+    double lik = 0;
+    for (;;) {
+        lik += r_site_lik_from(t, n, bprob, one_mask, zero_mask, anc);
+        if (ncfg == 1) break;
+        bool more = false;
+        for (int i = 0; i + 1 < n; i += 2) {
+            if (!((het_pairs >> i) & 1)) continue;
+            if ((zero_mask >> i) & 1) {
+                zero_mask &= ~(1u << i); one_mask |= 1u << i;
+                one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
+                more = true;
+                break;
+            }
+            one_mask &= ~(1u << i); zero_mask |= 1u << i;
+            zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
+        }
+        if (!more) break;
+    }
+    lik *= norm;
+    return lik;
+}
+// the five wavefront primitives behind the final weights of a row (the whole wavefront calls this), and where the row pipeline leaves them
+struct RowScans { double sc, sp, sq, scp, scm; };
+__device__ __forceinline__ RowScans row_scans(double w_post, double w_pilot, int lane) {
+    RowScans r;
+    r.sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
+    r.sp = wave_tree_sum(w_post);
+    r.sq = wave_tree_sum(w_pilot * w_pilot);
+    r.scp = wave_hs_scan(w_post, lane);
+    r.scm = wave_max_scan_d(r.sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
+    return r;
+}
+template <class KA>
+__device__ __forceinline__ void row_scans_store(const KA& A2, int cur, long long p, bool active, int lane, const RowScans& r) {
+    const long long chunk = p >> 6;
+    const size_t ro = (size_t)cur * A2.Np, co = (size_t)cur * A2.nc;
+    if (active) { A2.rg_scan1[ro + p] = r.sc; A2.rg_scanp[ro + p] = r.scp; A2.rg_scan1m[ro + p] = r.scm; }
+    if (p == A2.Np - 1) A2.ctrl->last1[cur] = r.sc;
+    if (lane == 63 && chunk < A2.nc) {
+        A2.rg_cpost[co + chunk] = r.sp;
+        A2.rg_csq[co + chunk] = r.sq;
+        A2.rg_cpil[co + chunk] = r.sc;
+        A2.rg_cpp[co + chunk] = r.scp;
+        A2.rg_cmx1[co + chunk] = r.scm;
+    }
+}
+
+// the head of a row of the headline row kernels, requests only: what the decision on the row before needs and the window of pilot scans
+// that starts at wavefront spec_lo
+template <class HR>
+__device__ __forceinline__ void row_head_decision(const HR& H, int nc, long long Np_head, int spec_lo, RowPre& pre, long long& o_nres, int& o_bflag, int& o_bgen,
+                                                  double (&spec_sm)[PF_PIPE_STAGE * 64 / PF_BS]) {
+    const int ch = threadIdx.x, perc = (nc + PF_BS - 1) / PF_BS;
+    pre.have = true;
+    if (ch < nc) { pre.vp = PF_HP(H, cpost)[ch]; pre.vs = PF_HP(H, csq)[ch]; pre.vl = PF_HP(H, cpil)[ch]; }
+    if (ch + PF_BS < nc) { pre.vp2 = PF_HP(H, cpost)[ch + PF_BS]; pre.vs2 = PF_HP(H, csq)[ch + PF_BS]; pre.vl2 = PF_HP(H, cpil)[ch + PF_BS]; }
+    // (the entry or the two entries of the prefix-maxima pass, row_preload; two plain guarded requests: behind an if / else chain
+    // the second one waited for everything before it)
+    const int cm = perc == 2 ? 2 * ch : ch;
+    if (perc <= 2 && cm < nc) pre.vm = PF_HP(H, cmx1)[cm];
+    if (perc == 2 && cm + 1 < nc) pre.vm2 = PF_HP(H, cmx1)[cm + 1];
+    pre.last1 = *PF_HP(H, last1);
+    asm volatile("" ::: "memory");
+    o_nres = PF_HP(H, xr_before)->n_res; o_bflag = PF_HP(H, xr_before)->flag; o_bgen = PF_HP(H, xr_before)->gen;
+    asm volatile("" ::: "memory");
+    // (the window of scans requested ahead of the parent search: as in the other form of the head)
+#pragma unroll
+    for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) {
+        const long long src = (long long)spec_lo * 64 + k * PF_BS + threadIdx.x;
+        spec_sm[k] = (src >= 0 && src < Np_head) ? PF_HP(H, scan1m)[src] : PF_INF;
+    }
+    asm volatile("" ::: "memory");
+}
+// ... the epoch tables and the bucket table, one entry a thread
+template <class HR>
+__device__ __forceinline__ void row_head_tables(const HR& H, int E_head, double& h_T, double& h_Hc, double& h_I, bool& use_lut, unsigned& h_lut) {
+    if ((int)threadIdx.x < E_head) { h_T = PF_HP(H, T)[threadIdx.x]; h_Hc = PF_HP(H, Hc)[threadIdx.x]; h_I = PF_HP(H, inv2N)[threadIdx.x]; }
+    use_lut = PF_HP(H, lut) != nullptr;
+    if (use_lut && threadIdx.x < 2 * PF_LUT_N / 4) h_lut = ((const __attribute__((address_space(1))) unsigned*)PF_HP(H, lut))[threadIdx.x];
+}
+// ... the end of the row before and the row's own segment
+template <int NM, bool EXACT, class HR>
+__device__ __forceinline__ void row_head_segment(const HR& H, long long s, int n, double& sgp_start, double& sgp_len, double& sg_start, double& sg_len, int& sg_limit, int& sg_state,
+                                                 int (&sg_allele)[NM]) {
+    // (requested whatever the step, from rows the call has: a flush step and the first step of a call use none of them, and a
+    // request under a condition is one more join at which the value would have to be in its final register)
+    {
+        const long long s_first = PF_HL(H, s_begin), s_last = PF_HL(H, s_last);
+        const long long sq = s <= s_last ? s : s_last, sb = s > s_first ? s - 1 : s_first;
+        sgp_start = PF_HP(H, seg_start)[sb]; sgp_len = PF_HP(H, seg_len)[sb];
+        sg_start = PF_HP(H, seg_start)[sq]; sg_len = PF_HP(H, seg_len)[sq];
+        sg_limit = PF_HP(H, seg_limit)[sq]; sg_state = ((const __attribute__((address_space(1))) unsigned char*)PF_HP(H, seg_state))[sq];
+        // (as loaded, all four in one word where there are four: sign-extended where they arrive)
+        if constexpr (EXACT && NM == 4) sg_allele[0] = (int)*(const __attribute__((address_space(1))) unsigned*)(PF_HP(H, seg_alleles) + (size_t)sq * 4);
+        else {
+#pragma unroll
+            for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = ((const __attribute__((address_space(1))) unsigned char*)PF_HP(H, seg_alleles))[(size_t)sq * n + i];
+        }
+    }
+}
+// the row's segment where it is first used: in scalar registers, the bytes sign-extended (a flush step has none)
+template <int NM, bool EXACT>
+__device__ __forceinline__ void row_segment_arrive(bool do_extend, int n, double& sg_start, double& sg_len, int& sg_limit, int& sg_state, int (&sg_allele)[NM]) {
+    if (!do_extend) {
+        sg_start = 0.0; sg_len = 0.0; sg_limit = 0; sg_state = 1;
+#pragma unroll
+        for (int i = 0; i < NM; ++i) sg_allele[i] = 0;
+    } else {
+        sg_start = pf_arrive(sg_start); sg_len = pf_arrive(sg_len); sg_limit = pf_arrive(sg_limit); sg_state = (int)(int8_t)pf_arrive(sg_state);
+        if constexpr (EXACT && NM == 4) {
+            const unsigned w = (unsigned)pf_arrive(sg_allele[0]);
+#pragma unroll
+            for (int i = 0; i < NM; ++i) sg_allele[i] = (int)(int8_t)(w >> (8 * i));
+        } else {
+#pragma unroll
+            for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = (int)(int8_t)pf_arrive(sg_allele[i]);
+        }
+    }
+}
+// The wavefronts the parents of a workgroup's slots sit in, from what its NW searching wavefronts left in q.wint, and their pilot scans in q.stage:
+// the window requested with the head where it covers them, staged now otherwise.  Every thread of the workgroup calls this (barriers).
+template <int NW, class KA>
+__device__ __forceinline__ void row_stage_parents(const KA& A, const PipeLds& q, const double* sm, int spec_lo, int& stage_lo, int& nst) {
+    int cmin = q.wint[0], cmax = q.wint[PF_BS / 64];
+    for (int w = 1; w < NW; ++w) {
+        cmin = q.wint[w] < cmin ? q.wint[w] : cmin;
+        cmax = q.wint[PF_BS / 64 + w] > cmax ? q.wint[PF_BS / 64 + w] : cmax;
+    }
+    nst = cmax - cmin + 1;
+    if (nst > PF_PIPE_STAGE) nst = PF_PIPE_STAGE;
+    if (nst < 0) nst = 0;
+    stage_lo = cmin;
+    if (cmin >= spec_lo && cmax < spec_lo + PF_PIPE_STAGE) {
+        stage_lo = spec_lo; nst = PF_PIPE_STAGE;       // the scans requested with the prologue cover the range
+    } else {
+        __syncthreads();                               // everybody has read the range before the buffer is refilled
+        for (int idx = threadIdx.x; idx < nst * 64; idx += PF_BS) {
+            long long src = (long long)cmin * 64 + idx;
+            q.stage[idx] = src < A.Np ? sm[src] : PF_INF;
+        }
+    }
+    __syncthreads();
+}
+
+// the state a row of the headline row kernels continues from: ring slot slot_prev (the pointers of the row header), or on the first step of a
+// call the slot Ctrl::cur names, and then the handle's own record counters
+struct RowHeadPtrs {
+    const __attribute__((address_space(1))) double* S; const __attribute__((address_space(1))) int8_t* C;
+    const __attribute__((address_space(1))) double* w_post; const __attribute__((address_space(1))) double* w_pilot;
+    const __attribute__((address_space(1))) double* next_base; const __attribute__((address_space(1))) double* x_mark;
+    const __attribute__((address_space(1))) int* mark_limit; const __attribute__((address_space(1))) double* Ltree;
+    const __attribute__((address_space(1))) unsigned* widx;
+};
+template <class HR>
+__device__ __forceinline__ RowHeadPtrs row_head_ptrs(const HR& H, bool complete, long long Np_head, int n_head) {
+    RowHeadPtrs r;
+    r.S = PF_HP(H, S); r.C = PF_HP(H, C); r.w_post = PF_HP(H, w_post); r.w_pilot = PF_HP(H, w_pilot);
+    r.next_base = PF_HP(H, next_base); r.x_mark = PF_HP(H, x_mark); r.mark_limit = PF_HP(H, mark_limit); r.Ltree = PF_HP(H, Ltree);
+    r.widx = PF_HP(H, rg_widx);
+    if (!complete) {
+        const long long dk = (long long)__builtin_amdgcn_readfirstlane(PF_HP(H, ctrl)->cur) - PF_HI(H, slot_prev), dN = dk * Np_head, n1 = n_head - 1;
+        r.S += dN * n1; r.C += dN * 2 * n1; r.w_post += dN; r.w_pilot += dN; r.next_base += dN; r.x_mark += dN; r.mark_limit += dN; r.Ltree += dN;
+        r.widx = PF_HP(H, widx);
+    }
+    return r;
+}
+// weights of a copy (pc.cpp:350-351)
+__device__ __forceinline__ void row_copy_weights(double& w_post, double& w_pilot, double inv, double S1v, double dn) {
+    double wp = w_post * inv;
+    double wq = w_pilot * inv;
+    double sumn = S1v * inv;
+    double adj = sumn / (dn * wq);
+    w_post = wp * adj;
+    w_pilot = wq * adj;
+}
+// the stores of a row's end, but for the weights: the tree, ...
+template <int NM>
+__device__ __forceinline__ void row_store_tree(const DState& st1, size_t Np, long long p, int n, const RTree<NM>& t) {
+#pragma unroll
+    for (int r = 0; r < RTree<NM>::NI; ++r)
+        if (r < n - 1) {
+            st1.S[(size_t)r * Np + p] = t.S[r];
+            st1.C[(size_t)(2 * r) * Np + p] = (int8_t)t.C0[r];
+            st1.C[(size_t)(2 * r + 1) * Np + p] = (int8_t)t.C1[r];
+        }
+}
+// ... what the chain carries from row to row, ...
+template <class KA>
+__device__ __forceinline__ void row_store_chain(const KA& A1, const DState& st1, long long p, double next_base, double x_mark, int mark_limit, const RCtx& cx) {
+    st1.next_base[p] = next_base;
+    st1.x_mark[p] = x_mark;
+    st1.mark_limit[p] = mark_limit;
+    st1.Ltree[p] = cx.Ltree;
+    A1.rng_ctr[p] = cx.ctr;
+    A1.ebuf[p] = cx.ebuf;
+}
+// ... and the counters of the row pipeline
+template <class KA>
+__device__ __forceinline__ void row_store_counters(const KA& A1, const PipeRow& PR, int cur, long long p, unsigned long long ctr, unsigned widx, bool do_extend) {
+    if (PR.draws) A1.dt_ctr[(size_t)(PR.draws - 1) * A1.Np + p] = ctr;      // where the next row's draws start
+    A1.rg_widx[(size_t)cur * A1.Np + p] = widx;
+    if (!do_extend) A1.widx[p] = widx;              // the state goes back to the general kernels
+    if (PR.ahead) {
+        // running ahead of the counts: what they check of the ring (records appended as of the row they count) cannot see
+        // this row's writes, so the writer checks them itself against the oldest generation any pending count can ask for
+        const unsigned kold = A1.gstart[(size_t)(A1.ctrl->g_safe % A1.Gcap) * A1.Np + p];
+        if (widx - kold > A1.cap && !A1.ctrl->err) A1.ctrl->err = ERR_LOG_OVERFLOW;
+    }
+}
+// the per-lane context of the update loop, but for the position in the recombination guide
+template <bool BIASED, bool TREES, bool PIPE, class KA>
+__device__ __forceinline__ void row_ctx(RCtx& cx, const KA& A, const double* sT, const double* sI, const double* sH, const double* sBH, const double* sBS, int n, long long p,
+                                        double v_L, double v_mu, double v_rho, bool use_lut, const unsigned* s_lut, int draws, unsigned o_tab_end) {
+    cx.T = sT; cx.I = sI; cx.H = sH; cx.E = A.E; cx.n = n; cx.L = v_L; cx.mu = v_mu; cx.rho = v_rho;
+    cx.seed = in_vgpr(A.seed); cx.slot = (unsigned)p; cx.stream = 0;
+    cx.nb = A.n_bias + 1; cx.bH = sBH; cx.bS = sBS; cx.last_iw = 1.0;
+    cx.want_desc = A.lmap_opp != nullptr || TREES; cx.want_desc_new = TREES; cx.last_desc = 0; cx.last_desc_new = 0;
+    cx.vbc = A.vb_coal; cx.upd_fac = 1.0;
+    cx.gK = BIASED ? A.g_K : 0; cx.gpos = A.g_pos; cx.grho = A.g_rho; cx.gleaf = A.g_leaf; cx.last_rbiw = 1.0;
+    cx.ridx = 0; cx.g_rp = 0; cx.g_sb = 0;
+    if constexpr (PIPE) {
+        cx.lutT = use_lut ? (const unsigned char*)s_lut : nullptr;
+        cx.lutH = use_lut ? (const unsigned char*)s_lut + PF_LUT_N : nullptr;
+        cx.kbT = A.lut_kbT; cx.kbH = A.lut_kbH;
+        cx.tab = nullptr; cx.tab_end = 0; cx.pf_ok = false; cx.pf_ctr = 0; cx.draws_log = false;
+        if (draws) {
+            cx.tab = (const double2*)A.dt_tab + (size_t)p * PF_DRAW_RING;
+            cx.tab_end = o_tab_end;
+        }
+    }
+}
+
+// one trip of the update loop behind the move to updated_to < extend_to: the record of the stretch that ends there, the genealogy update, the
+// tracked length and the next recombination position (w_post, w_pilot: only vb_coal and focused sampling touch them)
+template <int NM, bool BIASED, bool EXACT, bool TREES, bool PIPE, class KA>
+__device__ __forceinline__ void row_update_trip(const KA& A, RCtx& cx, RTree<NM>& t, DStore& ds, long long p, int n, int limit, int leaf_status, unsigned present_mask,
+                                                double updated_to, unsigned& widx, double& x_mark, int& mark_limit, double& next_base, double& B,
+                                                double& w_post, double& w_pilot, const double* sBH, const double* sBS PF_ACC_PARAMS) {
+    double* rec = rec_ptr(A, p, widx);
+    rec[0] = x_mark;
+    rec[1] = updated_to;
+#pragma unroll
+    for (int r = 0; r < RTree<NM>::NI; ++r) if (r < n - 1) rec[5 + r] = t.S[r];
+    double h, tc;
+    PF_TICK(tk2);
+    PF_ACC(1, tk1, tk2);
+    r_genealogy_update<NM, BIASED, PIPE, PIPE && EXACT && NM == 4 && !BIASED && !TREES>(cx, t, &h, &tc);
+    PF_TICK(tk3);
+    PF_ACC(2, tk2, tk3);
+#ifdef PF_STAMPS
+    PF_ACC2(2, tk2, cx.gt[0]);
+    for (int k_ = 0; k_ < 5; ++k_) PF_ACC2(3 + k_, cx.gt[k_], cx.gt[k_ + 1]);
+#endif
+    if (cx.vbc) { w_post *= cx.upd_fac; w_pilot *= cx.upd_fac; cx.upd_fac = 1.0; }
+    rec[2] = h;
+    rec[3] = tc;
+    rec[4] = __longlong_as_double((long long)make_meta(0, mark_limit, limit, n, cx.last_desc, TREES ? cx.last_desc_new : 0u));
+    ++widx;
+    if (leaf_status == 0) B = r_tracked_len(t, n, present_mask);
+    if (leaf_status == 1) B = cx.Ltree;
+    PF_TICK(tk4);
+    PF_ACC(3, tk3, tk4);
+    pf_acc_trip(pf_acc);
+    if (BIASED) {
+        // particle.cpp:866-891: immediate vs delayed application of the importance weight
+        double iw = cx.last_iw, rbiw = cx.last_rbiw;
+        double delay_height = (A.delay_type & 3) == 0 ? h : tc;
+        int idx = 0;
+        while (idx + 1 < cx.nb + 1 && sBH[idx + 1] < delay_height) ++idx;
+        if (idx >= cx.nb) idx = cx.nb - 1;
+        if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
+        double delay = A.app_delays[r_epoch_of(cx, delay_height)];
+        d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+    }
+    PF_TICK(tk5);
+    next_base = r_sample_next_base<true, PIPE>(cx, updated_to);      // fourth uniform of the update
+    x_mark = updated_to;
+    mark_limit = limit;
+    PF_TICK(tk6);
+    PF_ACC(4, tk5, tk6);
+}
 
 template <int NM, bool BIASED, bool EXACT = false, bool TREES = false, bool PIPE = false, bool HEAD = false, bool LOOK = false, class KA>
 __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fuse, PipeRow PR = PipeRow(), const SweepHeadR& H = SweepHeadR()) {
@@ -182,10 +570,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             // of this workgroup's own wavefronts and six on either side are requested now, with everything else the prologue
             // reads, instead of in a round trip of their own once the search knows the range; a range outside this window
             // is staged the old way.
-            spec_lo = pf_bx() * (PF_BS / 64) - (PF_PIPE_STAGE - PF_BS / 64) / 2;
-            if (spec_lo > A.nc - PF_PIPE_STAGE) spec_lo = A.nc - PF_PIPE_STAGE;
-            if (spec_lo < 0) spec_lo = 0;
-            if (A.flags & 256) spec_lo = -0x40000000;              // PF_DEBUG_NO_SPEC_STAGE (A/B): never covers the range
+            spec_lo = row_spec_lo(pf_bx() * (PF_BS / 64), PF_BS / 64, A.nc, A.flags);
             const double* sm0 = A.rg_scan1m + (size_t)fs * A.Np;
 #pragma unroll
             for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) {
@@ -221,39 +606,12 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         static_assert(PF_EPAD <= PF_BS && 2 * PF_LUT_N / 4 <= PF_BS && !BIASED, "one table entry a thread");
         const int nc = PF_HI(H, nc);
         // the state the row continues from: ring slot slot_prev, or on the first step of a call the slot Ctrl::cur names
-        auto pS = PF_HP(H, S); auto pC = PF_HP(H, C); auto pwpost = PF_HP(H, w_post); auto pwpil = PF_HP(H, w_pilot);
-        auto pnext = PF_HP(H, next_base); auto pxm = PF_HP(H, x_mark); auto pml = PF_HP(H, mark_limit); auto pLt = PF_HP(H, Ltree);
-        auto pwidx = PF_HP(H, rg_widx);
-        if (!PR.complete) {
-            const long long dk = (long long)__builtin_amdgcn_readfirstlane(PF_HP(H, ctrl)->cur) - PF_HI(H, slot_prev), dN = dk * Np_head, n1 = n_head - 1;
-            pS += dN * n1; pC += dN * 2 * n1; pwpost += dN; pwpil += dN; pnext += dN; pxm += dN; pml += dN; pLt += dN;
-            pwidx = PF_HP(H, widx);
-        }
+        const RowHeadPtrs hp = row_head_ptrs(H, PR.complete != 0, Np_head, n_head);
+        const auto pS = hp.S; const auto pC = hp.C; const auto pwpost = hp.w_post; const auto pwpil = hp.w_pilot;
+        const auto pnext = hp.next_base; const auto pxm = hp.x_mark; const auto pml = hp.mark_limit; const auto pLt = hp.Ltree; const auto pwidx = hp.widx;
         if (PR.complete) {
-            const int ch = threadIdx.x, perc = (nc + PF_BS - 1) / PF_BS;
-            pre.have = true;
-            if (ch < nc) { pre.vp = PF_HP(H, cpost)[ch]; pre.vs = PF_HP(H, csq)[ch]; pre.vl = PF_HP(H, cpil)[ch]; }
-            if (ch + PF_BS < nc) { pre.vp2 = PF_HP(H, cpost)[ch + PF_BS]; pre.vs2 = PF_HP(H, csq)[ch + PF_BS]; pre.vl2 = PF_HP(H, cpil)[ch + PF_BS]; }
-            // (the entry or the two entries of the prefix-maxima pass, row_preload; two plain guarded requests: behind an if / else chain
-            // the second one waited for everything before it)
-            const int cm = perc == 2 ? 2 * ch : ch;
-            if (perc <= 2 && cm < nc) pre.vm = PF_HP(H, cmx1)[cm];
-            if (perc == 2 && cm + 1 < nc) pre.vm2 = PF_HP(H, cmx1)[cm + 1];
-            pre.last1 = *PF_HP(H, last1);
-            asm volatile("" ::: "memory");
-            o_nres = PF_HP(H, xr_before)->n_res; o_bflag = PF_HP(H, xr_before)->flag; o_bgen = PF_HP(H, xr_before)->gen;
-            asm volatile("" ::: "memory");
-            // (the window of scans requested ahead of the parent search: as in the other form of the head above)
-            spec_lo = pf_bx() * (PF_BS / 64) - (PF_PIPE_STAGE - PF_BS / 64) / 2;
-            if (spec_lo > nc - PF_PIPE_STAGE) spec_lo = nc - PF_PIPE_STAGE;
-            if (spec_lo < 0) spec_lo = 0;
-            if (PF_HI(H, flags) & 256) spec_lo = -0x40000000;              // PF_DEBUG_NO_SPEC_STAGE
-#pragma unroll
-            for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) {
-                const long long src = (long long)spec_lo * 64 + k * PF_BS + threadIdx.x;
-                spec_sm[k] = (src >= 0 && src < Np_head) ? PF_HP(H, scan1m)[src] : PF_INF;
-            }
-            asm volatile("" ::: "memory");
+            spec_lo = row_spec_lo(pf_bx() * (PF_BS / 64), PF_BS / 64, nc, PF_HI(H, flags));
+            row_head_decision(H, nc, Np_head, spec_lo, pre, o_nres, o_bflag, o_bgen, spec_sm);
         }
         // (every lane asks, the lanes behind the last particle for the last particle's and use nothing of it: requests under a lane
         // condition come out with the widening of the bytes, and a wait, right behind them)
@@ -277,25 +635,9 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             o_sm = PF_HP(H, scan1m)[q];
         }
         asm volatile("" ::: "memory");
-        if ((int)threadIdx.x < E_head) { h_T = PF_HP(H, T)[threadIdx.x]; h_Hc = PF_HP(H, Hc)[threadIdx.x]; h_I = PF_HP(H, inv2N)[threadIdx.x]; }
-        use_lut = PF_HP(H, lut) != nullptr;
-        if (use_lut && threadIdx.x < 2 * PF_LUT_N / 4) h_lut = ((const __attribute__((address_space(1))) unsigned*)PF_HP(H, lut))[threadIdx.x];
+        row_head_tables(H, E_head, h_T, h_Hc, h_I, use_lut, h_lut);
         asm volatile("" ::: "memory");
-        // (requested whatever the step, from rows the call has: a flush step and the first step of a call use none of them, and a
-        // request under a condition is one more join at which the value would have to be in its final register)
-        {
-            const long long s_first = PF_HL(H, s_begin), s_last = PF_HL(H, s_last);
-            const long long sq = s <= s_last ? s : s_last, sb = s > s_first ? s - 1 : s_first;
-            sgp_start = PF_HP(H, seg_start)[sb]; sgp_len = PF_HP(H, seg_len)[sb];
-            sg_start = PF_HP(H, seg_start)[sq]; sg_len = PF_HP(H, seg_len)[sq];
-            sg_limit = PF_HP(H, seg_limit)[sq]; sg_state = ((const __attribute__((address_space(1))) unsigned char*)PF_HP(H, seg_state))[sq];
-            // (as loaded, all four in one word where there are four: sign-extended where they arrive)
-            if constexpr (EXACT && NM == 4) sg_allele[0] = (int)*(const __attribute__((address_space(1))) unsigned*)(PF_HP(H, seg_alleles) + (size_t)sq * 4);
-            else {
-#pragma unroll
-                for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = ((const __attribute__((address_space(1))) unsigned char*)PF_HP(H, seg_alleles))[(size_t)sq * n + i];
-            }
-        }
+        row_head_segment<NM, EXACT>(H, s, n, sgp_start, sgp_len, sg_start, sg_len, sg_limit, sg_state, sg_allele);
         asm volatile("" ::: "memory");
     } else {
         for (int e = threadIdx.x; e < PF_EPAD; e += blockDim.x) {
@@ -364,14 +706,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
                 // ---- parent of slot p: the first particle a with (p+u) * S1 < N * (largest prefix sum up to a) ----
                 const double lhs = ((double)p + d.u) * d.S1;
                 int pch = 0;
-                if (active) {
-                    int lo_c = 0, hi_c = A.nc - 1;
-                    while (lo_c < hi_c) {
-                        int mid = (lo_c + hi_c) >> 1;
-                        if (lhs < dn * q.pmx[mid + 1]) hi_c = mid; else lo_c = mid + 1;
-                    }
-                    pch = lo_c;
-                }
+                if (active) pch = row_parent_chunk(q, A.nc, lhs, dn);
                 PF_STAMP(17);
                 int cmin = active ? pch : 0x7fffffff, cmax = active ? pch : -1;
                 wave_minmax(cmin, cmax);
@@ -382,68 +717,25 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
                     if (threadIdx.x > 0) lo_p = q.slo[threadIdx.x - 1];
                     else lo_p = p > 0 ? pipe_lo_from(q.pmx[ch_own], dn, A.Np, d.S1, invS1, d.u) : 0;
                 }
-                cmin = q.wint[0]; cmax = q.wint[PF_BS / 64];
-                for (int w = 1; w < PF_BS / 64; ++w) {
-                    cmin = q.wint[w] < cmin ? q.wint[w] : cmin;
-                    cmax = q.wint[PF_BS / 64 + w] > cmax ? q.wint[PF_BS / 64 + w] : cmax;
-                }
                 // survivors of this workgroup (the ledger positions the run list of the ending generation with them)
                 {
                     unsigned long long bal = __ballot(active && lo_p1 > lo_p);
-                    if (lane == 0) q.wint[2 * (PF_BS / 64) + wave] = __popcll(bal);
-                }
-                PF_STAMP(18);
-                int nst = cmax - cmin + 1;
-                if (nst > PF_PIPE_STAGE) nst = PF_PIPE_STAGE;
-                if (nst < 0) nst = 0;
-                int stage_lo = cmin;
-                if (cmin >= spec_lo && cmax < spec_lo + PF_PIPE_STAGE) {
-                    stage_lo = spec_lo; nst = PF_PIPE_STAGE;       // the scans requested with the prologue cover the range
-                } else {
-                    __syncthreads();                               // everybody has read the range before the buffer is refilled
-                    for (int idx = threadIdx.x; idx < nst * 64; idx += PF_BS) {
-                        long long src = (long long)cmin * 64 + idx;
-                        q.stage[idx] = src < A.Np ? sm[src] : PF_INF;
+                    if (lane == 0) {
+                        if (A.blk_gran == PF_BS / 64) A.rg_blkcnt[((size_t)row_slot * gridDim_particles(A) + pf_bx()) * (PF_BS / 64) + wave] = __popcll(bal);
+                        else q.wint[2 * (PF_BS / 64) + wave] = __popcll(bal);
                     }
                 }
-                __syncthreads();
+                PF_STAMP(18);
+                int stage_lo, nst;
+                row_stage_parents<PF_BS / 64>(A, q, sm, spec_lo, stage_lo, nst);
                 PF_STAMP(19);
-                if (threadIdx.x == 0) {
+                if (threadIdx.x == 0 && A.blk_gran != PF_BS / 64) {      // (one entry a wavefront: written with the ballot above)
                     int tot = 0;
                     for (int w = 0; w < PF_BS / 64; ++w) tot += q.wint[2 * (PF_BS / 64) + w];
                     A.rg_blkcnt[(size_t)row_slot * gridDim_particles(A) * A.blk_gran + pf_bx()] = tot;
                 }
                 if (active) {
-                    const double coff_p = pipe_chunk_offset(q, pch);
-                    const double pm_p = q.pmx[pch];
-                    const bool staged = pch >= stage_lo && pch - stage_lo < nst;
-                    auto val_at = [&](int l) -> double {           // largest prefix sum up to particle pch*64 + l
-                        long long idx = (long long)pch * 64 + l;
-                        double smv = staged ? q.stage[(pch - stage_lo) * 64 + l] : (idx < A.Np ? sm[idx] : PF_INF);
-                        double w = coff_p + smv;
-                        return pm_p > w ? pm_p : w;
-                    };
-                    int lo_l = 0, hi_l = 63;
-                    while (lo_l < hi_l) {
-                        int mid = (lo_l + hi_l) >> 1;
-                        if (lhs < dn * val_at(mid)) hi_l = mid; else lo_l = mid + 1;
-                    }
-                    a = (long long)pch * 64 + lo_l;
-                    PF_STAMP(20);
-                    if (a > A.Np - 1) a = A.Np - 1;
-                    // slot p is the first copy of a (it keeps a's next recombination position) iff it equals a's offset
-                    const int la = (int)(a & 63);
-                    if (p == 0 || a == 0) first_copy = (p == 0);
-                    else {
-                        double vprev = la > 0 ? val_at(la - 1) : pm_p;      // largest prefix sum up to a - 1
-                        if (a != (long long)pch * 64 + lo_l) {             // clamped: recompute on the true chunk of a - 1
-                            long long am = a - 1;
-                            int chm = (int)(am >> 6);
-                            double w = pipe_chunk_offset(q, chm) + sm[am];
-                            vprev = q.pmx[chm] > w ? q.pmx[chm] : w;
-                        }
-                        first_copy = ((((double)(p - 1)) + d.u) * d.S1 < dn * vprev);
-                    }
+                    row_parent_in_chunk(A, q, sm, pch, stage_lo, nst, lhs, dn, p, d, a, first_copy, [&]() { PF_STAMP(20); });
                     // the offspring table of the generation that ends here, for the ledger (launch s + 1) and -arg
                     int* lo_tab = A.lo + (size_t)(G_end % A.Gcap) * (A.Np + 1);
                     lo_tab[p] = lo_p;
@@ -510,23 +802,8 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         }
         RCtx cx;
         const double v_L = in_vgpr(A.L), v_mu = in_vgpr(A.mu), v_rho = in_vgpr(A.rho);
-        cx.T = sT; cx.I = sI; cx.H = sH; cx.E = A.E; cx.n = n; cx.L = v_L; cx.mu = v_mu; cx.rho = v_rho;
-        cx.seed = in_vgpr(A.seed); cx.slot = (unsigned)p; cx.stream = 0;
-        cx.nb = A.n_bias + 1; cx.bH = sBH; cx.bS = sBS; cx.last_iw = 1.0;
-        cx.want_desc = A.lmap_opp != nullptr || TREES; cx.want_desc_new = TREES; cx.last_desc = 0; cx.last_desc_new = 0;
-        cx.vbc = A.vb_coal; cx.upd_fac = 1.0;
-        cx.gK = BIASED ? A.g_K : 0; cx.gpos = A.g_pos; cx.grho = A.g_rho; cx.gleaf = A.g_leaf; cx.last_rbiw = 1.0;
-        cx.ridx = cx.gK > 0 ? from.ridx[a] : 0; cx.g_rp = 0; cx.g_sb = 0;
-        if constexpr (PIPE) {
-            cx.lutT = use_lut ? (const unsigned char*)s_lut : nullptr;
-            cx.lutH = use_lut ? (const unsigned char*)s_lut + PF_LUT_N : nullptr;
-            cx.kbT = A.lut_kbT; cx.kbH = A.lut_kbH;
-            cx.tab = nullptr; cx.tab_end = 0; cx.pf_ok = false; cx.pf_ctr = 0; cx.draws_log = false;
-            if (PR.draws) {
-                cx.tab = (const double2*)A.dt_tab + (size_t)p * PF_DRAW_RING;
-                cx.tab_end = o_tab_end;
-            }
-        }
+        row_ctx<BIASED, TREES, PIPE>(cx, A, sT, sI, sH, sBH, sBS, n, p, v_L, v_mu, v_rho, use_lut, s_lut, PR.draws, o_tab_end);
+        cx.ridx = cx.gK > 0 ? from.ridx[a] : 0;
         DStore ds;
         if (BIASED) {
             d_bind(ds, A, st, p);
@@ -568,10 +845,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
                 // role of the old slot p: close its stretch if it has offspring
                 if (lo_p1 > lo_p) {
                     double* rec = rec_ptr(A, p, widx);
-                    rec[0] = PIPE ? o_xmark : src.x_mark[p];
-                    rec[1] = pos;
-                    rec[2] = 0.0; rec[3] = 0.0;
-                    rec[4] = __longlong_as_double((long long)make_meta(1, PIPE ? o_ml : src.mark_limit[p], -1, n));
+                    row_close_record(rec, PIPE ? o_xmark : src.x_mark[p], pos, PIPE ? o_ml : src.mark_limit[p], n);
                     if constexpr (PIPE) {
 #pragma unroll
                         for (int r = 0; r < RTree<NM>::NI; ++r) if (r < n - 1) rec[5 + r] = t0.S[r];
@@ -583,12 +857,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
                 A.gstart[(size_t)((G + 1) % A.Gcap) * A.Np + p] = widx;
                 // role of the new slot p: weights of the copy (pc.cpp:350-351), fresh position for all but the first
                 if (ev < A.max_trace_events) A.ev_parents[(size_t)ev * A.Np + p] = (int)a;
-                double wp = w_post * inv;
-                double wq = w_pilot * inv;
-                double sumn = S1v * inv;
-                double adj = sumn / ((double)A.Np * wq);
-                w_post = wp * adj;
-                w_pilot = wq * adj;
+                row_copy_weights(w_post, w_pilot, inv, S1v, (double)A.Np);
                 x_mark = pos;
                 if (!first_copy && pos < v_L) {
                     next_base = r_sample_next_base<false>(cx, pos);     // pc.cpp:357-368
@@ -600,21 +869,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         PF_STAMP(4);
         const bool do_extend = !PIPE || PR.extend != 0;
         if constexpr (HEAD) {
-            if (!do_extend) {
-                sg_start = 0.0; sg_len = 0.0; sg_limit = 0; sg_state = 1;
-#pragma unroll
-                for (int i = 0; i < NM; ++i) sg_allele[i] = 0;
-            } else {
-                sg_start = pf_arrive(sg_start); sg_len = pf_arrive(sg_len); sg_limit = pf_arrive(sg_limit); sg_state = (int)(int8_t)pf_arrive(sg_state);
-                if constexpr (EXACT && NM == 4) {
-                    const unsigned w = (unsigned)pf_arrive(sg_allele[0]);
-#pragma unroll
-                    for (int i = 0; i < NM; ++i) sg_allele[i] = (int)(int8_t)(w >> (8 * i));
-                } else {
-#pragma unroll
-                    for (int i = 0; i < NM; ++i) if (i < n) sg_allele[i] = (int)(int8_t)pf_arrive(sg_allele[i]);
-                }
-            }
+            row_segment_arrive<NM, EXACT>(do_extend, n, sg_start, sg_len, sg_limit, sg_state, sg_allele);
         }
         const int8_t* data = A.seg_alleles + (size_t)s * n;
         double seg_end = 0.0;
@@ -622,18 +877,10 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         if constexpr (PIPE) { if (do_extend) { seg_end = sg_start + sg_len; limit = sg_limit; } }
         else { if (do_extend) { seg_end = A.seg_start[s] + A.seg_len[s]; limit = A.seg_limit[s]; } }
         const double extend_to = seg_end < v_L ? seg_end : v_L;
-        unsigned one_mask = 0, zero_mask = 0, present_mask = 0, two_mask = 0;
-        int missing = 0;
-        if (do_extend)
-#pragma unroll
-            for (int i = 0; i < NM; ++i) if (i < n) {
-                int d = PIPE ? sg_allele[i] : (int)data[i];
-                missing += d == -1;
-                if (d == 1) one_mask |= 1u << i;
-                if (d == 0) zero_mask |= 1u << i;
-                if (d == 2) two_mask |= 1u << i;
-                if (d >= 0) present_mask |= 1u << i;
-            }
+        RowMasks rm;
+        if (do_extend) rm = row_masks<NM>(n, [&](int i) { return PIPE ? sg_allele[i] : (int)data[i]; });
+        const unsigned one_mask = rm.one, zero_mask = rm.zero, present_mask = rm.present, two_mask = rm.two;
+        const int missing = rm.missing;
         int leaf_status = 0;
         if (missing == 0) leaf_status = 1;
         if (missing == n) leaf_status = -1;
@@ -677,48 +924,8 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             PF_ACC(0, tk0, tk1);
             PF_ACC2(1, tk0a, tk1);
             if (updated_to < extend_to) {
-                double* rec = rec_ptr(A, p, widx);
-                rec[0] = x_mark;
-                rec[1] = updated_to;
-#pragma unroll
-                for (int r = 0; r < RTree<NM>::NI; ++r) if (r < n - 1) rec[5 + r] = t.S[r];
-                double h, tc;
-                PF_TICK(tk2);
-                PF_ACC(1, tk1, tk2);
-                r_genealogy_update<NM, BIASED, PIPE, PIPE && EXACT && NM == 4 && !BIASED && !TREES>(cx, t, &h, &tc);
-                PF_TICK(tk3);
-                PF_ACC(2, tk2, tk3);
-#ifdef PF_STAMPS
-                PF_ACC2(2, tk2, cx.gt[0]);
-                for (int k_ = 0; k_ < 5; ++k_) PF_ACC2(3 + k_, cx.gt[k_], cx.gt[k_ + 1]);
-#endif
-                if (cx.vbc) { w_post *= cx.upd_fac; w_pilot *= cx.upd_fac; cx.upd_fac = 1.0; }
-                rec[2] = h;
-                rec[3] = tc;
-                rec[4] = __longlong_as_double((long long)make_meta(0, mark_limit, limit, n, cx.last_desc, TREES ? cx.last_desc_new : 0u));
-                ++widx;
-                if (leaf_status == 0) B = r_tracked_len(t, n, present_mask);
-                if (leaf_status == 1) B = cx.Ltree;
-                PF_TICK(tk4);
-                PF_ACC(3, tk3, tk4);
-                pf_acc_trip(pf_acc);
-                if (BIASED) {
-                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
-                    double iw = cx.last_iw, rbiw = cx.last_rbiw;
-                    double delay_height = (A.delay_type & 3) == 0 ? h : tc;
-                    int idx = 0;
-                    while (idx + 1 < cx.nb + 1 && sBH[idx + 1] < delay_height) ++idx;
-                    if (idx >= cx.nb) idx = cx.nb - 1;
-                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
-                    double delay = A.app_delays[r_epoch_of(cx, delay_height)];
-                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
-                }
-                PF_TICK(tk5);
-                next_base = r_sample_next_base<true, PIPE>(cx, updated_to);      // fourth uniform of the update
-                x_mark = updated_to;
-                mark_limit = limit;
-                PF_TICK(tk6);
-                PF_ACC(4, tk5, tk6);
+                row_update_trip<NM, BIASED, EXACT, TREES, PIPE>(A, cx, t, ds, p, n, limit, leaf_status, present_mask, updated_to, widx, x_mark, mark_limit, next_base, B,
+                                                                w_post, w_pilot, sBH, sBS PF_ACC_ARGS);
             }
         }
         PF_ACC_STORE;
@@ -743,45 +950,7 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
             has_pending = ds.count > 0;
         }
         if (do_extend && (PIPE ? sg_state : (int)A1.seg_state[s]) == 0) {
-            const bool dephase = A1.flags & 2;
-            const bool anc = A1.flags & 1;
-            unsigned het_pairs = 0;
-            int ncfg = 1;
-            for (int i = 0; i + 1 < n; i += 2) {
-                bool d0_two = (two_mask >> i) & 1u;
-                bool one0 = (one_mask >> i) & 1u, one1 = (one_mask >> (i + 1)) & 1u;
-                bool zero0 = (zero_mask >> i) & 1u, zero1 = (zero_mask >> (i + 1)) & 1u;
-                bool het = d0_two || (dephase && ((one0 && zero1) || (zero0 && one1)));
-                if (het) {
-                    ncfg *= 2;
-                    het_pairs |= 1u << i;
-                    one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
-                    zero_mask |= 1u << i;
-                    one_mask |= 1u << (i + 1);
-                }
-            }
-            double norm = 1.0 / (double)ncfg;
-            RBranchP<NM> bprob;
-            r_site_branch_probs(t, n, v_mu, bprob);     // once per row: the phasing configurations share them
-            double lik = 0;
-            for (;;) {
-                lik += r_site_lik_from(t, n, bprob, one_mask, zero_mask, anc);
-                if (ncfg == 1) break;
-                bool more = false;
-                for (int i = 0; i + 1 < n; i += 2) {
-                    if (!((het_pairs >> i) & 1)) continue;
-                    if ((zero_mask >> i) & 1) {
-                        zero_mask &= ~(1u << i); one_mask |= 1u << i;
-                        one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
-                        more = true;
-                        break;
-                    }
-                    one_mask &= ~(1u << i); zero_mask |= 1u << i;
-                    zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
-                }
-                if (!more) break;
-            }
-            lik *= norm;
+            const double lik = row_site_lik<NM>(t, n, v_mu, one_mask, zero_mask, two_mask, A1.flags & 2, A1.flags & 1);
             w_post *= lik;
             w_pilot *= lik;
         }
@@ -799,31 +968,12 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         }
 
         PF_STAMP(6);
-#pragma unroll
-        for (int r = 0; r < RTree<NM>::NI; ++r)
-            if (r < n - 1) {
-                st1.S[(size_t)r * A1.Np + p] = t.S[r];
-                st1.C[(size_t)(2 * r) * A1.Np + p] = (int8_t)t.C0[r];
-                st1.C[(size_t)(2 * r + 1) * A1.Np + p] = (int8_t)t.C1[r];
-            }
+        row_store_tree<NM>(st1, (size_t)A1.Np, p, n, t);
         st1.w_post[p] = w_post;
         st1.w_pilot[p] = w_pilot;
-        st1.next_base[p] = next_base;
-        st1.x_mark[p] = x_mark;
-        st1.mark_limit[p] = mark_limit;
-        st1.Ltree[p] = cx.Ltree;
-        A1.rng_ctr[p] = cx.ctr;
-        A1.ebuf[p] = cx.ebuf;
+        row_store_chain(A1, st1, p, next_base, x_mark, mark_limit, cx);
         if constexpr (PIPE) {
-            if (PR.draws) A1.dt_ctr[(size_t)(PR.draws - 1) * A1.Np + p] = cx.ctr;      // where the next row's draws start
-            A1.rg_widx[(size_t)cur * A1.Np + p] = widx;
-            if (!do_extend) A1.widx[p] = widx;              // the state goes back to the general kernels
-            if (PR.ahead) {
-                // running ahead of the counts: what they check of the ring (records appended as of the row they count) cannot see
-                // this row's writes, so the writer checks them itself against the oldest generation any pending count can ask for
-                const unsigned kold = A1.gstart[(size_t)(A1.ctrl->g_safe % A1.Gcap) * A1.Np + p];
-                if (widx - kold > A1.cap && !A1.ctrl->err) A1.ctrl->err = ERR_LOG_OVERFLOW;
-            }
+            row_store_counters(A1, PR, cur, p, cx.ctr, widx, do_extend);
         } else {
             A1.widx[p] = widx;
         }
@@ -836,24 +986,13 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
     }
     PF_STAMP(7);
     const KA& A2 = pf_reopen(A);
-    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
-    double sp = wave_tree_sum(w_post);
-    double sq = wave_tree_sum(w_pilot * w_pilot);
-    double scp = wave_hs_scan(w_post, lane);
-    double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
+    const RowScans rs = row_scans(w_post, w_pilot, lane);
+    const double sc = rs.sc, sp = rs.sp, sq = rs.sq, scp = rs.scp, scm = rs.scm;
     long long chunk = p >> 6;
     PF_STAMP(8);
     if constexpr (PIPE) {
-        const size_t ro = (size_t)cur * A2.Np, co = (size_t)cur * A2.nc;
-        if (active) { A2.rg_scan1[ro + p] = sc; A2.rg_scanp[ro + p] = scp; A2.rg_scan1m[ro + p] = scm; }
-        if (p == A2.Np - 1) A2.ctrl->last1[cur] = sc;
-        if (lane == 63 && chunk < A2.nc) {
-            A2.rg_cpost[co + chunk] = sp;
-            A2.rg_csq[co + chunk] = sq;
-            A2.rg_cpil[co + chunk] = sc;
-            A2.rg_cpp[co + chunk] = scp;
-            A2.rg_cmx1[co + chunk] = scm;
-        }
+        const size_t co = (size_t)cur * A2.nc;
+        row_scans_store(A2, cur, p, active, lane, rs);
         if (BIASED) {
             unsigned long long pend = __ballot(has_pending);
             if (lane == 0 && chunk < A2.nc) {
@@ -876,6 +1015,8 @@ __device__ __forceinline__ void extend_reg_body(const KA& A, long long s, int fu
         }
     }
 }
+
+#include "pf_pair.h"
 
 template <int NM, bool BIASED, bool TREES = false>
 __global__ __launch_bounds__(PF_BS) void k_extend_reg(KArgs A, long long s, int fuse) {
@@ -2227,7 +2368,8 @@ __device__ __forceinline__ unsigned long long* wg_trace_slot(SweepChunkC& ch, lo
 // pf_pipe.h): entry t & (PF_RING - 1), which lies in front of the chunk table at an address the kernel arguments give (sweep_head_of),
 // loaded in one batch -- two dependent scalar round trips in front of the first request where sweep_plan and the argument block had
 // ten.  The other roles plan as before.
-template <int NM, bool BIASED, bool EXACT, bool TREES, bool TRACE = false, bool QUEUE = false, bool HEAD = false, bool LOOK = false>
+// PAIR (with HEAD): the extend workgroups run the paired form of the role (extend_pair_body, pf_pair.h), 128 particles each.
+template <int NM, bool BIASED, bool EXACT, bool TREES, bool TRACE = false, bool QUEUE = false, bool HEAD = false, bool LOOK = false, bool PAIR = false>
 __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long long t, int nb) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[pf_chunk()];
@@ -2258,7 +2400,8 @@ __device__ __forceinline__ void sweep_kernel_body(const SweepChunk* tab_g, long 
                 PR.pos_prev = 0.0;                                 // (the end of row s - 1 is requested with the head)
                 PR.draws = PF_HI(H, nT) > 0 ? 1 + (int)(sx & 1) : 0;
                 PR.ahead = (PF_HI(H, split) || PF_HI(H, P) > 1) ? 1 : 0;
-                extend_reg_body<NM, BIASED, EXACT, TREES, true, true>(A, sx, 0, PR, H);
+                if constexpr (PAIR) extend_pair_body<EXACT>(A, sx, nb, PR, H);
+                else extend_reg_body<NM, BIASED, EXACT, TREES, true, true>(A, sx, 0, PR, H);
             }
         }
     } else {
@@ -2288,6 +2431,12 @@ __global__ __launch_bounds__(PF_BS) void k_sweep(const SweepChunk* tab_g, long l
 template <bool EXACT, bool TREES>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_sweep4(const SweepChunk* tab_g, long long t, int nb) {
     sweep_kernel_body<4, false, EXACT, TREES, false, false, true>(tab_g, t, nb);
+}
+// the headline instance with the extend role in its paired form (run_sweep_split, where every extend workgroup has a compute unit of its own: the
+// occupancy is one workgroup, the registers are what the two roles need)
+template <bool EXACT>
+__global__ __launch_bounds__(PF_BS) void k_sweep4p(const SweepChunk* tab_g, long long t, int nb) {
+    sweep_kernel_body<4, false, EXACT, false, false, false, true, false, true>(tab_g, t, nb);
 }
 // the headline instance with the ledger and count work of a step taken off a queue (pf_params.count_workers; the traced form too)
 template <bool EXACT, bool TRACE>

@@ -212,7 +212,7 @@ struct SweepChunk {
 };
 typedef const __attribute__((address_space(4))) SweepChunk SweepChunkC;
 
-// The row header of the headline row kernels (k_sweep4, k_sweep4q, k_sweep4t): what the head of an extend workgroup reads, resolved on the
+// The row header of the headline row kernels (k_sweep4, k_sweep4p, k_sweep4q, k_sweep4t): what the head of an extend workgroup reads, resolved on the
 // host once per call and uploaded in front of the chunk table (sweep_head_of).  Every address the head loads from is a function of the chunk's device pointers (fixed for the life of the handle)
 // and of the ring slots of the step, and those are (s_begin + t) mod PF_RING: one entry per chunk and ring phase, PF_RING entries a chunk,
 // entry t & (PF_RING - 1) for step t.  slot_prev = (s_begin + t - 1) & (PF_RING - 1) is the row the step completes and continues from,

@@ -67,8 +67,7 @@ static RunPath run_path(const pf_handle* h, bool many) {
         if (h->rings != Rings::Reg || dbg(h, PF_DEBUG_TWO_LAUNCH)) return RunPath::TwoLaunch;
         if (dbg(h, PF_DEBUG_K_PIPE) && !many) return RunPath::KPipe;      // (k_pipe takes one chunk per launch: several go through k_sweep)
         // at most four haplotypes, no focused sampling, no -arg: a step is two launches unless the switch says one
-        const bool split = h->n <= 4 && !is_biased(h) && !h->A.rec_trees && !dbg(h, PF_DEBUG_ONE_LAUNCH | PF_DEBUG_K_PIPE);
-        return split ? RunPath::SweepSplit : RunPath::Sweep;
+        return split_shape(h->rings == Rings::Reg, h->P, h->n, is_biased(h), h->A.rec_trees != 0, h->debug) ? RunPath::SweepSplit : RunPath::Sweep;
     }
     if (h->rings == Rings::Xmp) return RunPath::SweepXmp;     // (create_impl gives these rings to no handle with -arg or a path switch)
     if (h->rings == Rings::Xl && many) return RunPath::SweepXl;
@@ -493,7 +492,7 @@ struct SweepFrame {
         }
         if (steps == 0) return 0;
         // the row headers of the call (SweepHead, pf_pipe.h): PF_RING entries a chunk, from the chunk's pointers and s_begin / s_last
-        // (read by k_sweep4, k_sweep4q and k_sweep4t only: launch_sweep), uploaded with the chunk table in one copy
+        // (read by k_sweep4, k_sweep4p, k_sweep4q and k_sweep4t only: launch_sweep, run_sweep_split), uploaded with the chunk table in one copy
         const size_t head_bytes = sizeof(SweepHead) * PF_RING * (size_t)nh, chunk_bytes = sizeof(SweepChunk) * (size_t)nh;
         h->h_table.assign(head_bytes + chunk_bytes, 0);
         SweepHead* heads_end = (SweepHead*)(h->h_table.data() + head_bytes);
@@ -599,7 +598,7 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
 
 // One or several chunks in lockstep as TWO launches per step (the default for one population, at most four haplotypes, no focused sampling;
 // PF_DEBUG_ONE_LAUNCH = run_sweep): the extend, bookkeeping and draw roles of all chunks
-// (k_sweep4, one launch after the other on the leader's stream: the chain of dependent loads that is the critical path of a step) and
+// (k_sweep4, or k_sweep4p where every extend workgroup can have a compute unit of its own; one launch after the other on the leader's stream: the chain of dependent loads that is the critical path of a step) and
 // their ledger and count roles (k_sweep_blc4, on the counting stream, behind the extend launch of the step before by its completion
 // signal and paced by the sixteen-slot ring as in run_sweep_x).  The second launch needs no dynamic LDS -- that is the bookkeeping
 // role's -- and fewer registers than the extend role: four of its workgroups share a compute unit where the single launch has room for
@@ -613,7 +612,25 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
     const int nb = F.nb;
     if (F.join()) return -1;
     if (const int rc = F.table(s_end, 2); rc <= 0) return rc;
-    const dim3 gx((unsigned)(nb + 1 + h->h_sweep[0].nT), (unsigned)nh), blk(PF_BS);
+    // The paired form of the extend role (k_sweep4p, pf_pair.h: 128 particles a workgroup, a weight wavefront beside each tree wavefront) where every
+    // extend workgroup of the call can have a compute unit of its own -- one or two headline chunks; with more the chip is full, a helper wavefront
+    // would take its slot from another chunk's chain, and the one-wavefront form stays.  (vb_coal multiplies the weights inside the loop: those
+    // handles keep the one-wavefront form too.)
+    const int nbp = (int)((h->Np + PF_PAIR_N - 1) / PF_PAIR_N);
+    bool paired = !dbg(h, PF_DEBUG_NO_PAIR) && (long long)nh * nbp <= pf_device_cus(h->device);
+    for (int k = 0; k < nh; ++k) if (hs[k]->A.vb_coal || dbg(hs[k], PF_DEBUG_NO_PAIR)) paired = false;
+    for (int k = 0; k < nh; ++k) hs[k]->row_form = paired ? PF_ROW_FORM_PAIRED : PF_ROW_FORM_SINGLE;
+    const int nbx = paired ? nbp : nb;                      // extend workgroups of a chunk
+    if (paired && !h->pair_lds_set) {
+        // (the ring of the pairs is static LDS: with the tables of the decision the workgroup asks for more than 64 KB; once per handle)
+        hipError_t rc = hipSuccess;
+        with_row_instance(h, [&](auto NM, auto BIASED, auto EXACT, auto TREES) {
+            if constexpr (NM == 4 && !BIASED && !TREES) rc = hipFuncSetAttribute((const void*)k_sweep4p<EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_pipe);
+        });
+        if (rc != hipSuccess) { g_err = "k_sweep4p: the LDS of the paired row kernel was refused (PF_DEBUG_NO_PAIR runs the other form)"; return -1; }
+        h->pair_lds_set = true;
+    }
+    const dim3 gx((unsigned)(nbx + 1 + h->h_sweep[0].nT), (unsigned)nh), blk(PF_BS);
     // (at most four: the second launch of step t - 7 must be enqueued when step t waits for it.  Several chunks: eight 20 Mb chunks 1.205e5 ->
     // 1.248e5 segments/s with two, 1.272e5 with four.  One chunk was the same with any while its extend launch took 26 us; at 23 us the
     // completion signal on every extend launch is what a row waits for -- 20 Mb, round 12: 4.00e4 segments/s with one, 4.27e4 with two or four)
@@ -630,12 +647,15 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
             Timed tm(h, 0, timing_on(h, s_begin + t));
             with_row_instance(h, [&](auto NM, auto BIASED, auto EXACT, auto TREES) {
                 if constexpr (NM == 4 && !BIASED && !TREES) {      // (RunPath::SweepSplit is no other instance)
-                    if (batch_end) hipExtLaunchKernelGGL((k_sweep4<EXACT, false>), gx, blk, h->smem_pipe, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t, nb);
+                    if (paired) {
+                        if (batch_end) hipExtLaunchKernelGGL((k_sweep4p<EXACT>), gx, blk, h->smem_pipe, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t, nbx);
+                        else hipLaunchKernelGGL((k_sweep4p<EXACT>), gx, blk, h->smem_pipe, h->stream, h->d_sweep, t, nbx);
+                    } else if (batch_end) hipExtLaunchKernelGGL((k_sweep4<EXACT, false>), gx, blk, h->smem_pipe, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t, nb);
                     else hipLaunchKernelGGL((k_sweep4<EXACT, false>), gx, blk, h->smem_pipe, h->stream, h->d_sweep, t, nb);
                 }
             });
         }
-        if (check_launch("k_sweep4 (extend, bookkeeping and draw roles)")) return -1;
+        if (check_launch(paired ? "k_sweep4p (extend, bookkeeping and draw roles)" : "k_sweep4 (extend, bookkeeping and draw roles)")) return -1;
         pending_grid[(size_t)(t % batch)] = (unsigned)(1 + F.lc_wgs(t));
         if (batch_end) {
             hipStreamWaitEvent(h->cstream, F.x_done(t), 0);
@@ -734,6 +754,8 @@ int pf_get_run_path(pf_handle* h, int many) {
     return many && !runs_many(p) ? -1 : (int)p;
 }
 
+int pf_get_row_form(pf_handle* h) { return h->row_form; }
+
 // the general kernels: one launch per role and row
 static int run_general(pf_handle* h, long long s_begin, long long s_end) {
     // structured models on the register-tree kernel: the next row's extend completes this row while it loads (two
@@ -759,6 +781,7 @@ static int run_general(pf_handle* h, long long s_begin, long long s_end) {
 
 // rows [s_begin, s_end) of the handles (one, unless a sweep) on the path run_path() named
 static int run_on(RunPath path, pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
+    for (int k = 0; k < nh; ++k) hs[k]->row_form = PF_ROW_FORM_NONE;      // (run_sweep_split says which form it ran)
     switch (path) {
     case RunPath::General: return run_general(hs[0], s_begin, s_end);
     case RunPath::TwoLaunch: return run_single_stream(hs[0], s_begin, s_end);

@@ -192,7 +192,7 @@ struct KArgs {
     double* rg_scan1; double* rg_scan1m; double* rg_scanp;
     double* rg_cpost; double* rg_csq; double* rg_cpil; double* rg_cpp; double* rg_cmx1; double* rg_coffp;
     int* rg_dpend; int* rg_blkcnt;
-    int blk_gran;                  // entries of rg_blkcnt per block of 256 particles: 1, or 4 when the extend workgroups own 64 particles
+    int blk_gran;                  // entries of rg_blkcnt per block of 256 particles: 1, or 4 (one a wavefront) when extend workgroups own fewer than 256 particles
     unsigned* rg_widx;
     int nc;                        // wavefronts = (Np + 63) / 64
     // profiling builds (-DPF_STAMPS): wall-clock stamps of the extend workgroups' phases, [rows][nc][PF_STAMP_W]; null otherwise
@@ -279,7 +279,7 @@ struct Windows {
 };
 
 enum { ERR_LOG_OVERFLOW = 1, ERR_GEN_OVERFLOW = 2, ERR_ZERO_PROB = 3, ERR_COUNT_MISMATCH = 4, ERR_MIG_OVERFLOW = 5,
-       ERR_MP_INTERNAL = 6, ERR_NO_COALESCENCE = 7, ERR_DELAY_OVERFLOW = 8 };
+       ERR_MP_INTERNAL = 6, ERR_NO_COALESCENCE = 7, ERR_DELAY_OVERFLOW = 8, ERR_PAIR_STALL = 9 };
 
 // record meta word: type | lim_start+1 << 8 | lim_event+1 << 16 | n_eff << 24 | descendants << 32 (samples below the
 // branch cut by the recombination that ends the stretch, bit i = sample i; descendants.hpp:22-33) | descendants of the

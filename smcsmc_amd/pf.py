@@ -98,9 +98,9 @@ class PackedLookahead:
 
 
 EXPORTS = [
-    "pf_last_error", "pf_device_count", "pf_create", "pf_destroy", "pf_init_prior", "pf_load_segments", "pf_load_lookahead",
+    "pf_last_error", "pf_device_count", "pf_device_cus", "pf_create", "pf_destroy", "pf_init_prior", "pf_load_segments", "pf_load_lookahead",
     "pf_terminal_branch_quantiles",
-    "pf_update_segment", "pf_count", "pf_resample", "pf_run", "pf_run_many", "pf_can_run_many", "pf_get_run_path", "pf_finish", "pf_sync",
+    "pf_update_segment", "pf_count", "pf_resample", "pf_run", "pf_run_many", "pf_can_run_many", "pf_get_run_path", "pf_get_row_form", "pf_finish", "pf_sync",
     "pf_num_segments_done", "pf_logl", "pf_get_counts", "pf_get_trace", "pf_get_resample_events",
     "pf_get_particles", "pf_get_migrations", "pf_get_local_recomb", "pf_sample_tree_events", "pf_sample_tree_events_pops", "pf_get_kernel_time", "pf_set_timing", "pf_get_stats", "pf_get_delay_stats", "pf_probe_handoff", "pf_probe_tree_edit", "pf_probe_wave_prims", "pf_set_wg_trace", "pf_get_wg_trace", "pf_debug_stamps", "pf_test_search_lut", "pf_simulate_sites",
     "pf_simulate_sites_wide", "pf_median_survival", "pf_median_survival_opts", "pf_test_math", "pf_test_div", "pf_test_uniform", "pf_test_reduce", "pf_test_systematic",
@@ -121,6 +121,7 @@ def load_library(path=None):
     vp = C.c_void_p
     L.pf_last_error.restype = C.c_char_p
     L.pf_device_count.restype = C.c_int
+    L.pf_device_cus.argtypes = [C.c_int]
     L.pf_create.restype = vp
     L.pf_create.argtypes = [C.POINTER(_Model), C.POINTER(_Params), C.c_int]
     L.pf_destroy.argtypes = [vp]
@@ -135,6 +136,7 @@ def load_library(path=None):
     L.pf_run_many.argtypes = [vp, C.c_int32, C.c_int64, C.c_int64]
     L.pf_can_run_many.argtypes = [vp, C.c_int32]
     L.pf_get_run_path.argtypes = [vp, C.c_int]
+    L.pf_get_row_form.argtypes = [vp]
     L.pf_finish.argtypes = [vp]
     L.pf_sync.argtypes = [vp]
     L.pf_sample_tree_events.restype = C.c_int64
@@ -318,6 +320,9 @@ def probe_wave_prims(xd, xi, device=0):
 
 # pf_get_run_path (PF_PATH_* of smcsmc_pf.h, in order)
 RUN_PATHS = ("General", "TwoLaunch", "KPipe", "Sweep", "SweepSplit", "SweepXmp", "SweepXl")
+# pf_get_row_form (PF_ROW_FORM_*)
+ROW_FORMS = (None, "single", "paired")
+DEBUG_NO_PAIR = 4096
 
 
 class ParticleFilter:
@@ -435,6 +440,11 @@ class ParticleFilter:
         many=True run_many()'s, where None says that run_many refuses the filter."""
         k = int(self.L.pf_get_run_path(self.h, int(bool(many))))
         return None if k < 0 else RUN_PATHS[k]
+
+    def row_form(self):
+        """Which form of the row kernel the last run() / run_many() call ran for this filter on SweepSplit (pf_get_row_form; ROW_FORMS):
+        "paired" (a weight wavefront beside each tree wavefront), "single", or None when the call took another path or ran no row."""
+        return ROW_FORMS[int(self.L.pf_get_row_form(self.h))]
 
     def update_segment(self, s):
         self._chk(self.L.pf_update_segment(self.h, int(s)))
