@@ -170,6 +170,14 @@ typedef struct pf_lookahead {
  * pf_get_run_path tells.  Same bits either way (tests/test_gpu_lookahead_rows.py).  A later pf_load_lookahead with level 0 or without
  * the bit returns the handle to the general kernels. */
 #define PF_LA_ROW_PIPELINE 1
+/* pf_lookahead.flags bit 1: the same for structured models -- run the look-ahead inside the extend role of their row pipeline (the LOOK
+ * instance of k_sweep_xmp; PF_PATH_SWEEP_XMP, two launches per row as without a look-ahead) where the handle qualifies: two to four
+ * populations, at most 8 haplotypes with the tree in registers, at most 131 072 particles, no focused sampling, no guide, no -arg, no
+ * debug switch that selects a path.  Any other handle keeps the general kernels, without an error: pf_get_run_path tells.  Same bits
+ * either way (tests/test_gpu_lookahead_rows_structured.py).  Bit 1 means nothing on a one-population handle and bit 0 nothing on a
+ * structured one; a later pf_load_lookahead without the bit returns the handle to the general kernels, one with level 0 to the plain
+ * rows of PF_PATH_SWEEP_XMP. */
+#define PF_LA_ROW_PIPELINE_MP 2
 
 typedef struct pf_handle pf_handle;
 
@@ -228,7 +236,7 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * handle of such a group records trees (a recording handle does not run with a plain one), and the chunks may differ in log_cap and
  * gen_cap -- each chunk brings its own argument block and rings.  pf_sample_tree_events* after pf_run_many + pf_finish returns what it
  * returns after pf_run: the sampled particle and its events, bit for bit.  Structured models with the tree in registers (two to four populations, at
- * most 8 haplotypes, no look-ahead, no -arg) are taken too: one extend launch (k_sweep_xmp, grid = particle blocks x chunks) and one
+ * most 8 haplotypes, no -arg; a look-ahead as said below) are taken too: one extend launch (k_sweep_xmp, grid = particle blocks x chunks) and one
  * launch of the bookkeeping, ledger and count roles (k_sweep_blc) per row for all chunks; such chunks must also share mig_cap,
  * piece_cap, delay_cap and the number of bias bands, and cannot be mixed with one-population chunks.
  * One population with 9 to 16 haplotypes (the tree in per-lane LDS columns; no look-ahead, no -arg, at most 131 072 particles, no debug
@@ -238,9 +246,10 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * pf_run on ONE such handle keeps the general kernels (k_extend -> k_decide -> k_resample); nobody has measured one chunk on the pipeline.
  * A look-ahead (pf_load_lookahead) is taken only when it was loaded with PF_LA_ROW_PIPELINE on a handle that qualifies for it (one
  * population, at most 8 haplotypes, no focused sampling, no -arg): k_sweep<..., LOOK>, one launch per row for pf_run and pf_run_many alike,
- * also at four haplotypes and fewer.  The handles of a group then agree in it: all without a look-ahead, or all with the bit and the same
- * level, max_doubletons and n_quantiles.
- * Not taken: structured models above 8 haplotypes, -arg with structure or above 8 haplotypes, a look-ahead without that bit or on a handle
+ * also at four haplotypes and fewer; or with PF_LA_ROW_PIPELINE_MP on a structured handle that qualifies (two to four populations, at most 8
+ * haplotypes, no focused sampling, no -arg): k_sweep_xmp<..., LOOK> in place of k_sweep_xmp, for pf_run and pf_run_many alike.  The
+ * handles of a group then agree in it: all without a look-ahead, or all with the same flags, level, max_doubletons and n_quantiles.
+ * Not taken: structured models above 8 haplotypes, -arg with structure or above 8 haplotypes, a look-ahead without its bit or on a handle
  * that does not qualify, more than 16 haplotypes (the wide kernels).
  * The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
  * every chunk's results are bit-identical to its own pf_run.  A chunk that runs out of rows simply stops and sits later calls out.
@@ -250,20 +259,21 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
  * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure
  * (at any number of haplotypes: such handles run on the general path, row kernel -> k_decide -> k_resample),
  * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path, or a
- * look-ahead loaded without PF_LA_ROW_PIPELINE or on a handle that does not qualify for it -- or they
- * differ in shape: one with a look-ahead and one without, or look-aheads of two levels or table sizes, haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks,
+ * look-ahead loaded without PF_LA_ROW_PIPELINE (one population) or PF_LA_ROW_PIPELINE_MP (structured) or on a handle that does not qualify for it -- or they
+ * differ in shape: one with a look-ahead and one without, or look-aheads of two levels, flags or table sizes, haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks,
  * or a tree-recording handle mixed with a plain one).  One population with at most 8 haplotypes and -arg IS taken, whatever the chunks'
  * log_cap / gen_cap. */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 /* Which runner takes the rows of this handle as it stands now (a look-ahead loaded later changes the answer): pf_run's with many == 0,
  * pf_run_many's otherwise, where -1 says that pf_run_many refuses the handle.  DESIGN.md, "Which path runs when". */
-#define PF_PATH_GENERAL     0    /* one launch per role and row, two streams (every model; a look-ahead loaded without PF_LA_ROW_PIPELINE) */
+#define PF_PATH_GENERAL     0    /* one launch per role and row, two streams (every model; a look-ahead loaded without PF_LA_ROW_PIPELINE / PF_LA_ROW_PIPELINE_MP, or with it on a handle that does not qualify) */
 #define PF_PATH_TWO_LAUNCH  1    /* k_row + k_decide_ledger (PF_DEBUG_TWO_LAUNCH, or more than 131 072 particles) */
 #define PF_PATH_K_PIPE      2    /* k_pipe (PF_DEBUG_K_PIPE) */
 #define PF_PATH_SWEEP       3    /* k_sweep: every role of a step in one launch */
 /*                               (also a look-ahead loaded with PF_LA_ROW_PIPELINE on a qualifying handle: k_sweep<..., LOOK>, at any n <= 8) */
 #define PF_PATH_SWEEP_SPLIT 4    /* k_sweep4 + k_sweep_blc4: one population, at most four haplotypes, the default */
 #define PF_PATH_SWEEP_XMP   5    /* k_sweep_xmp + k_sweep_blc: structured models, at most 8 haplotypes */
+/*                               (also a look-ahead loaded with PF_LA_ROW_PIPELINE_MP on a qualifying structured handle: k_sweep_xmp<..., LOOK>) */
 #define PF_PATH_SWEEP_XL    6    /* k_sweep_xl + k_sweep_blc: one population, 9 to 16 haplotypes, pf_run_many only */
 int pf_get_run_path(pf_handle* h, int many);
 /* Which form of the row kernel the last pf_run / pf_run_many call ran for this handle's rows on PF_PATH_SWEEP_SPLIT: the paired form (a weight

@@ -302,7 +302,7 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
         pf_lookahead pl;
         memset(&pl, 0, sizeof(pl));
         pl.level = P.apf_level; pl.max_doubletons = la.max_doubletons; pl.n_quantiles = 7; pl.n = sg.n;
-        pl.flags = P.apf_pipeline ? PF_LA_ROW_PIPELINE : 0;
+        pl.flags = P.apf_pipeline ? (PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP) : 0;      // (each bit means something on its own kind of model only)
         pl.first_singleton_distance = la.first_singleton_distance.data();
         pl.relative_mutation_rate = la.relative_mutation_rate.data();
         pl.is_singleton_unphased = la.is_singleton_unphased.data();

@@ -298,9 +298,10 @@ const std::vector<DriverOption>& driver_options() {
          [](PfParam& p, const std::string& v) { p.devices = convert<int>("-devices", v); if (p.devices < 1) throw OutOfRange("-devices", v); }},
         {"-reduce", "STR", "Several chunks", "Exchange of the statistics between ranks: rccl (one device per rank) or host [ rccl when possible ]",
          [](PfParam& p, const std::string& v) { p.reduce_transport = v; }},
-        // not a reference flag: the look-ahead of -apf in the extend role of the row pipeline (one launch per row, lockstep with -chunks) where
-        // the library takes it there (pf_lookahead.flags, include/smcsmc_pf.h); same bits as without.  Off until measured: DESIGN.md section 7
-        {"-apf_pipeline", "", "Several chunks", "With -apf: look-ahead inside the row pipeline (one population, at most 8 haplotypes, no -arg; same results) [ off ]",
+        // not a reference flag: the look-ahead of -apf in the extend role of the row pipeline (one launch per row, lockstep with -chunks; two
+        // launches per row for structured models) where the library takes it there (pf_lookahead.flags, both bits; include/smcsmc_pf.h); same
+        // bits as without.  Off until measured: DESIGN.md section 7
+        {"-apf_pipeline", "", "Several chunks", "With -apf: look-ahead inside the row pipeline (one population or a structured model, at most 8 haplotypes, no -arg; same results) [ off ]",
          [](PfParam& p, const std::string&) { p.apf_pipeline = true; }},
         // not a reference flag: room for migration events on one local tree (the reference's node list is unbounded)
         {"-migcap", "INT", "Several populations", "Migration events one local tree may hold; about 230 fit the LDS with 32 epochs [ 96 ]",

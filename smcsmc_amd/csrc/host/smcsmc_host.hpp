@@ -192,7 +192,7 @@ class PfParam {
     int delay_type = 0;          // 0 recombination height (default), 1 coalescence, 2 coalescence or migration
     bool ancestral_aware = false, dephase = false;
     int apf_level = 0;
-    bool apf_pipeline = false;     // -apf_pipeline: pf_lookahead.flags = PF_LA_ROW_PIPELINE (means something only with -apf > 0)
+    bool apf_pipeline = false;     // -apf_pipeline: pf_lookahead.flags = PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP (means something only with -apf > 0)
     double start_position = 1;
     double tmax = 2;
     bool cap_sizes = false;

@@ -36,7 +36,7 @@ struct pf_handle {
     bool finished = false;
     bool fin_pending = false;     // k_count partials not yet folded into the totals
     Windows step_windows;         // windows of the step being processed
-    int la_flags = 0;             // pf_lookahead.flags of the look-ahead in force (PF_LA_ROW_PIPELINE; 0 without one)
+    int la_flags = 0;             // pf_lookahead.flags of the look-ahead in force (PF_LA_ROW_PIPELINE, PF_LA_ROW_PIPELINE_MP; 0 without one)
     bool pair_lds_set = false;    // the LDS limit of k_sweep4p has been raised for this handle's instance (run_sweep_split)
     int row_form = 0;             // PF_ROW_FORM_*: what the last call ran (pf_get_row_form)
     int debug = 0;                // pf_params.debug: the PF_DEBUG_* switches that select a path are read from here (run_path)
@@ -367,7 +367,7 @@ int pf_load_lookahead(pf_handle* h, const pf_lookahead* la) {
     A.la_fsd = fsd; A.la_rmr = rmr; A.la_unph = unph; A.la_nd = nd; A.la_didx = didx; A.la_ddist = ddist;
     A.la_split = split; A.la_salleles = sal; A.la_sk = sk; A.la_q = q; A.la_tbl = tbl;
     A.la_mean_tbl = la->mean_total_branch_length;
-    h->la_flags = la->flags & PF_LA_ROW_PIPELINE;      // (with the load: a later one without the bit returns the handle to the general kernels)
+    h->la_flags = la->flags & (PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP);      // (with the load: a later one without the bits returns the handle to the general kernels)
     h->smem_la = smem_bytes_la(n, h->E);
     if (h->smem_la > 64 * 1024) hipFuncSetAttribute((const void*)k_lookahead, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_la);
     return 0;

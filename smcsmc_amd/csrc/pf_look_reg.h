@@ -1,13 +1,17 @@
 // smcsmc_amd/csrc/pf_look_reg.h -- the look-ahead factor of the auxiliary particle filter on the register tree.
 //
-// ForestState::includeLookaheadLikelihood (particle.cpp:439-617) for one particle of one population: k_lookahead's
+// ForestState::includeLookaheadLikelihood (particle.cpp:439-617) for one particle, of one population or of a structured model: k_lookahead's
 // arithmetic (pf_hip.hip), statement for statement and in the same operation order, and therefore its bits.  Only the
 // storage differs: the tree is RTree<NM>, and the per-lane scratch of k_lookahead -- n parent heights, n mutation
 // probabilities, n parent ranks, LDS columns there -- is three register arrays here.  Their run-time indices (the
 // haplotypes of a row's singletons and doubletons) are the same for every lane, and are taken with the bit-mask
 // selects of RTree (a `?:` chain is folded back into an indexed load, and the arrays into scratch memory).  The
 // split term goes through the register form of the site likelihood (r_site_branch_probs / r_site_lik_from), which
-// tests/test_gpu_parity.py holds equal to site_lik_lane.  Used by extend_reg_body<..., LOOK> and by nothing else.
+// tests/test_gpu_parity.py holds equal to site_lik_lane.
+// With several populations the first node above a leaf may be a migration event on its branch (k_lookahead's A.P > 1 branch): the
+// caller hands in its event list as a small functor (count / branch / time, sorted by time as the state keeps it), and the leaf's
+// height and parent id come from the lowest event on the branch.  Without one (LookNoMig, the default) that code is not there.
+// Used by extend_reg_body<..., LOOK> (pf_hip.hip, one population) and extend_mpr_body<..., LOOK> (pf_mp.hip, LookMigR), nothing else.
 #pragma once
 #include "pf_tree_reg.h"
 
@@ -40,9 +44,12 @@ __device__ __forceinline__ int la_geti(const int (&v)[N], int i) {
     return r;
 }
 
-// the factor of row `row` for the tree t (as the extend of that row left it), Ltree its length
-template <int NM, class KA>
-__device__ __forceinline__ double look_factor(const KA& A, const RTree<NM>& t, int n, long long row, double Ltree) {
+// no migration events: one population
+struct LookNoMig { static constexpr bool on = false; };
+
+// the factor of row `row` for the tree t (as the extend of that row left it), Ltree its length, mig the migration events on it
+template <int NM, class KA, class MG = LookNoMig>
+__device__ __forceinline__ double look_factor(const KA& A, const RTree<NM>& t, int n, long long row, double Ltree, MG mig = MG()) {
     constexpr int NI = RTree<NM>::NI;
     const int Q = A.la_Q, D = A.la_D, apf = A.apf;
     const double* fsd = A.la_fsd + (size_t)row * n;
@@ -70,6 +77,21 @@ __device__ __forceinline__ double look_factor(const KA& A, const RTree<NM>& t, i
         s_par[i] = pr;
         s_lh[i] = hgt;
         s_mp[i] = 0.0;
+    }
+    if constexpr (MG::on) {
+        // structured models: the first local node above a leaf may be a migration on its branch; its id is -2 - mi, which pairs it with
+        // no other leaf in the doubleton test.  One pass over the events, in time order: the first hit of a leaf is its lowest
+        const int nmig = mig.count();
+        for (int mi = 0; mi < nmig; ++mi) {
+            const int b = mig.branch(mi);
+            const double tm = mig.time(mi);
+#pragma unroll
+            for (int i = 0; i < NM; ++i) {
+                const bool hit = i < n && b == i && s_par[i] >= 0;
+                s_lh[i] = hit ? tm : s_lh[i];
+                s_par[i] = hit ? -2 - mi : s_par[i];
+            }
+        }
     }
     for (int i = 0; i < n; i++) {
         double pp = 0;

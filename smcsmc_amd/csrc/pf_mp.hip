@@ -13,6 +13,7 @@
 #include "pf_lane.h"
 #include "pf_mp.h"
 #include "pf_mp_reg.h"
+#include "pf_look_reg.h"
 #include "pf_mp_host.h"
 #include "pf_pipe.h"
 
@@ -450,8 +451,23 @@ __device__ __forceinline__ SmemMPR carve_mpr(double* base, int E, int P, int mca
 // previous row itself (decide_row), its first wavefront works out the offspring offsets and finds the parents of the
 // workgroup's 64 slots by search (the code of extend_reg_body's prologue, one particle per lane of that wavefront), the
 // previous row is read from one slot of the state ring and this row written to the next -- nothing from k_decide is read.
-template <int NM, bool BIASED, int LA, bool TREES, bool PIPE, class KA>
+// LOOK (with PIPE, without BIASED and TREES; k_sweep_xmp<..., LOOK>, pf_lookahead.flags bit 1): the auxiliary particle filter's
+// look-ahead factor (look_factor, pf_look_reg.h = k_lookahead, with the lane's migration events for the height of a leaf's branch) enters
+// the pilot weight behind the site likelihood and in front of the state stores and the workgroup's partials, so that the partials
+// decide_row reads are those k_lookahead leaves.  The previous factor travels with the state: the slot's own, the parent's on a
+// resampling row.  A completion-only launch applies none and hands on the one it carried.
+// (LookMigR: the lane's event list as look_factor reads it)
+struct LookMigR {
+    static constexpr bool on = true;
+    const MRLane& ml;
+    __device__ __forceinline__ int count() const { return ml.nm; }
+    __device__ __forceinline__ int branch(int mi) const { return LMb(ml, mi); }
+    __device__ __forceinline__ double time(int mi) const { return LMt(ml, mi); }
+};
+
+template <int NM, bool BIASED, int LA, bool TREES, bool PIPE, bool LOOK = false, class KA>
 __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fuse, PipeRow PR = PipeRow()) {
+    static_assert(!LOOK || (PIPE && !BIASED && !TREES), "the look-ahead rides on the plain rows of k_sweep_xmp");
     constexpr int NI = RTree<NM>::NI;
     constexpr int BS = 64 * (64 / LA);
     MP_TICK(tk_begin);                      // profiling builds: "load state" counts from here (tables, completion of the previous row)
@@ -695,6 +711,8 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
         const double ld_wpost = from.w_post[a], ld_wpilot = from.w_pilot[a], ld_next = from.next_base[a], ld_xmark = from.x_mark[a];
         const int ld_ml = from.mark_limit[a];
         const double ld_Ltree = from.Ltree[a], ld_ebuf = A.ebuf[p];
+        [[maybe_unused]] double la_prev = 1.0;
+        if constexpr (LOOK) la_prev = from.lookahead[a];       // the parent's on a resampling row, the slot's own otherwise
         const unsigned long long ld_ctr = A.rng_ctr[p];
         const unsigned ld_widx = (PIPE && completing) ? A.rg_widx[(size_t)from_slot * A.Np + p] : A.widx[p];
         const unsigned ld_pidx = A.pidx[p];
@@ -954,6 +972,18 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
             w_post *= lik;
             w_pilot *= lik;
         }
+        if constexpr (LOOK) {
+            // removeLookaheadLikelihood + includeLookaheadLikelihood (particle.hpp:182, particle.cpp:614-616), as k_lookahead ends
+            double la_w = la_prev;
+            if (do_extend) {
+                const double likelihood = look_factor<NM>(A, t, n, s, cx.Ltree, LookMigR{ml});
+                w_pilot /= la_prev;
+                la_w = 1.0;
+                la_w *= likelihood;
+                w_pilot *= likelihood;
+            }
+            st.lookahead[p] = la_w;          // (the slot the general kernels and the step API read when the call ends here)
+        }
         MP_TICK(tk_lik);
         MP_ACC(ml, 10, tk_loop, tk_lik);
 
@@ -1054,7 +1084,8 @@ __global__ __launch_bounds__(64 * (64 / LA)) void k_extend_mpr(KArgs A, long lon
 // the extend role of the row pipeline for structured models: step t of the chunk table (pf_pipe.h; blockIdx.y is the chunk,
 // a chunk that is finished or sits the call out leaves before it touches LDS or memory other than its table entry), the
 // bookkeeping / ledger / count roles of the step run as their own launch on the counting stream (pf_hip.hip)
-template <int NM, bool BIASED, int LA, bool TREES>
+// (LOOK: with the look-ahead factor in the extend role -- pf_lookahead.flags bit 1; BIASED = TREES = false)
+template <int NM, bool BIASED, int LA, bool TREES, bool LOOK = false>
 __global__ __launch_bounds__(64 * (64 / LA)) void k_sweep_xmp(const SweepChunk* tab_g, long long t) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[blockIdx.y];
@@ -1062,7 +1093,7 @@ __global__ __launch_bounds__(64 * (64 / LA)) void k_sweep_xmp(const SweepChunk* 
     const long long s = ch.s_begin + t;
     PipeLaunch PL;
     if (!sweep_plan(ch, s, 0, PL)) return;
-    if (PL.row.extend || PL.row.complete) extend_mpr_body<NM, BIASED, LA, TREES, true>(A, s, 0, PL.row);
+    if (PL.row.extend || PL.row.complete) extend_mpr_body<NM, BIASED, LA, TREES, true, LOOK>(A, s, 0, PL.row);
 }
 
 __global__ __launch_bounds__(PF_BS) void k_calibrate_mp(KArgs A, unsigned long long seed, long long rep0, long long nrep,
@@ -1242,12 +1273,15 @@ int pf_mp_sweep_prepare(size_t smem) {
     if (smem > 160 * 1024) return -1;
     if (hipFuncSetAttribute((const void*)k_sweep_xmp<8, false, PF_MPR_LANES_PLAIN, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
     if (hipFuncSetAttribute((const void*)k_sweep_xmp<8, true, PF_MPR_LANES_BIASED, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+    if (hipFuncSetAttribute((const void*)k_sweep_xmp<8, false, PF_MPR_LANES_PLAIN, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
     return 0;
 }
 void pf_mp_launch_sweep_x(const KArgs& A, const SweepChunk* tab, int nchunks, long long t, size_t smem, hipStream_t st, hipEvent_t done) {
     const bool biased = A.n_bias > 0 || A.g_K > 0;
     const dim3 grid(mp_blocks(A.Np), (unsigned)nchunks), blk(64 * (64 / (biased ? PF_MPR_LANES_BIASED : PF_MPR_LANES_PLAIN)));
-    if (biased) hipExtLaunchKernelGGL((k_sweep_xmp<8, true, PF_MPR_LANES_BIASED, false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
+    // a look-ahead on this path (run_path: look_on_rows_mp, never with focused sampling): the LOOK instance, the same launch otherwise
+    if (A.apf > 0) hipExtLaunchKernelGGL((k_sweep_xmp<8, false, PF_MPR_LANES_PLAIN, false, true>), grid, blk, smem, st, nullptr, done, 0, tab, t);
+    else if (biased) hipExtLaunchKernelGGL((k_sweep_xmp<8, true, PF_MPR_LANES_BIASED, false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
     else hipExtLaunchKernelGGL((k_sweep_xmp<8, false, PF_MPR_LANES_PLAIN, false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
 }
 void pf_mp_launch_init(const KArgs& A, double initial_position, size_t smem, hipStream_t st) {

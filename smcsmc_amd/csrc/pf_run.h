@@ -57,11 +57,19 @@ static bool look_on_rows(const pf_handle* h) {
            h->workers == 0 && !dbg(h, PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_K_PIPE);
 }
 
+// The same for structured models: the look-ahead was loaded with PF_LA_ROW_PIPELINE_MP and the handle is one the LOOK instance of k_sweep_xmp
+// is built for -- two to four populations with the rings of their row pipeline (at most 8 haplotypes, the tree in registers, no -arg and no
+// debug switch that selects a path: plan_create gives the rings to no other), no focused sampling and no guide
+static bool look_on_rows_mp(const pf_handle* h) {
+    return (h->la_flags & PF_LA_ROW_PIPELINE_MP) && h->P > 1 && h->rings == Rings::Xmp && !is_biased(h) && !h->A.rec_trees &&
+           !dbg(h, PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_K_PIPE);
+}
+
 // `many`: as pf_run_many takes the handle (it refuses General, TwoLaunch and KPipe), otherwise as pf_run does
 static RunPath run_path(const pf_handle* h, bool many) {
     // the look-ahead (loaded after creation): on the general kernels, or by its flag in the extend role of k_sweep -- one launch a step at any
-    // number of haplotypes up to 8, like focused sampling
-    if (h->A.apf != 0) return look_on_rows(h) ? RunPath::Sweep : RunPath::General;
+    // number of haplotypes up to 8, like focused sampling -- or of k_sweep_xmp, the path a structured model has without a look-ahead
+    if (h->A.apf != 0) return look_on_rows(h) ? RunPath::Sweep : (look_on_rows_mp(h) ? RunPath::SweepXmp : RunPath::General);
     // the register-tree kernels of one population, which complete the previous row while loading the particle (fused k_resample)
     if (h->P == 1 && h->n <= 8 && !h->wide && !dbg(h, PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE)) {
         if (h->rings != Rings::Reg || dbg(h, PF_DEBUG_TWO_LAUNCH)) return RunPath::TwoLaunch;
@@ -399,7 +407,7 @@ static void launch_sweep(pf_handle* h, const dim3& grid, long long t) {
 static bool sweep_compatible(const pf_handle* a, const pf_handle* b) {
     const RunPath path = run_path(a, true);
     const bool x = path == RunPath::SweepXmp || path == RunPath::SweepXl;
-    // the look-ahead: off in both, or the same level and table sizes in both (one kernel instance and one set of loop bounds a launch)
+    // the look-ahead: off in both, or the same level, flags (both bits) and table sizes in both (one kernel instance and one set of loop bounds a launch)
     const bool look = a->A.apf == b->A.apf && (a->A.apf == 0 || (a->la_flags == b->la_flags && a->A.la_D == b->A.la_D && a->A.la_Q == b->A.la_Q));
     return look && a->device == b->device && a->Np == b->Np && a->n == b->n && a->E == b->E && a->P == b->P && is_biased(a) == is_biased(b) &&
            a->A.rec_trees == b->A.rec_trees && a->ncw == b->ncw && a->workers == b->workers && a->ledger_wgs == b->ledger_wgs && path == run_path(b, true) && a->cw_off == b->cw_off && a->smem_pipe == b->smem_pipe && a->no_count == b->no_count &&
@@ -731,13 +739,14 @@ static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles
     for (int k = 0; k < n_handles; ++k) {
         pf_handle* g = handles[k];
         if (!g) return "pf_run_many: null handle";
-        // Out of scope: structured models above 8 haplotypes, -arg above 8 haplotypes, a look-ahead without PF_LA_ROW_PIPELINE or on a handle
-        // that does not qualify for it (look_on_rows), the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the
-        // general kernels
+        // Out of scope: structured models above 8 haplotypes, -arg above 8 haplotypes, a look-ahead without PF_LA_ROW_PIPELINE (one
+        // population) or PF_LA_ROW_PIPELINE_MP (structured) or on a handle that does not qualify for it (look_on_rows, look_on_rows_mp),
+        // the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the general kernels
         if (!runs_many(run_path(g, true)))
             return "pf_run_many: the chunks must run on the row pipeline (one population of at most 16 haplotypes, or a structured model of two to "
                    "four populations with the tree in registers, at most 8 haplotypes; a look-ahead only with PF_LA_ROW_PIPELINE on one "
-                   "population of at most 8 haplotypes, no -arg above 8 haplotypes, no debug switch that selects another path)";
+                   "population of at most 8 haplotypes or with PF_LA_ROW_PIPELINE_MP on such a structured model, without focused sampling; "
+                   "no -arg above 8 haplotypes, no debug switch that selects another path)";
         if (!sweep_compatible(h, g)) return "pf_run_many: the chunks must share device, particle count, haplotypes (and with them the form of the tree: registers up to 8, "
                                               "LDS columns of one width from 9 to 16), epochs and options (the look-ahead among them: all without, or one level and one table size)";
         for (int j = 0; j < k; ++j) if (handles[j] == g) return "pf_run_many: a handle appears twice";
