@@ -6,7 +6,11 @@ The reference's own tests hold no golden vectors for weights / indices / log-lik
 published known answers (Philox), analytic expectations of the model it simulates, the
 reference's committed real-scrm data with the known simulation truth, and the acceptance bands of
 the reference's own no-data regression classes (tests/golden/reference_bands.json; the other
-classes need Np = 1000 over 10 Mb and run on the GPU, tests/test_gpu_reference_bands.py)."""
+classes need Np = 1000 over 10 Mb and run on the GPU, tests/test_gpu_reference_bands.py).
+
+Two pins are independent statements of the model and live in files of their own: the exact two-sample E-step
+(tests/exact_hmm2.py, tests/test_exact_hmm_cpu.py) and, for three and four samples and for two populations, the
+brute-force Monte Carlo likelihood and expected counts of tests/mc_model.py (tests/test_mc_model_cpu.py)."""
 import numpy as np
 import pytest
 
