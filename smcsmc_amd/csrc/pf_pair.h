@@ -18,10 +18,19 @@
 //                in LDS.  weight: f = fastexp(-mu * B * dt), w_post *= f, w_pilot *= f, in the order of the passes
 //   tail         tree: site likelihood (through LDS), the tree's stores.  weight: the last product, the weights' stores, the five wavefront
 //                primitives, scans and partials
-// The hand-off words are volatile LDS accesses: the LDS operations of one wavefront complete in order, so an entry is in place when its
-// count is, and no fence is needed inside a workgroup.  Every spin sleeps and is bounded by the 100 MHz clock (PF_PAIR_TICKS, 0.1 s where a row
-// takes tens of microseconds): on expiry the wavefront notes ERR_PAIR_STALL and leaves, and so does every wavefront that sees the note.  No
-// barrier stands inside or behind the update loop.
+// The hand-off words (ring, lik, pub, con, fin, lkf, stall) are read and written through pair_get / pair_put alone: volatile accesses through
+// pointers whose type says LDS (address space 3), so each is one ds_read / ds_write and none a flat instruction.  (Through a generic
+// `volatile PairLds*` every one was a flat access at system scope behind a wait for every request of the wavefront, the draw table's
+// prefetch among them.)  What orders them: the compiler keeps volatile accesses in program order, and the DS instructions of one wavefront
+// execute in order in the one LDS of the compute unit -- an entry is in place when its count is, pub is final once fin is set, lik is in place
+// when lkf says so -- so no fence and no wait stands between an entry's stores and its count's; a reader waits (lgkmcnt) for a count only
+// because it branches on it.  What they do NOT order: global memory.  A hand-off implies nothing about the stores and loads either wavefront
+// has in flight, and nothing needs it to: within a row no role reads global memory the other writes (the closing record, the offspring table,
+// ev_parents, the survivor counts, the weights and the scans are written by the weight wavefront and read by later launches; the tree's
+// records, gstart -- which the check of the record ring reads back, hence on the tree wavefront -- state and counters likewise), and the
+// parent index goes through LDS in front of a barrier.  A dependence through memory added later needs an order of its own.
+// Every spin sleeps and is bounded by the 100 MHz clock (PF_PAIR_TICKS, 0.1 s where a row takes tens of microseconds): on expiry the
+// wavefront notes ERR_PAIR_STALL and leaves, and so does every wavefront that sees the note.  No barrier stands inside or behind the update loop.
 #pragma once
 
 #define PF_PAIR_N 128                   // particles of an extend workgroup
@@ -55,12 +64,20 @@ struct PairLds {
 #define PF_PACC_STORE do {} while (0)
 #endif
 
+// the hand-off words: the address space stands in the pointer's type, here and nowhere else (w: the address of a member of the __shared__ PairLds)
+template <class T>
+__device__ __forceinline__ volatile __attribute__((address_space(3))) T* pair_word(T* w) { return (volatile __attribute__((address_space(3))) T*)w; }
+template <class T>
+__device__ __forceinline__ T pair_get(T* w) { return *pair_word(w); }
+template <class T, class V>
+__device__ __forceinline__ void pair_put(T* w, V v) { *pair_word(w) = (T)v; }
+
 // a turn of a spin that found nothing: sleep; true when the wavefront has to leave (the partner gave up, or the row has taken PF_PAIR_TICKS)
-__device__ __forceinline__ bool pair_spin_fail(volatile PairLds* vl, unsigned long long t_row, Ctrl* c) {
+__device__ __forceinline__ bool pair_spin_fail(PairLds& pl, unsigned long long t_row, Ctrl* c) {
     __builtin_amdgcn_s_sleep(1);
-    if (vl->stall) return true;
+    if (pair_get(&pl.stall)) return true;
     if (wall_clock64() - t_row > PF_PAIR_TICKS) {
-        vl->stall = 1;
+        pair_put(&pl.stall, 1);
         if (!c->err) c->err = ERR_PAIR_STALL;
         return true;
     }
@@ -74,7 +91,6 @@ __device__ __forceinline__ void extend_pair_body(const KA& A, long long s, int n
     extern __shared__ double smem[];
     __shared__ PairLds pl;
     __shared__ unsigned s_lut[2 * PF_LUT_N / 4];
-    volatile PairLds* vl = &pl;
     const int E_head = PF_HI(H, E), n_head = PF_HI(H, n), nc = PF_HI(H, nc);
     const long long Np_head = PF_HL(H, Np);
     double* sT = smem;
@@ -89,13 +105,8 @@ __device__ __forceinline__ void extend_pair_body(const KA& A, long long s, int n
     const int idx = tid & (PF_PAIR_N - 1);
     const long long p = (long long)pf_bx() * PF_PAIR_N + idx;
     const bool active = p < Np_head;
-    const unsigned long long t_row = wall_clock64();
     Ctrl* const cw = A.ctrl;
     if (tree) PF_PSTAMP(0);
-    PF_PHWID();
-    if (tree) { vl->pub[pw][lane] = 0; vl->fin[pw][lane] = 0; vl->lkf[pw][lane] = 0; }
-    else vl->con[pw][lane] = 0;
-    if (tid == 0) vl->stall = 0;
 
     // ---- head: every request of the row's start, back to back.  The particle's doubles come from addresses chosen by role (a scalar
     // select, no branch to join behind): next_base / Ltree / ebuf for the tree, w_post / w_pilot / the slot's scan for the weights.  Heights, x_mark,
@@ -144,6 +155,15 @@ __device__ __forceinline__ void extend_pair_body(const KA& A, long long s, int n
         row_head_segment<NM, EXACT>(H, s, n, sgp_start, sgp_len, sg_start, sg_len, sg_limit, sg_state, sg_allele);
         asm volatile("" ::: "memory");
     }
+    // the hand-off words start the row at zero, behind the issue of the row's requests and in front of the row's first barrier: the first poll of
+    // a weight wavefront (pub, fin, lkf, stall) and the first read of con by a tree wavefront lie behind at least one __syncthreads() on every
+    // path, rows that complete nothing included, since either role runs tables_to_lds(); __syncthreads(); in front of them.  (The spin bound counts
+    // from here.)
+    const unsigned long long t_row = wall_clock64();
+    PF_PHWID();
+    if (tree) { pair_put(&pl.pub[pw][lane], 0); pair_put(&pl.fin[pw][lane], 0); pair_put(&pl.lkf[pw][lane], 0); }
+    else pair_put(&pl.con[pw][lane], 0);
+    if (tid == 0) pair_put(&pl.stall, 0);
 
     // ---- the decision on the row before, by all 256 threads as in the other form
     const PipeLds q = pipe_carve(sBS + (PF_BIAS_MAX + 1), A.nc);
@@ -285,14 +305,14 @@ __device__ __forceinline__ void extend_pair_body(const KA& A, long long s, int n
                 const double new_to = extend_to < next_base ? extend_to : next_base;
                 // the pass's entry for the weight lane; a lane a whole ring ahead waits for its partner
                 while (npub - con_seen >= PF_PAIR_DEPTH) {
-                    con_seen = vl->con[pw][lane];
-                    if (npub - con_seen >= PF_PAIR_DEPTH && pair_spin_fail(vl, t_row, cw)) { failed = true; break; }
+                    con_seen = pair_get(&pl.con[pw][lane]);
+                    if (npub - con_seen >= PF_PAIR_DEPTH && pair_spin_fail(pl, t_row, cw)) { failed = true; break; }
                 }
                 if (failed) break;
-                vl->ring[pw][npub & (PF_PAIR_DEPTH - 1)][0][lane] = B;
-                vl->ring[pw][npub & (PF_PAIR_DEPTH - 1)][1][lane] = new_to - updated_to;
+                pair_put(&pl.ring[pw][npub & (PF_PAIR_DEPTH - 1)][0][lane], B);              // entry, then count
+                pair_put(&pl.ring[pw][npub & (PF_PAIR_DEPTH - 1)][1][lane], new_to - updated_to);
                 ++npub;
-                vl->pub[pw][lane] = npub;
+                pair_put(&pl.pub[pw][lane], npub);
                 updated_to = new_to;
                 PF_TICK(tk1);
                 PF_ACC(0, tk0, tk1);
@@ -303,15 +323,15 @@ __device__ __forceinline__ void extend_pair_body(const KA& A, long long s, int n
             PF_PACC_STORE;
         }
         if (__any(failed)) return;
-        vl->fin[pw][lane] = npub + 1;
+        pair_put(&pl.fin[pw][lane], npub + 1);
         PF_PSTAMP(5);
         // the site likelihood needs the tree: it goes to the weight lane through LDS
         unsigned lflag = 1;
         if (do_extend && sg_state == 0) {
-            if (active) vl->lik[pw][lane] = row_site_lik<NM>(t, n, v_mu, rm.one, rm.zero, rm.two, A.flags & 2, A.flags & 1);
+            if (active) pair_put(&pl.lik[pw][lane], row_site_lik<NM>(t, n, v_mu, rm.one, rm.zero, rm.two, A.flags & 2, A.flags & 1));
             lflag = 2;
         }
-        vl->lkf[pw][lane] = lflag;
+        pair_put(&pl.lkf[pw][lane], lflag);
         PF_PSTAMP(6);
         if (active) {
             const KA& A1 = pf_reopen(A);
@@ -368,28 +388,28 @@ __device__ __forceinline__ void extend_pair_body(const KA& A, long long s, int n
         // the factors of the update loop as the tree lane produces them
         unsigned consumed = 0;
         for (;;) {
-            const unsigned finv = vl->fin[pw][lane];            // (before pub: once the loop has ended, pub is final)
-            const unsigned pubv = vl->pub[pw][lane];
+            const unsigned finv = pair_get(&pl.fin[pw][lane]);           // (before pub: once the loop has ended, pub is final)
+            const unsigned pubv = pair_get(&pl.pub[pw][lane]);
             const bool have = pubv != consumed;
             if (have) {
-                const double eB = vl->ring[pw][consumed & (PF_PAIR_DEPTH - 1)][0][lane];
-                const double edt = vl->ring[pw][consumed & (PF_PAIR_DEPTH - 1)][1][lane];
+                const double eB = pair_get(&pl.ring[pw][consumed & (PF_PAIR_DEPTH - 1)][0][lane]);      // count, then entry; the entry's reads, then con
+                const double edt = pair_get(&pl.ring[pw][consumed & (PF_PAIR_DEPTH - 1)][1][lane]);
                 const double f = fastexp(-v_mu * eB * edt);
                 w_post *= f;
                 w_pilot *= f;
                 ++consumed;
-                vl->con[pw][lane] = consumed;
+                pair_put(&pl.con[pw][lane], consumed);
             }
             if (__all(finv != 0 && consumed == finv - 1)) break;
-            if (!__any(have) && pair_spin_fail(vl, t_row, cw)) return;
+            if (!__any(have) && pair_spin_fail(pl, t_row, cw)) return;
         }
         for (;;) {
-            const unsigned lf = vl->lkf[pw][lane];
+            const unsigned lf = pair_get(&pl.lkf[pw][lane]);
             if (__all(lf != 0)) {
-                if (lf == 2 && active) { const double lik = vl->lik[pw][lane]; w_post *= lik; w_pilot *= lik; }
+                if (lf == 2 && active) { const double lik = pair_get(&pl.lik[pw][lane]); w_post *= lik; w_pilot *= lik; }
                 break;
             }
-            if (pair_spin_fail(vl, t_row, cw)) return;
+            if (pair_spin_fail(pl, t_row, cw)) return;
         }
         PF_PSTAMP(30);
         const KA& A2 = pf_reopen(A);
