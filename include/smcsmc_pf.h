@@ -129,7 +129,10 @@ typedef struct pf_params {
                                   * and draw roles; the ledger and count roles on the counting stream, four workgroups to a compute unit
                                   * (run_sweep_split).  A/B, same bits */
 
-#define PF_DEBUG_NO_PAIR 4096     /* RunPath SweepSplit: the row kernel's one-wavefront form (k_sweep4) also where the paired form (k_sweep4p) would run (A/B) */
+#define PF_DEBUG_SIGNAL_ALL_COUNTS 16384 /* RunPath SweepSplit: a completion signal on EVERY second launch (k_sweep_blc4) of the counting stream, as up to
+                                  * round 19, instead of only on those a wait reads -- one in eight for the ring, and the last of the call (A/B, same
+                                  * bits; bench.py --debug 16384) */
+#define PF_DEBUG_NO_PAIR 4096    /* RunPath SweepSplit: the row kernel's one-wavefront form (k_sweep4) also where the paired form (k_sweep4p) would run (A/B) */
 #define PF_DEBUG_FORCE_WIDE 2048  /* one population: run the wide kernels of nsam > 16 (64-lane workgroups, 64-bit masks, the records' extra
                                    * descendant word, k_count<64>) whatever nsam is -- how that path is pinned against the oracle at n <= 16 */
 

@@ -1624,10 +1624,15 @@ __device__ __forceinline__ int* count_flat_prefix() {
 
 // The body of k_count for the workgroup (bx, by) of a column of nbxg workgroups; `sp` = parity of the step whose
 // weights and snapshot it reads.  Called from k_count and from the count workgroups of k_row.
-template <int NM, int P, bool EXACT = false, class KA>
+// ACC_AT_ENTRY (k_sweep_blc4): the workgroup's accumulator -- it belongs to the position (e, bx), and the launches that write it are serial on one
+// stream -- is requested here, with the first loads, and not read, added to and written back behind the last sum, where the round trip of
+// the read was the tail of every count workgroup.  The same addition on the same two numbers; a workgroup that leaves early stores nothing.
+template <int NM, int P, bool EXACT = false, bool ACC_AT_ENTRY = false, class KA>
 __device__ __forceinline__ void count_body(const KA& A, const CountSrc& Q, int e, double win_a, double win_b, int bx, int nbxg) {
     constexpr int NI = NM - 1;
     using AC = AccT<P>;
+    double acc_before = 0.0;
+    if constexpr (ACC_AT_ENTRY) { if (threadIdx.x < AC::NC) acc_before = A.partial[((size_t)e * A.nbx + bx) * AC::NC + threadIdx.x]; }
     constexpr int LDS_BYTES = (int)(((sizeof(AC) * (PF_BS / 64) + 15) & ~(size_t)15) + sizeof(int) * (PF_CNT_TILE + 1 + PF_BS / 64) + 16);
     char* const cl = count_lds<LDS_BYTES>();
     AC* const red = (AC*)cl;
@@ -1835,7 +1840,9 @@ __device__ __forceinline__ void count_body(const KA& A, const CountSrc& Q, int e
         const int k = threadIdx.x;
         double t = red[0].v[k];
         for (int w = 1; w < PF_BS / 64; ++w) t += red[w].v[k];
-        A.partial[((size_t)e * A.nbx + bx) * AC::NC + k] += t;      // this workgroup's own accumulator (folded by k_count_fin)
+        // this workgroup's own accumulator (folded by k_count_fin)
+        if constexpr (ACC_AT_ENTRY) A.partial[((size_t)e * A.nbx + bx) * AC::NC + k] = acc_before + t;
+        else A.partial[((size_t)e * A.nbx + bx) * AC::NC + k] += t;
     }
 }
 
@@ -2216,7 +2223,7 @@ __device__ __forceinline__ void pipe_ledger_item(const KA& A, const PipeLaunch& 
 }
 
 // count work item idx of that row: part cbx of cnb of the column of epoch e
-template <int NM, bool EXACT, int P, class KA>
+template <int NM, bool EXACT, int P, bool ACC_AT_ENTRY = false, class KA>
 __device__ __forceinline__ void pipe_count_item(const KA& A, const PipeLaunch& PL, const Ctrl::RowInfo& r, int idx) {
     // the columns of the oldest epochs first: their lags are the shortest, their windows sit right behind the front where
     // nearly every particle is still its own ancestor, and their workgroups are the long ones -- dispatched last they were
@@ -2244,11 +2251,12 @@ __device__ __forceinline__ void pipe_count_item(const KA& A, const PipeLaunch& P
     Q.offp = A.rg_coffp + (size_t)PL.lc_slot * A.nc;
     Q.lists = run_lists(A, r.lver);
     Q.inv = r.inv_T; Q.G = r.gen; Q.g_lo = r.g_lo[e]; Q.g_hi = r.g_hi[e];
-    count_body<NM, P, EXACT>(A, Q, e, r.wa[e], r.wb[e], cbx, cnb);
+    count_body<NM, P, EXACT, ACC_AT_ENTRY>(A, Q, e, r.wa[e], r.wb[e], cbx, cnb);
 }
 
-// (NO_EXTEND: the caller has run the extend role itself -- sweep_kernel_body with the row header)
-template <int NM, bool BIASED, bool EXACT, bool TREES, int P = 1, bool BLC = false, bool QUEUE = false, bool LEAN = false, bool NO_EXTEND = false, bool LOOK = false, class KA>
+// (NO_EXTEND: the caller has run the extend role itself -- sweep_kernel_body with the row header; ACC_AT_ENTRY: count_body)
+template <int NM, bool BIASED, bool EXACT, bool TREES, int P = 1, bool BLC = false, bool QUEUE = false, bool LEAN = false, bool NO_EXTEND = false, bool LOOK = false,
+          bool ACC_AT_ENTRY = false, class KA>
 __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeLaunch& PL, const Windows& Wb) {
     const int bx = pf_bx();
     const int nb = PL.nb;
@@ -2282,7 +2290,7 @@ __device__ __forceinline__ void pipe_roles(const KA& A, long long s, const PipeL
     // oldest epoch first).
     if constexpr (!QUEUE) {
         if (lb < PL.nL) { if (r.flag) pipe_ledger_item(A, PL, r, lb); }
-        else pipe_count_item<NM, EXACT, P>(A, PL, r, lb - PL.nL);
+        else pipe_count_item<NM, EXACT, P, ACC_AT_ENTRY>(A, PL, r, lb - PL.nL);
     } else {
         // With it, `workers` workgroups take the items -- the columns first, then the ledger's blocks -- off a counter until none is
         // left: an item writes the same accumulators whoever runs it, the sums do not change.  What that saves several chunks per
@@ -2453,7 +2461,11 @@ __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(3, 3))) v
 // stream beside their extend launch (k_sweep_xmp, pf_mp.hip).  The extend workgroups of those models carry their trees'
 // migration events in LDS (61 KB per 64 particles at the default capacity); in one launch every count workgroup would be
 // given the same allocation and one would fit a CU.
-template <int NM, int P, bool BIASED, bool EXACT = false, bool LEAN = false, bool QUEUE = false>
+// COUNTS_ONLY (k_sweep_blc4, with LEAN): the launch is only ever the second one of a split step (SweepChunk::split = 2, run_sweep_split), said at
+// compile time -- the plan is made without the end of row s - 1, which only the bookkeeping wants (sweep_plan<false>), the word `split` is not
+// read, and a count workgroup asks for its accumulator when it starts (count_body, ACC_AT_ENTRY): three dependent scalar round trips fewer in
+// front of the first vector request of every workgroup of the launch, and one memory round trip fewer behind the last sum of a count workgroup.
+template <int NM, int P, bool BIASED, bool EXACT = false, bool LEAN = false, bool QUEUE = false, bool COUNTS_ONLY = false>
 __device__ __forceinline__ void sweep_blc_body(const SweepChunk* tab_g, long long t) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[pf_chunk()];
@@ -2462,7 +2474,13 @@ __device__ __forceinline__ void sweep_blc_body(const SweepChunk* tab_g, long lon
     __shared__ Windows W;
     Ctrl* c = A.ctrl;
     PipeLaunch PL;
-    if (sweep_plan(ch, s, 0, PL)) {
+    if constexpr (COUNTS_ONLY) {
+        static_assert(LEAN && !QUEUE, "the second launch of a split step in its static form");
+        if (sweep_plan<false>(ch, s, 0, PL)) {
+            PL.nT = 0; PL.b_slot = -1;
+            pipe_roles<NM, BIASED, EXACT, false, P, true, false, true, false, false, true>(A, s, PL, W);
+        }
+    } else if (sweep_plan(ch, s, 0, PL)) {
         PL.nT = 0;                                         // the draw role rides with the extend launch
         if (ch.split == 2) PL.b_slot = -1;                 // ... and so does the bookkeeping (run_sweep_split)
         if (pf_bx() == 0 && PL.b_slot >= 0) sweep_windows(A, c, PL.b_pos, W);
@@ -2478,7 +2496,7 @@ __global__ __launch_bounds__(PF_BS) void k_sweep_blc(const SweepChunk* tab_g, lo
 // sampling, and no dynamic LDS -- four workgroups to a compute unit (128 registers, 36.6 KB)
 template <bool EXACT>
 __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_sweep_blc4(const SweepChunk* tab_g, long long t) {
-    sweep_blc_body<4, 1, false, EXACT, true>(tab_g, t);
+    sweep_blc_body<4, 1, false, EXACT, true, false, true>(tab_g, t);
 }
 // ... with the ledger and count items of a step taken off a queue by a fixed number of workgroups (pf_params.count_workers)
 template <bool EXACT>

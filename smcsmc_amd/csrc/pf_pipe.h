@@ -301,6 +301,20 @@ inline SweepHead sweep_head_entry(const KArgs& A, const SweepChunk& ch, int phas
     return H;
 }
 
+// The pacing of the two streams of a sweep through the ring (host; SweepFrame, pf_run.h).  The extend launch of step t overwrites the slot of
+// row t - PF_RING, which the counts read in step t - PF_RING + 2: one wait every eight steps, for the second launch of seven steps ago, covers the
+// eight steps that follow (t + 7 - 14 <= t - 7).  sweep_ring_awaited: the step whose second launch the extend launch of step t waits for (-1: none).
+// sweep_blc_awaited: whether anything in a call of `steps` steps waits for the second launch of step u -- the ring wait of step u + 7, or the end
+// of the call.  The second says what the first says, by calling it: a launch that signals only where the second holds records every entry the
+// first makes a wait read (tests/test_count_chain_cpu.py plays the schedule through).
+inline long long sweep_ring_awaited(long long t) {
+    static_assert(PF_RING == 16, "the wait schedule is written for sixteen ring slots");
+    return (t >= 8 && (t & 7) == 0) ? t - 7 : -1;
+}
+inline bool sweep_blc_awaited(long long u, long long steps) {
+    return (u + 7 < steps && sweep_ring_awaited(u + 7) == u) || u == steps - 1;
+}
+
 template <class KA>
 __device__ __forceinline__ double sweep_seg_pos(const KA& A, long long s) {       // seg_pos() of the host
     const double e = A.seg_start[s] + A.seg_len[s];
@@ -308,6 +322,9 @@ __device__ __forceinline__ double sweep_seg_pos(const KA& A, long long s) {     
 }
 
 // what run_pipeline's `launch` lambda computes on the host, from the step's row alone
+// (ROW_END = false: a launch without the extend and bookkeeping roles -- k_sweep_blc4 -- does not ask for the end of row s - 1, two dependent
+// scalar round trips through the segment table in front of every workgroup's first request)
+template <bool ROW_END = true>
 __device__ __forceinline__ bool sweep_plan(SweepChunkC& ch, long long s, int nb, PipeLaunch& PL) {
     const long long s_begin = ch.s_begin, s_last = ch.s_last;
     if (s_last < s_begin || s > s_last + 2) return false;
@@ -320,13 +337,13 @@ __device__ __forceinline__ bool sweep_plan(SweepChunkC& ch, long long s, int nb,
     PL.row.slot_prev = PL.row.complete ? (int)((s - 1) & (PF_RING - 1)) : -1;
     PL.row.slot_out = (int)(s & (PF_RING - 1));
     // only a step that completes a row needs its end; on the second flush step row s - 1 = s_last + 1 may lie past the table
-    PL.row.pos_prev = (PL.row.complete && s > s_begin) ? sweep_seg_pos(ch.A, s - 1) : 0.0;
+    PL.row.pos_prev = (ROW_END && PL.row.complete && s > s_begin) ? sweep_seg_pos(ch.A, s - 1) : 0.0;
     PL.row.draws = ch.nT > 0 ? 1 + (int)(s & 1) : 0;
     PL.ahead = PL.row.ahead = (ch.split || ch.A.P > 1) ? 1 : 0;
     PL.nT = extend ? ch.nT : 0;
     PL.b_slot = have_b ? (int)((s - 1) & (PF_RING - 1)) : -1;
     PL.b_row = s - 1;
-    PL.b_pos = have_b ? sweep_seg_pos(ch.A, s - 1) : 0.0;
+    PL.b_pos = (ROW_END && have_b) ? sweep_seg_pos(ch.A, s - 1) : 0.0;
     PL.b_set_cur = flush1 ? (int)((s_last + 1) & (PF_RING - 1)) : -1;
     PL.lc_slot = (have_lc && !ch.no_count) ? (int)((s - 2) & (PF_RING - 1)) : -1;
     PL.live_slot = (int)((s - 1) & (PF_RING - 1));

@@ -524,10 +524,14 @@ struct SweepFrame {
     // Ring slot reuse with two streams: the extend launch of step t overwrites the slot of row t - PF_RING, which the counts read in step
     // t - PF_RING + 2.  One wait every eight steps, for the second launch of seven steps ago, covers the eight steps that
     // follow (t + 7 - 14 <= t - 7); between two waits the extend launches are dispatched back to back.
+    // (sweep_ring_awaited, pf_pipe.h)
     void ring_wait(long long t) const {
-        static_assert(PF_RING == 16, "the wait schedule is written for sixteen ring slots");
-        if (t >= 8 && (t & 7) == 0) hipStreamWaitEvent(h->stream, h->ev_blc[(size_t)((t - 7) & 15)], 0);
+        if (const long long u = sweep_ring_awaited(t); u >= 0) hipStreamWaitEvent(h->stream, blc_done(u), 0);
     }
+    // whether anything waits for the second launch of step u: the ring wait of step u + 7, or leave().  One definition for both sides
+    // (run_sweep_split signals only where this says so): a wait on an entry that step u did not record would return at once, on the
+    // record an earlier step left there.
+    bool blc_awaited(long long u) const { return sweep_blc_awaited(u, steps); }
     hipEvent_t x_done(long long t) const { return h->ev_x[(size_t)(t & 15)]; }        // completion of step t's extend launch ...
     hipEvent_t blc_done(long long t) const { return h->ev_blc[(size_t)(t & 15)]; }    // ... and of its second launch
     // Ledger and count workgroups per chunk in step t.  They belong to row s - 2, whose windows (W2) the host knows as well as the device
@@ -612,7 +616,15 @@ static int run_sweep(pf_handle* const* hs, int nh, long long s_begin, long long 
 // role's -- and fewer registers than the extend role: four of its workgroups share a compute unit where the single launch has room for
 // three, and its tail no longer holds up the next row's extend role.  Same bits as run_sweep.
 //   per step t:  [every 8 steps: stream waits blc_done(t - 7)]  k_sweep4(t), signalling x_done(t) at the end of a batch
-//   per batch:   cstream waits x_done(last t of the batch); k_sweep_blc4(u) signalling blc_done(u), for every step u of the batch
+//   per batch:   cstream waits x_done(last t of the batch); k_sweep_blc4(u) for every step u of the batch, signalling blc_done(u) where a wait reads it
+// Completion signals of the second launches: the counting stream is the longer chain of a row, and a signal is a packet of its own behind the
+// kernel.  Only two waits read one -- the ring wait of step u + 7 (SweepFrame::ring_wait: steps u with (u & 7) == 1) and leave() (the last step) --
+// so only those launches carry one (SweepFrame::blc_awaited); the others are plain launches.  (PF_DEBUG_SIGNAL_ALL_COUNTS: every one, the A/B.)
+// The invariant: every hipStreamWaitEvent on an ev_blc entry waits for a record made by the launch it means, IN THIS CALL.  The entries outlive
+// a call, and a wait on one that its step did not record returns at once, on what an earlier step or call left there: the extend role would
+// overwrite a ring slot the counts still read, and nothing would report it.  That is why the signalling steps and the awaited steps are one
+// definition (sweep_ring_awaited, pf_pipe.h) and not two conditions that happen to agree, and why the record of step u is enqueued (with its batch, at most
+// three steps later) before the wait of step u + 7 is.
 static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long long s_end) {
     if (s_begin >= s_end) return 0;
     SweepFrame F(hs, nh, s_begin, true);
@@ -645,6 +657,7 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
     const long long batch = std::max(1, std::min(4, h->split_batch > 0 ? h->split_batch : 4));
     std::vector<unsigned> pending_grid((size_t)batch, 1u);
     const bool queue = h->h_sweep[0].workers > 0;          // pf_params.count_workers: the second launch takes its items off a queue
+    const bool signal_all = dbg(h, PF_DEBUG_SIGNAL_ALL_COUNTS);   // A/B: a completion signal on every second launch, as up to round 19
     hipStreamWaitEvent(h->cstream, F.seeded, 0);
     for (long long t = 0; t < F.steps; ++t) {
         F.ring_wait(t);
@@ -669,10 +682,14 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
             hipStreamWaitEvent(h->cstream, F.x_done(t), 0);
             for (long long u = t - (t % batch); u <= t; ++u) {
                 const dim3 grid(pending_grid[(size_t)(u % batch)], (unsigned)nh);
+                const bool signal = signal_all || F.blc_awaited(u);
                 with_row_instance(h, [&](auto NM, auto BIASED, auto EXACT, auto TREES) {
                     if constexpr (NM == 4 && !BIASED && !TREES) {
-                        if (queue) hipExtLaunchKernelGGL((k_sweep_blc4q<EXACT>), grid, blk, 0, h->cstream, nullptr, F.blc_done(u), 0, h->d_sweep, u);
-                        else hipExtLaunchKernelGGL((k_sweep_blc4<EXACT>), grid, blk, 0, h->cstream, nullptr, F.blc_done(u), 0, h->d_sweep, u);
+                        if (queue) {
+                            if (signal) hipExtLaunchKernelGGL((k_sweep_blc4q<EXACT>), grid, blk, 0, h->cstream, nullptr, F.blc_done(u), 0, h->d_sweep, u);
+                            else hipLaunchKernelGGL((k_sweep_blc4q<EXACT>), grid, blk, 0, h->cstream, h->d_sweep, u);
+                        } else if (signal) hipExtLaunchKernelGGL((k_sweep_blc4<EXACT>), grid, blk, 0, h->cstream, nullptr, F.blc_done(u), 0, h->d_sweep, u);
+                        else hipLaunchKernelGGL((k_sweep_blc4<EXACT>), grid, blk, 0, h->cstream, h->d_sweep, u);
                     }
                 });
             }

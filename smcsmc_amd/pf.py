@@ -326,6 +326,7 @@ RUN_PATHS = ("General", "TwoLaunch", "KPipe", "Sweep", "SweepSplit", "SweepXmp",
 # pf_get_row_form (PF_ROW_FORM_*)
 ROW_FORMS = (None, "single", "paired")
 DEBUG_NO_PAIR = 4096
+DEBUG_SIGNAL_ALL_COUNTS = 16384      # a completion signal on every second launch of a split step (A/B)
 
 
 class ParticleFilter:
