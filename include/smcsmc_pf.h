@@ -82,7 +82,8 @@ typedef struct pf_params {
     int32_t flags;               /* bit0: record the 100-bp local recombination map (count.cpp:559-654);
                                   * bit1: -arg, keep what pf_sample_tree_events needs;
                                   * bit2: a full delayed-factor store applies its earliest factor early instead of stopping the run
-                                  *       (see delay_cap) */
+                                  *       (see delay_cap);
+                                  * bit3: PF_FLAG_MP_LDS_ROWS below */
     /* Capacities of the device-side rings that stand in for the reference's Arena of EvolutionaryEvents
      * (arena.cpp:56-111, unbounded there).  0 = default.  A ring that is too small for the lags in force is a
      * reported error (pf_sync returns -2, "event log ring overflow" / "generation ledger overflow"), never a
@@ -111,6 +112,13 @@ typedef struct pf_params {
                                   * (pf_run_many), where the launch of a step is several thousand workgroups otherwise. */
     int32_t reserved4;
 } pf_params;
+/* pf_params.flags bit 3: a structured model (two to four populations) of 9 to 16 haplotypes gets the rings of the row pipeline, and pf_run and
+ * pf_run_many take its rows there (PF_PATH_SWEEP_XLMP: k_sweep_xlmp with tree and migration list in LDS + k_sweep_blc, two launches a row where
+ * the general kernels need five).  Off by default.  The handle qualifies with at most 131 072 particles, without -arg, without
+ * PF_DEBUG_FORCE_LDS / NO_FUSE / K_PIPE / TWO_LAUNCH, with gen_cap >= 20 and where the decision tables of the prologue fit in the LDS of the extend
+ * launch.  On every other handle the bit means nothing: path and plan are those without it, never an error -- pf_get_run_path tells.  A
+ * look-ahead loaded on such a handle takes it to the general kernels. */
+#define PF_FLAG_MP_LDS_ROWS 8
 #define PF_DEBUG_FORCE_LDS 1     /* run the LDS-tree kernels whatever nsam is */
 #define PF_DEBUG_NO_FUSE   2     /* complete every row with the stand-alone k_resample (two-stream pipeline) */
 #define PF_DEBUG_NO_COUNT  4     /* profiling: skip the lagged counting and the ledger upkeep */
@@ -252,14 +260,15 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * also at four haplotypes and fewer; or with PF_LA_ROW_PIPELINE_MP on a structured handle that qualifies (two to four populations, at most 8
  * haplotypes, no focused sampling, no -arg): k_sweep_xmp<..., LOOK> in place of k_sweep_xmp, for pf_run and pf_run_many alike.  The
  * handles of a group then agree in it: all without a look-ahead, or all with the same flags, level, max_doubletons and n_quantiles.
- * Not taken: structured models above 8 haplotypes, -arg with structure or above 8 haplotypes, a look-ahead without its bit or on a handle
+ * Structured models of 9 to 16 haplotypes are taken with PF_FLAG_MP_LDS_ROWS (the chunks then agree on haplotypes, populations, mig_cap and the flag).
+ * Not taken: structured models above 8 haplotypes without that flag, -arg with structure or above 8 haplotypes, a look-ahead without its bit or on a handle
  * that does not qualify, more than 16 haplotypes (the wide kernels).
  * The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
  * every chunk's results are bit-identical to its own pf_run.  A chunk that runs out of rows simply stops and sits later calls out.
  * Afterwards every handle's own stream continues behind the call: pf_run, pf_finish, pf_get_counts and the step API mix freely with it. */
 int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, int64_t s_end);
 /* 1 when pf_run_many would take these handles, 0 when the caller has to run them one after the other with pf_run (the row
- * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree), -arg with structure
+ * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree) without PF_FLAG_MP_LDS_ROWS, -arg with structure
  * (at any number of haplotypes: such handles run on the general path, row kernel -> k_decide -> k_resample),
  * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path, or a
  * look-ahead loaded without PF_LA_ROW_PIPELINE (one population) or PF_LA_ROW_PIPELINE_MP (structured) or on a handle that does not qualify for it -- or they
@@ -278,6 +287,7 @@ int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 #define PF_PATH_SWEEP_XMP   5    /* k_sweep_xmp + k_sweep_blc: structured models, at most 8 haplotypes */
 /*                               (also a look-ahead loaded with PF_LA_ROW_PIPELINE_MP on a qualifying structured handle: k_sweep_xmp<..., LOOK>) */
 #define PF_PATH_SWEEP_XL    6    /* k_sweep_xl + k_sweep_blc: one population, 9 to 16 haplotypes, pf_run_many only */
+#define PF_PATH_SWEEP_XLMP  7    /* k_sweep_xlmp + k_sweep_blc: structured models, 9 to 16 haplotypes, only with PF_FLAG_MP_LDS_ROWS; pf_run and pf_run_many */
 int pf_get_run_path(pf_handle* h, int many);
 /* Which form of the row kernel the last pf_run / pf_run_many call ran for this handle's rows on PF_PATH_SWEEP_SPLIT: the paired form (a weight
  * wavefront beside each tree wavefront, 128 particles a workgroup) runs when every extend workgroup of the call can have a compute unit of its

@@ -51,7 +51,7 @@ static void dump_model_json(const PfParam& p) {
     }
     cout << "], \"sample_pops\": [";
     for (size_t k = 0; k < m.sample_pops.size(); ++k) cout << (k ? ", " : "") << m.sample_pops[k];
-    cout << "], \"apf\": " << p.apf_level << ", \"apf_pipeline\": " << (p.apf_pipeline ? "true" : "false") << ", \"record_mask\": [";
+    cout << "], \"apf\": " << p.apf_level << ", \"apf_pipeline\": " << (p.apf_pipeline ? "true" : "false") << ", \"mp_rows\": " << (p.mp_rows ? "true" : "false") << ", \"record_mask\": [";
     for (size_t k = 0; k < p.record_mask.size(); ++k) cout << (k ? ", " : "") << p.record_mask[k];
     cout << "], \"guide_positions\": [";
     for (size_t k = 0; k < p.guide_positions.size(); ++k) cout << (k ? ", " : "") << p.guide_positions[k];
@@ -286,6 +286,7 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
     pp.log_cap = P.log_cap;
     pp.count_wgs = job ? job->count_wgs : P.count_wgs;
     if (P.delay_evict) pp.flags |= 4;
+    if (P.mp_rows) pp.flags |= PF_FLAG_MP_LDS_ROWS;      // (means something for a structured model of 9 to 16 haplotypes only)
     if (P.record_trees) {
         pp.flags |= 2;     // -arg (pfparam.cpp:353-357)
         const ArgRings rings = arg_rings(P, start.size());
@@ -622,8 +623,12 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
     // instances of k_sweep / k_sweep4 -- above 8 the library refuses tree-recording handles, and a group of -arg rings opened only to be
     // filtered one by one would hold the device's memory for nothing).  pf_can_run_many decides.  The library takes
     // the chunks of a structured model too (pf_run_many), but this binary keeps filtering those one after the other
-    // until lockstep has been measured not slower than that at four chunks (section 7: not measured yet) -- npop == 1 below is the switch
-    const bool lockstep = P.model.npop == 1 && P.model.nsam <= 16 && (P.apf_level == 0 || P.apf_pipeline) && !(P.record_trees && P.model.nsam > 8);
+    // until lockstep has been measured not slower than that at four chunks (section 7: not measured yet) -- npop == 1 below is the switch.
+    // -mp_rows is the caller's own switch for structured models of 9 to 16 haplotypes: their chunks then share the launches of a row whenever
+    // pf_can_run_many says so (no -arg, no look-ahead); structured chunks of at most 8 haplotypes keep their default
+    const bool one_pop_rows = P.model.npop == 1 && P.model.nsam <= 16 && (P.apf_level == 0 || P.apf_pipeline) && !(P.record_trees && P.model.nsam > 8);
+    const bool mp_rows = P.mp_rows && P.model.npop > 1 && P.model.nsam > 8 && P.model.nsam <= 16 && P.apf_level == 0 && !P.record_trees;
+    const bool lockstep = one_pop_rows || mp_rows;
     std::mutex notes_lock;
     auto rank_main = [&](int r) {
         bool entered = false;

@@ -303,6 +303,11 @@ const std::vector<DriverOption>& driver_options() {
         // bits as without.  Off until measured: DESIGN.md section 7
         {"-apf_pipeline", "", "Several chunks", "With -apf: look-ahead inside the row pipeline (one population or a structured model, at most 8 haplotypes, no -arg; same results) [ off ]",
          [](PfParam& p, const std::string&) { p.apf_pipeline = true; }},
+        // not a reference flag: structured models of 9 to 16 haplotypes on the row pipeline with tree and migration list in LDS (pf_params.flags bit 3,
+        // PF_FLAG_MP_LDS_ROWS; include/smcsmc_pf.h): two launches a row instead of five, lockstep with -chunks; same bits as without.  Off until
+        // measured: DESIGN.md section 7
+        {"-mp_rows", "", "Several chunks", "Structured models of 9 to 16 haplotypes: rows on the row pipeline, chunks of a rank side by side (no -arg, no -apf; same results) [ off ]",
+         [](PfParam& p, const std::string&) { p.mp_rows = true; }},
         // not a reference flag: room for migration events on one local tree (the reference's node list is unbounded)
         {"-migcap", "INT", "Several populations", "Migration events one local tree may hold; about 230 fit the LDS with 32 epochs [ 96 ]",
          [](PfParam& p, const std::string& v) { p.mig_cap = convert<int>("-migcap", v); if (p.mig_cap < 1) throw OutOfRange("-migcap", v); }},

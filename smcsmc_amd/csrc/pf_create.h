@@ -119,6 +119,11 @@ static CreatePlan create_plan(const pf_model* m, const pf_params* p, long long l
     // general kernels serve such a handle as before)
     else if (P == 1 && n > 8 && n <= PF_NMAX && fits && plain && gen_cap >= PF_RING + 4 && !(p->debug & PF_DEBUG_TWO_LAUNCH) && lds_pipe_tables_fit(n, (int)nc))
         pl.rings = Rings::Xl;
+    // structured models on the LDS tree, only where the caller asked (PF_FLAG_MP_LDS_ROWS): the same rings, the extend role k_sweep_xlmp with 64
+    // particles a workgroup.  The decision's tables go into the lanes' migration-time column or behind the state: 0 says that they fit in neither
+    else if ((p->flags & PF_FLAG_MP_LDS_ROWS) && P > 1 && n > 8 && n <= PF_NMAX && fits && plain && gen_cap >= PF_RING + 4 && !(p->debug & PF_DEBUG_TWO_LAUNCH) &&
+             pf_mp_sweep_xl_smem_bytes(n, E, P, pl.mcap, (int)nc) > 0)
+        pl.rings = Rings::Xlmp;
     const bool has_rings = pl.rings != Rings::None;
     pl.nslots = has_rings ? PF_RING : 2;
     pl.draw_table = pl.rings == Rings::Reg && !(p->debug & (PF_DEBUG_K_PIPE | PF_DEBUG_NO_DRAW_TABLE));
@@ -255,10 +260,10 @@ static int create_allocate(pf_handle* h, const pf_model* m, const pf_params* p, 
         for (int k = 0; k <= A.n_bias && A.n_bias > 0; ++k) A.bias_S[k] = m->bias_strengths[k];
         rc |= h->mem.upload(&A.app_delays, m->application_delays, E, h->stream);
     }
-    // one entry of rg_blkcnt per wavefront where the extend workgroups own fewer than 256 particles: the structured models (64), and the handles
+    // one entry of rg_blkcnt per wavefront where the extend workgroups own fewer than 256 particles: the structured models (64, on either tree), and the handles
     // RunPath::SweepSplit takes (split_shape, pf_handle.h), whose paired form owns 128 -- whichever form of the row kernel then runs
     const bool split = split_shape(h->rings == Rings::Reg, m->n_pops, n, m->n_bias_heights > 0 || m->n_rate_segments > 0, (p->flags & 2) != 0, p->debug);
-    A.blk_gran = (h->rings == Rings::Xmp || split) ? 4 : 1;
+    A.blk_gran = (h->rings == Rings::Xmp || h->rings == Rings::Xlmp || split) ? 4 : 1;
     {
         const size_t K = (size_t)pl.nslots;
         A.nslots = pl.nslots;
@@ -414,6 +419,11 @@ static int create_prepare(pf_handle* h, const pf_params* p) {
             demote();
         }
     }
+    if (h->rings == Rings::Xlmp) {
+        // k_sweep_xlmp: the LDS of k_extend_mp, and the decision's tables behind it where the migration-time column is too short for them
+        h->smem_sweep_x = pf_mp_sweep_xl_smem_bytes(n, E, P, A.mcap, A.nc);
+        if (pf_mp_sweep_xl_prepare(h->smem_sweep_x)) demote();
+    }
     return 0;
 }
 
@@ -427,7 +437,7 @@ pf_handle* pf_create(const pf_model* m, const pf_params* p, int device) {
 
 void pf_destroy(pf_handle* h) { delete h; }
 
-// Steps 1 and 2 without a device: the refusal, or the plan as integers -- rings (0 none, 1 Reg, 2 Xmp, 3 Xl), nslots, draw_table, smem,
+// Steps 1 and 2 without a device: the refusal, or the plan as integers -- rings (0 none, 1 Reg, 2 Xmp, 3 Xl, 4 Xlmp), nslots, draw_table, smem,
 // smem_pipe, ledger_wgs, ncw, workers, split_batch, mcap, dcap, pcap, RS, ncol, max_trace_events, E, cw_off[0..E]
 int pf_test_plan(const pf_model* m, const pf_params* p, int32_t* out, int32_t n_out) {
     if (!m || !p) { g_err = "pf_create: null model or parameters"; return -1; }

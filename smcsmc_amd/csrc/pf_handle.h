@@ -5,7 +5,8 @@
 // The row pipeline a handle's rings were allocated for at creation (create_plan, pf_create.h); run_path() (pf_run.h) picks the runner from this, the debug
 // switches and the look-ahead.  None: two copies of the state, the general kernels or k_row.  Reg: one population, n <= 8, tree in registers
 // (k_sweep*).  Xmp: two to four populations, n <= 8 (k_sweep_xmp).  Xl: one population, 9 <= n <= 16, tree in LDS (k_sweep_xl, pf_run_many only).
-enum class Rings { None, Reg, Xmp, Xl };
+// Xlmp: two to four populations, 9 <= n <= 16, tree and migration list in LDS, only with PF_FLAG_MP_LDS_ROWS (k_sweep_xlmp; pf_run and pf_run_many).
+enum class Rings { None, Reg, Xmp, Xl, Xlmp };
 // The shape RunPath::SweepSplit takes -- run_path (pf_run.h) asks here, and so does create_impl, which gives these handles one entry of rg_blkcnt
 // per wavefront: one population of at most four haplotypes on the rings of the row pipeline, no focused sampling or guide, no -arg, no switch
 // to another path.  (A look-ahead loaded later takes the handle off the path; every writer and reader of rg_blkcnt goes by KArgs::blk_gran.)
@@ -52,7 +53,7 @@ struct pf_handle {
     unsigned long long* d_trace = nullptr;   // pf_set_wg_trace (leader of a pf_run_many call): four words per workgroup and step
     size_t trace_words = 0;
     int trace_t0 = 0, trace_n = 0, trace_stride = 0, trace_grid[3] = {0, 0, 0};
-    size_t smem_sweep_x = 0;      // dynamic LDS of the extend launch of run_sweep_x (rings Xmp, Xl)
+    size_t smem_sweep_x = 0;      // dynamic LDS of the extend launch of run_sweep_x (rings Xmp, Xl, Xlmp)
     std::vector<hipEvent_t> ev_x, ev_blc;   // completion of the last 16 extend / bookkeeping-ledger-count launches
     bool no_spec_stage = false;   // PF_DEBUG_NO_SPEC_STAGE
     SweepChunk* d_sweep = nullptr; // device table of the chunks this handle leads through k_sweep

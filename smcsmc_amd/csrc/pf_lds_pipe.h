@@ -7,6 +7,9 @@
 // store, guide, site likelihood, partials), load_model_k / make_lane_k repeat load_model / make_lane (pf_lane.h), and the prologue
 // follows extend_reg_body<..., PIPE> (pf_hip.hip).  A fix to one of them belongs in both; tests/test_gpu_sweep_lds.py holds the
 // copies together bit for bit.
+// The prologue (what is requested first, the decision and the parent search), k_resample's part, the log-ring check and the partials are
+// functions of their own (lds_pipe_request, lds_pipe_decide, lds_pipe_complete, pipe_log_ring_check, lds_pipe_partials): the extend role of
+// the structured models from 9 to 16 haplotypes (k_sweep_xlmp, pf_mp_pipe.h, 64 lanes a workgroup) calls the same ones.
 #pragma once
 #include "pf_device.h"
 #include "pf_types.h"
@@ -41,27 +44,15 @@ __device__ __forceinline__ Lane make_lane_k(const KA& A, Smem& m, long long p) {
 // the decision tables of the prologue lie where the lanes' tree columns (S, t0, t1) go afterwards
 __host__ __device__ inline bool lds_pipe_tables_fit(int n, int nc) { return pipe_lds_doubles(nc) <= (size_t)3 * (n - 1) * PF_BS; }
 
-// BIASED: focused sampling or a guide (the delayed-factor store, the guide's segment index)
-template <bool BIASED, class KA>
-__device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, const PipeRow PR, double* smem) {
-    Smem m = carve(smem, A.n, A.E);
-    __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
-    const Ctrl* c = A.ctrl;
-    const int n = A.n;
-    const long long p = (long long)pf_bx() * PF_BS + threadIdx.x;
-    const bool active = p < A.Np;
-    const int lane = threadIdx.x & 63;
-    const bool guided = BIASED && A.g_K > 0;
-    const bool biased = BIASED;                          // a guide alone runs with one band of strength 1
-    // ---- everything the prologue and the lane need first, requested in one round trip: the row's own segment, the partials of the
-    // decision, the pilot scans around this workgroup (the parent search of a resampling row), what the slot owns ----
+// ---- The pieces of the prologue and of the end of a row that the LDS-tree extend roles share: k_sweep_xl (below: one population, 256 lanes a
+// workgroup) and k_sweep_xlmp (pf_mp_pipe.h: structured models, 64 lanes a workgroup, PF_BS of its translation unit).  One particle a lane in both. ----
+
+// Everything the prologue and the lane need first, requested in one round trip: the row's own segment, the partials of the decision, the pilot
+// scans around this workgroup (the parent search of a resampling row), what the slot owns.
+struct LdsPipeReq {
     double sg_start = 0.0, sg_len = 0.0;
     int sg_limit = 0, sg_state = 1;
-    if (PR.extend) {
-        sg_start = A.seg_start[s]; sg_len = A.seg_len[s];
-        sg_limit = A.seg_limit[s]; sg_state = A.seg_state[s];
-    }
-    const int fs = __builtin_amdgcn_readfirstlane(PR.slot_prev >= 0 ? PR.slot_prev : c->cur);
+    int fs = 0;                               // the ring slot the row continues from
     RowPre pre;
     long long o_nres = 0; int o_bflag = 0, o_bgen = 0;
     double spec_sm[PF_PIPE_STAGE * 64 / PF_BS];
@@ -70,60 +61,77 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
     int o_ml = 0;
     unsigned o_widx = 0;
     unsigned long long o_ctr = 0;
+};
+template <class KA>
+__device__ __forceinline__ LdsPipeReq lds_pipe_request(const KA& A, long long s, const PipeRow& PR, long long p, bool active) {
+    const Ctrl* c = A.ctrl;
+    LdsPipeReq R;
+    if (PR.extend) {
+        R.sg_start = A.seg_start[s]; R.sg_len = A.seg_len[s];
+        R.sg_limit = A.seg_limit[s]; R.sg_state = A.seg_state[s];
+    }
+    const int fs = __builtin_amdgcn_readfirstlane(PR.slot_prev >= 0 ? PR.slot_prev : c->cur);
+    R.fs = fs;
     if (PR.complete) {
-        pre = row_preload(A, fs);
+        R.pre = row_preload<PF_BS>(A, fs);
         // the row before it: what the extend role of the previous launch noted (the bookkeeping role runs on another stream and
         // is not waited for)
         const int bs = (fs + PF_RING - 1) & (PF_RING - 1);
-        o_nres = c->xr[bs].n_res; o_bflag = c->xr[bs].flag; o_bgen = c->xr[bs].gen;
-        spec_lo = pf_bx() * (PF_BS / 64) - (PF_PIPE_STAGE - PF_BS / 64) / 2;
-        if (spec_lo > A.nc - PF_PIPE_STAGE) spec_lo = A.nc - PF_PIPE_STAGE;
-        if (spec_lo < 0) spec_lo = 0;
+        R.o_nres = c->xr[bs].n_res; R.o_bflag = c->xr[bs].flag; R.o_bgen = c->xr[bs].gen;
+        R.spec_lo = pf_bx() * (PF_BS / 64) - (PF_PIPE_STAGE - PF_BS / 64) / 2;
+        if (R.spec_lo > A.nc - PF_PIPE_STAGE) R.spec_lo = A.nc - PF_PIPE_STAGE;
+        if (R.spec_lo < 0) R.spec_lo = 0;
         const double* sm0 = A.rg_scan1m + (size_t)fs * A.Np;
 #pragma unroll
         for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) {
-            const long long src = (long long)spec_lo * 64 + k * PF_BS + threadIdx.x;
-            spec_sm[k] = src < A.Np ? sm0[src] : PF_INF;
+            const long long src = (long long)R.spec_lo * 64 + k * PF_BS + threadIdx.x;
+            R.spec_sm[k] = src < A.Np ? sm0[src] : PF_INF;
         }
     }
     if (active) {
         const DState own = state_slot(A, fs);
-        o_xmark = own.x_mark[p]; o_ml = own.mark_limit[p];
-        o_widx = PR.complete ? A.rg_widx[(size_t)fs * A.Np + p] : A.widx[p];
-        o_ctr = A.rng_ctr[p]; o_ebuf = A.ebuf[p];
-        if (PR.complete) o_sm = A.rg_scan1m[(size_t)fs * A.Np + p];
+        R.o_xmark = own.x_mark[p]; R.o_ml = own.mark_limit[p];
+        R.o_widx = PR.complete ? A.rg_widx[(size_t)fs * A.Np + p] : A.widx[p];
+        R.o_ctr = A.rng_ctr[p]; R.o_ebuf = A.ebuf[p];
+        if (PR.complete) R.o_sm = A.rg_scan1m[(size_t)fs * A.Np + p];
     }
-    load_model_k(A, m);
-    if (threadIdx.x < PF_BIAS_MAX + 2) {
-        sBH[threadIdx.x] = A.bias_H[threadIdx.x];
-        if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
-    }
-    // ---- the decision on the previous row and, when it resampled, the parent of every slot of this workgroup (extend_reg_body's
-    // prologue: decide_row, the offspring offsets in closed form, the two-level search over the pilot prefix sums) ----
-    const bool completing = PR.complete != 0;
+    return R;
+}
+
+// The decision on the previous row and, when it resampled, the parent of every slot of this workgroup (extend_reg_body's prologue:
+// decide_row, the offspring offsets in closed form, the two-level search over the pilot prefix sums).  `tables`: the LDS the decision's
+// tables take (pipe_lds_doubles(A.nc) doubles, dead again when the caller has passed its next barrier).  Every thread of the workgroup
+// calls this (barriers).  rg_blkcnt gets one entry a workgroup: KArgs::blk_gran says how many that is per 256 particles, 1 at 256 lanes, 4 at 64.
+struct LdsPipeDec {
     bool gather = false;
     double inv = 1.0, S1v = 0.0;
-    const double pos_prev = PR.pos_prev;
     int lo_p = 0, lo_p1 = 0;
     bool first_copy = true;
-    long long a = p;
+    long long a = 0;               // the parent (the slot itself when the row did not resample)
     int G_end = 0, ev = 0;
-    if (completing) {
-        PipeLds q = pipe_carve(smem, A.nc);
+};
+template <class KA>
+__device__ __forceinline__ LdsPipeDec lds_pipe_decide(const KA& A, const PipeRow& PR, const LdsPipeReq& R, double* tables, long long p, bool active) {
+    const int lane = threadIdx.x & 63;
+    const int fs = R.fs;
+    LdsPipeDec D;
+    D.a = p;
+    if (PR.complete != 0) {
+        PipeLds q = pipe_carve(tables, A.nc);
         const int row_slot = fs;
-        const long long n_res = o_nres + o_bflag;
-        G_end = o_bgen + o_bflag;
-        ev = (int)n_res;
+        const long long n_res = R.o_nres + R.o_bflag;
+        D.G_end = R.o_bgen + R.o_bflag;
+        D.ev = (int)n_res;
 #pragma unroll
-        for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) q.stage[k * PF_BS + threadIdx.x] = spec_sm[k];    // visible after decide_row's barriers
-        RowDecision d = decide_row<true>(A, q, row_slot, n_res, pre);
-        inv = d.inv; S1v = d.S1;
-        gather = d.flag != 0;
+        for (int k = 0; k < PF_PIPE_STAGE * 64 / PF_BS; ++k) q.stage[k * PF_BS + threadIdx.x] = R.spec_sm[k];    // visible after decide_row's barriers
+        RowDecision d = decide_row<true, PF_BS>(A, q, row_slot, n_res, R.pre);
+        D.inv = d.inv; D.S1v = d.S1;
+        D.gather = d.flag != 0;
         if (pf_bx() == 0 && threadIdx.x == 0) {
             Ctrl* cw = A.ctrl;
-            cw->xr[row_slot].n_res = n_res; cw->xr[row_slot].gen = G_end; cw->xr[row_slot].flag = d.flag;
+            cw->xr[row_slot].n_res = n_res; cw->xr[row_slot].gen = D.G_end; cw->xr[row_slot].flag = d.flag;
         }
-        if (gather) {
+        if (D.gather) {
             const double dn = (double)A.Np;
             const double invS1 = 1.0 / d.S1;
             const double* sm = A.rg_scan1m + (size_t)row_slot * A.Np;
@@ -131,7 +139,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             const int ch_own = (int)(p >> 6);
             int lo_next = 0;
             if (active) {
-                const double w = pipe_chunk_offset(q, ch_own) + o_sm;
+                const double w = pipe_chunk_offset(q, ch_own) + R.o_sm;
                 const double v_own = q.pmx[ch_own] > w ? q.pmx[ch_own] : w;          // largest pilot prefix sum up to particle p
                 lo_next = p + 1 < A.Np ? pipe_lo_from(v_own, dn, A.Np, d.S1, invS1, d.u) : (int)A.Np;
                 q.slo[threadIdx.x] = lo_next;
@@ -152,9 +160,9 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             if (lane == 0) { q.wint[wave] = cmin; q.wint[PF_BS / 64 + wave] = cmax; }
             __syncthreads();
             if (active) {
-                lo_p1 = lo_next;
-                if (threadIdx.x > 0) lo_p = q.slo[threadIdx.x - 1];
-                else lo_p = p > 0 ? pipe_lo_from(q.pmx[ch_own], dn, A.Np, d.S1, invS1, d.u) : 0;
+                D.lo_p1 = lo_next;
+                if (threadIdx.x > 0) D.lo_p = q.slo[threadIdx.x - 1];
+                else D.lo_p = p > 0 ? pipe_lo_from(q.pmx[ch_own], dn, A.Np, d.S1, invS1, d.u) : 0;
             }
             cmin = q.wint[0]; cmax = q.wint[PF_BS / 64];
             for (int w = 1; w < PF_BS / 64; ++w) {
@@ -163,15 +171,15 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             }
             // survivors of this workgroup (the ledger positions the run list of the ending generation with them)
             {
-                unsigned long long bal = __ballot(active && lo_p1 > lo_p);
+                unsigned long long bal = __ballot(active && D.lo_p1 > D.lo_p);
                 if (lane == 0) q.wint[2 * (PF_BS / 64) + wave] = __popcll(bal);
             }
             int nst = cmax - cmin + 1;
             if (nst > PF_PIPE_STAGE) nst = PF_PIPE_STAGE;
             if (nst < 0) nst = 0;
             int stage_lo = cmin;
-            if (cmin >= spec_lo && cmax < spec_lo + PF_PIPE_STAGE) {
-                stage_lo = spec_lo; nst = PF_PIPE_STAGE;       // the scans requested with the prologue cover the range
+            if (cmin >= R.spec_lo && cmax < R.spec_lo + PF_PIPE_STAGE) {
+                stage_lo = R.spec_lo; nst = PF_PIPE_STAGE;       // the scans requested with the prologue cover the range
             } else {
                 __syncthreads();                               // everybody has read the range before the buffer is refilled
                 for (int idx = threadIdx.x; idx < nst * 64; idx += PF_BS) {
@@ -183,7 +191,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             if (threadIdx.x == 0) {
                 int tot = 0;
                 for (int w = 0; w < PF_BS / 64; ++w) tot += q.wint[2 * (PF_BS / 64) + w];
-                A.rg_blkcnt[(size_t)row_slot * (size_t)((A.Np + PF_BS - 1) / PF_BS) * A.blk_gran + pf_bx()] = tot;
+                A.rg_blkcnt[(size_t)row_slot * (size_t)((A.Np + 255) / 256) * A.blk_gran + pf_bx()] = tot;
             }
             if (active) {
                 const double coff_p = pipe_chunk_offset(q, pch);
@@ -200,11 +208,11 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
                     int mid = (lo_l + hi_l) >> 1;
                     if (lhs < dn * val_at(mid)) hi_l = mid; else lo_l = mid + 1;
                 }
-                a = (long long)pch * 64 + lo_l;
+                long long a = (long long)pch * 64 + lo_l;
                 if (a > A.Np - 1) a = A.Np - 1;
                 // slot p is the first copy of a (it keeps a's next recombination position) iff it equals a's offset
                 const int la = (int)(a & 63);
-                if (p == 0 || a == 0) first_copy = (p == 0);
+                if (p == 0 || a == 0) D.first_copy = (p == 0);
                 else {
                     double vprev = la > 0 ? val_at(la - 1) : pm_p;      // largest prefix sum up to a - 1
                     if (a != (long long)pch * 64 + lo_l) {             // clamped: recompute on the true chunk of a - 1
@@ -213,15 +221,117 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
                         double w = pipe_chunk_offset(q, chm) + sm[am];
                         vprev = q.pmx[chm] > w ? q.pmx[chm] : w;
                     }
-                    first_copy = ((((double)(p - 1)) + d.u) * d.S1 < dn * vprev);
+                    D.first_copy = ((((double)(p - 1)) + d.u) * d.S1 < dn * vprev);
                 }
+                D.a = a;
                 // the offspring table of the generation that ends here, for the ledger
-                int* lo_tab = A.lo + (size_t)(G_end % A.Gcap) * (A.Np + 1);
-                lo_tab[p] = lo_p;
+                int* lo_tab = A.lo + (size_t)(D.G_end % A.Gcap) * (A.Np + 1);
+                lo_tab[p] = D.lo_p;
                 if (p == A.Np - 1) lo_tab[A.Np] = (int)A.Np;
             }
         }
     }
+    return D;
+}
+
+// k_resample's part (pc.cpp:321-392, 435-437), operation for operation, on the values the lane has loaded from its parent `from[a]`:
+// normalisation, or the closing record of the old slot p, the generation mark, the weights of a copy and a fresh position for all but the first
+template <class KA>
+__device__ __forceinline__ void lds_pipe_complete(const KA& A, const DState& from, Lane& ln, long long p, const LdsPipeReq& R, const LdsPipeDec& D,
+                                                  double pos_prev, int ridx, double& w_post, double& w_pilot, double& x_mark, double& next_base,
+                                                  unsigned& widx) {
+    const int n = A.n;
+    if (!D.gather) {
+        w_post *= D.inv;                             // normalize_probability, pc.cpp:435-437
+        w_pilot *= D.inv;
+    } else {
+        // role of the old slot p: close its stretch if it has offspring
+        if (D.lo_p1 > D.lo_p) {
+            double* rec = rec_ptr(A, p, widx);
+            rec[0] = R.o_xmark;
+            rec[1] = pos_prev;
+            rec[2] = 0.0; rec[3] = 0.0;
+            rec[4] = __longlong_as_double((long long)make_meta(1, R.o_ml, -1, n));
+            for (int r = 0; r < n - 1; ++r) rec[5 + r] = from.S[(size_t)r * A.Np + p];
+            ++widx;
+        }
+        A.gstart[(size_t)((D.G_end + 1) % A.Gcap) * A.Np + p] = widx;
+        // role of the new slot p: weights of the copy (pc.cpp:350-351), fresh position for all but the first
+        if (D.ev < A.max_trace_events) A.ev_parents[(size_t)D.ev * A.Np + p] = (int)D.a;
+        const double wp = w_post * D.inv;
+        const double wq = w_pilot * D.inv;
+        const double sumn = D.S1v * D.inv;
+        const double adj = sumn / ((double)A.Np * wq);
+        w_post = wp * adj;
+        w_pilot = wq * adj;
+        x_mark = pos_prev;
+        if (!D.first_copy && pos_prev < A.L) next_base = sample_next_base_guided(ln, pos_prev, A.g_K, A.g_pos, A.g_rho, ridx);     // pc.cpp:357-368
+    }
+}
+
+// The extend launch runs up to PF_RING - 2 rows ahead of the counts: the writer itself checks that it has not overwritten a record that a
+// pending count can still ask for (Ctrl::g_safe: the oldest generation those counts reach)
+template <class KA>
+__device__ __forceinline__ void pipe_log_ring_check(const KA& A, long long p, unsigned widx) {
+    const unsigned kold = A.gstart[(size_t)(A.ctrl->g_safe % A.Gcap) * A.Np + p];
+    if (widx - kold > A.cap && !A.ctrl->err) A.ctrl->err = ERR_LOG_OVERFLOW;
+}
+
+// per-wavefront canonical partials (level 1 of the radix-64 reduction / scan) into ring slot `cur` of the row
+template <class KA>
+__device__ __forceinline__ void lds_pipe_partials(const KA& A, const PipeRow& PR, int cur, long long p, bool active, double w_post, double w_pilot,
+                                                  bool biased, bool has_pending) {
+    const int lane = threadIdx.x & 63;
+    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
+    double sp = wave_tree_sum(w_post);
+    double sq = wave_tree_sum(w_pilot * w_pilot);
+    double scp = wave_hs_scan(w_post, lane);
+    double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
+    const long long chunk = p >> 6;
+    const size_t ro = (size_t)cur * A.Np, co = (size_t)cur * A.nc;
+    if (active) { A.rg_scan1[ro + p] = sc; A.rg_scanp[ro + p] = scp; A.rg_scan1m[ro + p] = scm; }
+    if (p == A.Np - 1) A.ctrl->last1[cur] = sc;
+    if (lane == 63 && chunk < A.nc) {
+        A.rg_cpost[co + chunk] = sp;
+        A.rg_csq[co + chunk] = sq;
+        A.rg_cpil[co + chunk] = sc;
+        A.rg_cpp[co + chunk] = scp;
+        A.rg_cmx1[co + chunk] = scm;
+    }
+    if (biased) {
+        unsigned long long pend = __ballot(has_pending);
+        if (lane == 0 && chunk < A.nc) {
+            A.rg_dpend[co + chunk] = __popcll(pend);
+            if (!PR.extend) A.chunk_dpend[chunk] = __popcll(pend);     // the state goes back to the general kernels
+        }
+    }
+}
+
+// BIASED: focused sampling or a guide (the delayed-factor store, the guide's segment index)
+template <bool BIASED, class KA>
+__device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, const PipeRow PR, double* smem) {
+    Smem m = carve(smem, A.n, A.E);
+    __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
+    const Ctrl* c = A.ctrl;
+    const int n = A.n;
+    const long long p = (long long)pf_bx() * PF_BS + threadIdx.x;
+    const bool active = p < A.Np;
+    const bool guided = BIASED && A.g_K > 0;
+    const bool biased = BIASED;                          // a guide alone runs with one band of strength 1
+    const LdsPipeReq R = lds_pipe_request(A, s, PR, p, active);
+    const double sg_start = R.sg_start, sg_len = R.sg_len;
+    const int sg_limit = R.sg_limit, sg_state = R.sg_state;
+    const int fs = R.fs;
+    load_model_k(A, m);
+    if (threadIdx.x < PF_BIAS_MAX + 2) {
+        sBH[threadIdx.x] = A.bias_H[threadIdx.x];
+        if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
+    }
+    // the decision's tables lie where the lanes' tree columns go afterwards (lds_pipe_tables_fit)
+    const bool completing = PR.complete != 0;
+    const double pos_prev = PR.pos_prev;
+    const LdsPipeDec D = lds_pipe_decide(A, PR, R, smem, p, active);
+    const long long a = D.a;
     __syncthreads();          // the tables are dead from here on: the lanes' tree columns take their place (and the model tables are in)
     const int cur = __builtin_amdgcn_readfirstlane(PR.slot_out);
     const int from_slot = fs;
@@ -243,9 +353,9 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
         double x_mark = from.x_mark[a];
         int mark_limit = from.mark_limit[a];
         ln.Ltree = from.Ltree[a];
-        ln.ctr = o_ctr;
-        ln.ebuf = o_ebuf;
-        unsigned widx = o_widx;
+        ln.ctr = R.o_ctr;
+        ln.ebuf = R.o_ebuf;
+        unsigned widx = R.o_widx;
         DStore ds;
         d_bind(ds, A, st, p);
         ds.count = 0; ds.total = 1.0;
@@ -262,35 +372,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
         int ridx = guided ? from.ridx[a] : 0;
         double* tmp0 = m.t0 + threadIdx.x;
         double* tmp1 = m.t1 + threadIdx.x;
-        if (completing) {
-            // k_resample's part (pc.cpp:321-392, 435-437), operation for operation
-            if (!gather) {
-                w_post *= inv;                             // normalize_probability, pc.cpp:435-437
-                w_pilot *= inv;
-            } else {
-                // role of the old slot p: close its stretch if it has offspring
-                if (lo_p1 > lo_p) {
-                    double* rec = rec_ptr(A, p, widx);
-                    rec[0] = o_xmark;
-                    rec[1] = pos_prev;
-                    rec[2] = 0.0; rec[3] = 0.0;
-                    rec[4] = __longlong_as_double((long long)make_meta(1, o_ml, -1, n));
-                    for (int r = 0; r < n - 1; ++r) rec[5 + r] = from.S[(size_t)r * A.Np + p];
-                    ++widx;
-                }
-                A.gstart[(size_t)((G_end + 1) % A.Gcap) * A.Np + p] = widx;
-                // role of the new slot p: weights of the copy (pc.cpp:350-351), fresh position for all but the first
-                if (ev < A.max_trace_events) A.ev_parents[(size_t)ev * A.Np + p] = (int)a;
-                const double wp = w_post * inv;
-                const double wq = w_pilot * inv;
-                const double sumn = S1v * inv;
-                const double adj = sumn / ((double)A.Np * wq);
-                w_post = wp * adj;
-                w_pilot = wq * adj;
-                x_mark = pos_prev;
-                if (!first_copy && pos_prev < A.L) next_base = sample_next_base_guided(ln, pos_prev, A.g_K, A.g_pos, A.g_rho, ridx);     // pc.cpp:357-368
-            }
-        }
+        if (completing) lds_pipe_complete(A, from, ln, p, R, D, pos_prev, ridx, w_post, w_pilot, x_mark, next_base, widx);
 
         // ---- the row itself: extend_lds_body ----
         const bool do_extend = PR.extend != 0;             // the flush step of a call only completes the last row
@@ -446,35 +528,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
         A.ebuf[p] = ln.ebuf;
         A.rg_widx[(size_t)cur * A.Np + p] = widx;
         if (!do_extend) A.widx[p] = widx;              // the state goes back to the general kernels
-        {
-            // this launch runs up to PF_RING - 2 rows ahead of the counts: the writer itself checks that it has not overwritten a
-            // record that a pending count can still ask for (Ctrl::g_safe: the oldest generation those counts reach)
-            const unsigned kold = A.gstart[(size_t)(A.ctrl->g_safe % A.Gcap) * A.Np + p];
-            if (widx - kold > A.cap && !A.ctrl->err) A.ctrl->err = ERR_LOG_OVERFLOW;
-        }
+        pipe_log_ring_check(A, p, widx);
     }
-    // per-wavefront canonical partials (level 1 of the radix-64 reduction / scan) into the row's ring slot
-    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
-    double sp = wave_tree_sum(w_post);
-    double sq = wave_tree_sum(w_pilot * w_pilot);
-    double scp = wave_hs_scan(w_post, lane);
-    double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
-    const long long chunk = p >> 6;
-    const size_t ro = (size_t)cur * A.Np, co = (size_t)cur * A.nc;
-    if (active) { A.rg_scan1[ro + p] = sc; A.rg_scanp[ro + p] = scp; A.rg_scan1m[ro + p] = scm; }
-    if (p == A.Np - 1) A.ctrl->last1[cur] = sc;
-    if (lane == 63 && chunk < A.nc) {
-        A.rg_cpost[co + chunk] = sp;
-        A.rg_csq[co + chunk] = sq;
-        A.rg_cpil[co + chunk] = sc;
-        A.rg_cpp[co + chunk] = scp;
-        A.rg_cmx1[co + chunk] = scm;
-    }
-    if (biased) {
-        unsigned long long pend = __ballot(has_pending);
-        if (lane == 0 && chunk < A.nc) {
-            A.rg_dpend[co + chunk] = __popcll(pend);
-            if (!PR.extend) A.chunk_dpend[chunk] = __popcll(pend);     // the state goes back to the general kernels
-        }
-    }
+    lds_pipe_partials(A, PR, cur, p, active, w_post, w_pilot, biased, has_pending);
 }

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <atomic>
+
 #include "pf_device.h"
 #include "pf_types.h"
 #include "pf_lane.h"
@@ -44,14 +46,16 @@ __device__ __forceinline__ SmemMP carve_mp(double* base, int n, int E, int P, in
     m.Bp = m.Mq + (size_t)mcap * PF_BS;
     return m;
 }
-__device__ __forceinline__ void load_model_mp(const KArgs& A, SmemMP& m) {
+template <class KA>      // (the argument block by value, or in the constant address space: k_sweep_xlmp)
+__device__ __forceinline__ void load_model_mp(const KA& A, SmemMP& m) {
     const int EP = A.E * A.P;
     for (int i = threadIdx.x; i < EP; i += blockDim.x) { m.I2[i] = A.inv2Np[i]; m.MT[i] = A.mig_tot[i]; m.JM[i] = A.join_map[i]; m.CI[i] = A.cum_coal[i]; m.CM[i] = A.cum_mig[i]; }
     for (int i = threadIdx.x; i < A.E; i += blockDim.x) m.TJ[i] = A.next_join[i];
     for (int i = threadIdx.x; i < EP * A.P; i += blockDim.x) m.MR[i] = A.mig_rate[i];
     for (int i = threadIdx.x; i < A.n; i += blockDim.x) m.SP[i] = A.sample_pop[i];
 }
-__device__ __forceinline__ MLane make_mlane(const KArgs& A, SmemMP& m) {
+template <class KA>      // (the argument block by value, or in the constant address space: k_sweep_xlmp)
+__device__ __forceinline__ MLane make_mlane(const KA& A, SmemMP& m) {
     MLane ml;
     ml.Pn = m.Pn + threadIdx.x; ml.Mt = m.Mt + threadIdx.x; ml.Mb = m.Mb + threadIdx.x; ml.Mq = m.Mq + threadIdx.x; ml.Bp = m.Bp + threadIdx.x;
     ml.nm = 0; ml.P = A.P; ml.mcap = A.mcap;
@@ -59,14 +63,16 @@ __device__ __forceinline__ MLane make_mlane(const KArgs& A, SmemMP& m) {
     ml.err = 0;
     return ml;
 }
-__device__ __forceinline__ void mp_report(const KArgs& A, const MLane& ml) {
+template <class KA>      // (the argument block by value, or in the constant address space: k_sweep_xlmp)
+__device__ __forceinline__ void mp_report(const KA& A, const MLane& ml) {
     // an error of an earlier row stays the one reported (what follows it on a broken state is a consequence)
     if (ml.err && !A.ctrl->err) A.ctrl->err = ml.err == 1 ? ERR_MIG_OVERFLOW : (ml.err == 2 ? ERR_MP_INTERNAL : ERR_NO_COALESCENCE);
 }
 __device__ __forceinline__ double piece_ref(unsigned pstart, unsigned npieces) {
     return __longlong_as_double((long long)((unsigned long long)pstart | ((unsigned long long)npieces << 32)));
 }
-__device__ __forceinline__ void store_mp_state(const KArgs& A, const DState& st, const Lane& ln, const MLane& ml, long long p) {
+template <class KA>      // (the argument block by value, or in the constant address space: k_sweep_xlmp)
+__device__ __forceinline__ void store_mp_state(const KA& A, const DState& st, const Lane& ln, const MLane& ml, long long p) {
     const int n = A.n;
     for (int r = 0; r < n - 1; ++r) st.Pn[(size_t)r * A.Np + p] = LPn(ml, r);
     st.nm[p] = ml.nm;
@@ -405,6 +411,26 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
         unsigned long long pend = __ballot(has_pending);
         if (lane == 0 && chunk < (A.Np + 63) / 64) A.chunk_dpend[chunk] = __popcll(pend);
     }
+}
+
+// ------------------------------------------------------------------ structured models, LDS tree, on the row pipeline (9 <= n <= 16, PF_FLAG_MP_LDS_ROWS)
+#include "pf_mp_pipe.h"
+
+// The extend role of the row pipeline for structured models with the tree and the migration list in per-lane LDS columns (extend_mp_pipe_body,
+// pf_mp_pipe.h): step t of the chunk table, blockIdx.y is the chunk, 64 particles a workgroup as in k_extend_mp.  A chunk that is finished or sits
+// the call out leaves before it touches LDS or memory other than its table entry.  The bookkeeping, ledger and count roles of the step are
+// k_sweep_blc<16, 2 or PF_PMAX, *> on the counting stream (pf_hip.hip).
+template <bool BIASED>
+__global__ __launch_bounds__(PF_BS) void k_sweep_xlmp(const SweepChunk* tab_g, long long t) {
+    SweepChunkC* tab = (SweepChunkC*)tab_g;
+    SweepChunkC& ch = tab[pf_chunk()];
+    KArgsC& A = ch.A;
+    const long long s = ch.s_begin + t;
+    PipeLaunch PL;
+    if (!sweep_plan(ch, s, 0, PL)) return;
+    if (!(PL.row.extend || PL.row.complete)) return;
+    extern __shared__ double smem[];
+    extend_mp_pipe_body<BIASED>(A, s, PL.row, smem);
 }
 
 // ------------------------------------------------------------------ structured models, register-resident tree (n <= 8)
@@ -1283,6 +1309,29 @@ void pf_mp_launch_sweep_x(const KArgs& A, const SweepChunk* tab, int nchunks, lo
     if (A.apf > 0) hipExtLaunchKernelGGL((k_sweep_xmp<8, false, PF_MPR_LANES_PLAIN, false, true>), grid, blk, smem, st, nullptr, done, 0, tab, t);
     else if (biased) hipExtLaunchKernelGGL((k_sweep_xmp<8, true, PF_MPR_LANES_BIASED, false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
     else hipExtLaunchKernelGGL((k_sweep_xmp<8, false, PF_MPR_LANES_PLAIN, false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
+}
+// the extend role of the row pipeline on the LDS tree (k_sweep_xlmp): LDS = k_extend_mp's, plus the decision's tables where they do not fit into
+// the lanes' migration-time column; 0: the tables do not fit at all
+size_t pf_mp_sweep_xl_smem_bytes(int n, int E, int P, int mcap, int nc) { return smem_bytes_mp_pipe(n, E, P, mcap, nc); }
+int pf_mp_sweep_xl_prepare(size_t smem) {
+    if (smem == 0 || smem > 160 * 1024) return -1;
+    // (the attribute belongs to the kernel, not to the handle: the largest any handle of the process has asked for)
+    static std::atomic<int> most_asked{0};
+    int most = most_asked.load();
+    while (most < (int)smem && !most_asked.compare_exchange_weak(most, (int)smem)) {}
+    most = most > (int)smem ? most : (int)smem;
+    if (most <= 64 * 1024) return 0;
+    if (hipFuncSetAttribute((const void*)k_sweep_xlmp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_sweep_xlmp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return 0;
+}
+void pf_mp_launch_sweep_xl(const KArgs& A, const SweepChunk* tab, int nchunks, long long t, size_t smem, hipStream_t st, hipEvent_t done) {
+    const dim3 grid(mp_blocks(A.Np), (unsigned)nchunks), blk(PF_BS);
+    if (A.n_bias > 0 || A.g_K > 0) hipExtLaunchKernelGGL((k_sweep_xlmp<true>), grid, blk, smem, st, nullptr, done, 0, tab, t);
+    else hipExtLaunchKernelGGL((k_sweep_xlmp<false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
 }
 void pf_mp_launch_init(const KArgs& A, double initial_position, size_t smem, hipStream_t st) {
     hipLaunchKernelGGL(k_init_mp, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);

@@ -20,6 +20,11 @@ struct SweepChunk;
 size_t pf_mp_sweep_smem_bytes(int E, int P, int mcap, int nc);
 int pf_mp_sweep_prepare(size_t smem);
 void pf_mp_launch_sweep_x(const KArgs& A, const SweepChunk* tab, int nchunks, long long t, size_t smem, hipStream_t st, hipEvent_t done);
+// the same role with tree and migration list in LDS (k_sweep_xlmp: 9 to 16 haplotypes, PF_FLAG_MP_LDS_ROWS).  The size is 0 where the decision's
+// tables fit neither into the lanes' migration-time column nor behind the state (create_plan asks here, without a device)
+size_t pf_mp_sweep_xl_smem_bytes(int n, int E, int P, int mcap, int nc);
+int pf_mp_sweep_xl_prepare(size_t smem);
+void pf_mp_launch_sweep_xl(const KArgs& A, const SweepChunk* tab, int nchunks, long long t, size_t smem, hipStream_t st, hipEvent_t done);
 void pf_mp_launch_calibrate(const KArgs& A, unsigned long long seed, long long rep0, long long nrep, int* out_epoch,
                             double* out_dist, int* out_err, size_t smem, hipStream_t st);
 void pf_mp_launch_tbl(const KArgs& A, unsigned long long seed, long long nrep, double* out_h, double* out_len, int* out_err,

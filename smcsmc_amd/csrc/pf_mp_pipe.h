@@ -1,0 +1,263 @@
+// smcsmc_amd/csrc/pf_mp_pipe.h -- the extend role of the row pipeline for structured models on the per-lane LDS tree (k_sweep_xlmp, pf_mp.hip):
+// two to four populations, 9 to PF_NMAX haplotypes, only on handles created with PF_FLAG_MP_LDS_ROWS.  It is to k_extend_mp what k_sweep_xl
+// (pf_lds_pipe.h) is to k_extend and what k_sweep_xmp is to k_extend_mpr: the decision on the previous row, the parent search and k_resample's
+// part are in the prologue, the state is read from one slot of the sixteen-slot ring and written to the next, nothing of k_decide is read.
+// Included by pf_mp.hip behind k_extend_mp (SmemMP, carve_mp, load_model_mp, make_mlane, mp_report, store_mp_state, piece_ref are that file's).
+//   prologue, k_resample's part, log-ring check, partials: the functions of pf_lds_pipe.h, shared with k_sweep_xl (64 lanes a workgroup here)
+//   the gather: tree, node populations and the migration list of the parent into this lane's LDS columns
+//   the row: k_extend_mp's statements (sample_point*, mp_genealogy_rest and the walk of pf_mp.h), from "the row" on; a fix to one belongs in
+//            both, tests/test_gpu_sweep_structured_lds.py holds them together through the oracle, bit for bit
+// No -arg and no look-ahead on this path (create_plan, run_path).
+#pragma once
+#include "pf_lds_pipe.h"
+
+// Where the decision's tables go: into the lanes' migration-time column (mcap * 64 doubles, loaded once the previous row is decided) when they
+// fit there, behind everything else otherwise (a small mig_cap).  Dynamic LDS of the launch; 0: more than the 160 KB of a workgroup.
+__host__ __device__ inline bool mp_pipe_tables_inside(int mcap, int nc) { return pipe_lds_doubles(nc) <= (size_t)mcap * PF_BS; }
+static size_t smem_bytes_mp_pipe(int n, int E, int P, int mcap, int nc) {
+    const size_t total = smem_bytes_mp(n, E, P, mcap) + (mp_pipe_tables_inside(mcap, nc) ? 0 : pipe_lds_doubles(nc) * 8);
+    return total <= 160 * 1024 ? total : 0;
+}
+
+// BIASED: focused sampling or a guide (the delayed-factor store, the guide's segment index)
+template <bool BIASED, class KA>
+__device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, const PipeRow PR, double* smem) {
+    Smem m = carve(smem, A.n, A.E);
+    SmemMP mm = carve_mp(smem, A.n, A.E, A.P, A.mcap);
+    __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
+    const Ctrl* c = A.ctrl;
+    const int n = A.n;
+    const long long p = (long long)pf_bx() * PF_BS + threadIdx.x;
+    const bool active = p < A.Np;
+    const bool guided = BIASED && A.g_K > 0;
+    const bool biased = BIASED && (A.n_bias > 0 || guided);          // a guide alone runs with one band of strength 1
+    const LdsPipeReq R = lds_pipe_request(A, s, PR, p, active);
+    load_model_k(A, m);
+    load_model_mp(A, mm);
+    if (threadIdx.x < PF_BIAS_MAX + 2) {
+        sBH[threadIdx.x] = A.bias_H[threadIdx.x];
+        if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
+    }
+    const bool completing = PR.complete != 0;
+    const double pos_prev = PR.pos_prev;
+    double* tables = mp_pipe_tables_inside(A.mcap, A.nc) ? mm.Mt : (double*)((char*)smem + smem_bytes(A.n, A.E) + smem_mp_extra(A.n, A.E, A.P, A.mcap));
+    const LdsPipeDec D = lds_pipe_decide(A, PR, R, tables, p, active);
+    const long long a = D.a;
+    __syncthreads();          // the tables are dead from here on: the lanes' event lists take their place (and the model tables are in)
+    const int cur = __builtin_amdgcn_readfirstlane(PR.slot_out);
+    bool has_pending = false;
+    double w_post = 0.0, w_pilot = 0.0;
+    if (active) {
+        const DState st = state_slot(A, cur);
+        const DState from = state_slot(A, R.fs);
+        Lane ln = make_lane_k(A, m, p);
+        MLane ml = make_mlane(A, mm);
+        // the parent's tree, node populations and migration list into this lane's columns (its own when the row did not resample)
+        for (int r = 0; r < n - 1; ++r) {
+            LS(ln, r) = from.S[(size_t)r * A.Np + a];
+            LC(ln, r, 0) = from.C[(size_t)(2 * r) * A.Np + a];
+            LC(ln, r, 1) = from.C[(size_t)(2 * r + 1) * A.Np + a];
+            LPn(ml, r) = from.Pn[(size_t)r * A.Np + a];
+        }
+        ml.nm = from.nm[a];
+        for (int q = 0; q < ml.nm; ++q) {
+            LMt(ml, q) = from.Mt[(size_t)q * A.Np + a];
+            LMb(ml, q) = from.Mb[(size_t)q * A.Np + a];
+            LMq(ml, q) = from.Mq[(size_t)q * A.Np + a];
+        }
+        w_post = from.w_post[a];
+        w_pilot = from.w_pilot[a];
+        double next_base = from.next_base[a];
+        double x_mark = from.x_mark[a];
+        int mark_limit = from.mark_limit[a];
+        ln.Ltree = from.Ltree[a];
+        ln.ctr = R.o_ctr;
+        ln.ebuf = R.o_ebuf;
+        unsigned widx = R.o_widx;
+        DStore ds;
+        d_bind(ds, A, st, p);
+        ds.count = 0; ds.total = 1.0;
+        if (biased) {
+            ds.count = from.dcount[a]; ds.total = from.total_delayed[a];
+            // the copy constructor copies the pending factors (particle.cpp:122-123); the ring moves them every row
+            for (int k = 0; k < ds.count; ++k) {
+                st.dpos[(size_t)k * A.Np + p] = from.dpos[(size_t)k * A.Np + a];
+                st.dfac[(size_t)k * A.Np + p] = from.dfac[(size_t)k * A.Np + a];
+                st.ddelta[(size_t)k * A.Np + p] = from.ddelta[(size_t)k * A.Np + a];
+                st.dk[(size_t)k * A.Np + p] = from.dk[(size_t)k * A.Np + a];
+            }
+        }
+        int ridx = guided ? from.ridx[a] : 0;
+        PLog pl;
+        pl.base = A.plog + (size_t)p * A.pcap * 3; pl.cap = A.pcap; pl.idx = A.pidx[p]; pl.pos = pl.idx % pl.cap; pl.on = true;
+        pl.fopen = false; pl.ropen = false;
+        double* tmp0 = m.t0 + threadIdx.x;
+        double* tmp1 = m.t1 + threadIdx.x;
+        if (completing) lds_pipe_complete(A, from, ln, p, R, D, pos_prev, ridx, w_post, w_pilot, x_mark, next_base, widx);
+
+        // ---- the row itself: k_extend_mp ----
+        const bool do_extend = PR.extend != 0;             // the flush step of a call only completes the last row
+        const int8_t* data = A.seg_alleles + (size_t)s * n;
+        const double seg_end = do_extend ? R.sg_start + R.sg_len : 0.0;
+        const double extend_to = seg_end < A.L ? seg_end : A.L;
+        const int limit = R.sg_limit;
+        int missing = 0;
+        for (int i = 0; i < n && do_extend; ++i) missing += data[i] == -1;
+        int leaf_status = 0;
+        if (missing == 0) leaf_status = 1;
+        if (missing == n) leaf_status = -1;
+
+        double updated_to = completing ? pos_prev : c->cur_pos;
+        if (!do_extend) updated_to = extend_to;             // completion only: the loop below does not run
+        double B = 0;
+        if (do_extend) {
+            if (leaf_status == -1) B = 0;
+            else if (leaf_status == 1) B = ln.Ltree;
+            else B = tracked_len_lane(ln, data, tmp0);
+        }
+
+        while (updated_to < extend_to) {
+            double new_to = extend_to < next_base ? extend_to : next_base;
+            double f = fastexp(-A.mu * B * (new_to - updated_to));
+            w_post *= f;
+            w_pilot *= f;
+            if (guided) {
+                // importance_weight_over_segment (particle.cpp:1138-1181)
+                const double dist = new_to - updated_to;
+                const double target_rate = dist * A.rho * ln.Ltree;
+                const double sampled_rate = dist * A.g_rho[ridx] * ln.Ltree;
+                const double iws = fastexp(sampled_rate - target_rate);
+                w_post *= iws;
+                w_pilot *= iws;
+            }
+            updated_to = new_to;
+            if (guided && updated_to < extend_to && ridx + 1 < A.g_K && updated_to == A.g_pos[ridx + 1]) {
+                // reached a change of the guide rate: no genealogy change, new draw under the new rate
+                ridx += 1;
+                next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
+                continue;
+            }
+            if (updated_to < extend_to) {
+                double* rec = rec_ptr(A, p, widx);
+                rec[0] = x_mark;
+                rec[1] = updated_to;
+                for (int r = 0; r < n - 1; ++r) rec[5 + r] = LS(ln, r);
+                int rp = 0, sb = 0;
+                double h, tc, sp_removed;
+                bool changed;
+                double iw = 1.0, rbiw = 1.0;
+                if (guided)
+                    sample_point_guided(ln, sBH, sBS, A.n_bias + 1, A.g_leaf + (size_t)ridx * n, A.rho / A.g_rho[ridx], &rp, &sb, &h,
+                                        &iw, &rbiw, tmp0);
+                else if (biased) { sample_point_biased(ln, sBH, sBS, A.n_bias + 1, &rp, &sb, &h, &iw); rbiw = iw; }
+                else sample_point(ln, &rp, &sb, &h);
+                const unsigned desc = A.lmap_opp ? lane_desc_mask(ln, LC(ln, rp, sb), tmp0) : 0u;
+                unsigned p0 = pl.idx;
+                double tfirst = 0.0;
+                unsigned span = 0;
+                mp_genealogy_rest<true, false>(ln, ml, pl, limit, rp, sb, h, &tc, &sp_removed, &changed, &tfirst, &span, desc, tmp0);
+                if (ln.vbc) { w_post *= ln.upd_fac; w_pilot *= ln.upd_fac; ln.upd_fac = 1.0; }
+                rec[2] = h;
+                rec[3] = piece_ref(p0, pl.idx - p0);
+                rec[4] = __longlong_as_double((long long)make_meta(0, mark_limit, limit, n, desc, span));
+                ++widx;
+                if (ml.err) break;
+                if (leaf_status == 0) B = tracked_len_lane(ln, data, tmp0);
+                if (leaf_status == 1) B = ln.Ltree;
+                if (biased) {
+                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
+                    const int nbands = A.n_bias + 1;
+                    const double delay_height = (A.delay_type & 3) == 0 ? h : ((A.delay_type & 3) == 2 ? tfirst : tc);
+                    int idx = 0;
+                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
+                    if (idx >= nbands) idx = nbands - 1;
+                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
+                    const double delay = A.app_delays[epoch_of(ln, delay_height)];
+                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+                }
+                next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
+                x_mark = updated_to;
+                mark_limit = limit;
+            }
+        }
+        mp_report(A, ml);
+        if (biased) {
+            // apply the factors that fell due during this extension (particle.cpp:910-916)
+            for (;;) {
+                if (ds.count == 0 || !do_extend) break;
+                double pm = ds.pos[0];
+                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
+                if (!(pm < extend_to)) break;
+                d_apply_earliest(ds, w_pilot);
+            }
+            st.dcount[p] = ds.count;
+            st.total_delayed[p] = ds.total;
+            if (guided) st.ridx[p] = ridx;
+            has_pending = ds.count > 0;
+        }
+
+        if (do_extend && R.sg_state == 0) {
+            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
+            const bool dephase = A.flags & 2;
+            const bool anc = A.flags & 1;
+            unsigned one_mask = 0, zero_mask = 0, het_pairs = 0;
+            int ncfg = 1;
+            for (int i = 0; i < n; ++i) {
+                if (data[i] == 1) one_mask |= 1u << i;
+                if (data[i] == 0) zero_mask |= 1u << i;
+            }
+            for (int i = 0; i + 1 < n; i += 2) {
+                bool het = (data[i] == 2) || (dephase && data[i] + data[i + 1] == 1);
+                if (het) {
+                    ncfg *= 2;
+                    het_pairs |= 1u << i;
+                    one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
+                    zero_mask |= 1u << i;
+                    one_mask |= 1u << (i + 1);
+                }
+            }
+            double norm = 1.0 / (double)ncfg;
+            double lik = 0;
+            for (;;) {
+                lik += site_lik_lane(ln, one_mask, zero_mask, anc, tmp0, tmp1);
+                if (ncfg == 1) break;
+                bool more = false;
+                for (int i = 0; i + 1 < n; i += 2) {
+                    if (!((het_pairs >> i) & 1)) continue;
+                    if ((zero_mask >> i) & 1) {
+                        zero_mask &= ~(1u << i); one_mask |= 1u << i;
+                        one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
+                        more = true;
+                        break;
+                    }
+                    one_mask &= ~(1u << i); zero_mask |= 1u << i;
+                    zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
+                }
+                if (!more) break;
+            }
+            lik *= norm;
+            w_post *= lik;
+            w_pilot *= lik;
+        }
+
+        for (int r = 0; r < n - 1; ++r) {
+            st.S[(size_t)r * A.Np + p] = LS(ln, r);
+            st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
+            st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
+        }
+        store_mp_state(A, st, ln, ml, p);
+        st.w_post[p] = w_post;
+        st.w_pilot[p] = w_pilot;
+        st.next_base[p] = next_base;
+        st.x_mark[p] = x_mark;
+        st.mark_limit[p] = mark_limit;
+        st.Ltree[p] = ln.Ltree;
+        A.rng_ctr[p] = ln.ctr;
+        A.ebuf[p] = ln.ebuf;
+        A.rg_widx[(size_t)cur * A.Np + p] = widx;
+        if (!do_extend) A.widx[p] = widx;              // the state goes back to the general kernels
+        A.pidx[p] = pl.idx;
+        pipe_log_ring_check(A, p, widx);
+    }
+    lds_pipe_partials(A, PR, cur, p, active, w_post, w_pilot, biased, has_pending);
+}

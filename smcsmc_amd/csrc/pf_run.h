@@ -46,7 +46,7 @@ static bool ends_data(const pf_handle* h, long long s) { return h->h_seg_start[s
 // run_many_refusal switch on it and choose by nothing else.  The values, and what each path launches, are with pf_get_run_path in smcsmc_pf.h.
 enum class RunPath {
     General = PF_PATH_GENERAL, TwoLaunch = PF_PATH_TWO_LAUNCH, KPipe = PF_PATH_K_PIPE, Sweep = PF_PATH_SWEEP, SweepSplit = PF_PATH_SWEEP_SPLIT,
-    SweepXmp = PF_PATH_SWEEP_XMP, SweepXl = PF_PATH_SWEEP_XL
+    SweepXmp = PF_PATH_SWEEP_XMP, SweepXl = PF_PATH_SWEEP_XL, SweepXlmp = PF_PATH_SWEEP_XLMP
 };
 
 // The look-ahead was loaded with PF_LA_ROW_PIPELINE and the handle is one the LOOK instances of k_sweep are built for: one population of at
@@ -79,6 +79,7 @@ static RunPath run_path(const pf_handle* h, bool many) {
     }
     if (h->rings == Rings::Xmp) return RunPath::SweepXmp;     // (create_impl gives these rings to no handle with -arg or a path switch)
     if (h->rings == Rings::Xl && many) return RunPath::SweepXl;
+    if (h->rings == Rings::Xlmp) return RunPath::SweepXlmp;   // (PF_FLAG_MP_LDS_ROWS; create_plan gives these rings to no handle with -arg or a path switch)
     return RunPath::General;
 }
 static bool runs_many(RunPath p) { return p >= RunPath::Sweep; }
@@ -117,13 +118,15 @@ static void with_count_instance(const pf_handle* h, F&& f) {
     else pick(ic<PF_PMAX>());
 }
 
-// k_sweep_blc<NM, P, BIASED>, the second launch of run_sweep_x: the LDS tree of one population, or a structured model in registers
+// k_sweep_blc<NM, P, BIASED>, the second launch of run_sweep_x: the LDS tree of one population, or a structured model in registers or on the LDS tree
 template <class F>
 static void with_blc_instance(const pf_handle* h, F&& f) {
     auto pick = [&](auto NM, auto P) { if (is_biased(h)) f(NM, P, std::true_type()); else f(NM, P, std::false_type()); };
     if (h->P == 1) pick(ic<PF_NMAX>(), ic<1>());
-    else if (h->P == 2) pick(ic<8>(), ic<2>());
-    else pick(ic<8>(), ic<PF_PMAX>());
+    else if (h->n <= 8) { if (h->P == 2) pick(ic<8>(), ic<2>()); else pick(ic<8>(), ic<PF_PMAX>()); }
+    // records sixteen wide: the structured models on the LDS tree (RunPath::SweepXlmp)
+    else if (h->P == 2) pick(ic<PF_NMAX>(), ic<2>());
+    else pick(ic<PF_NMAX>(), ic<PF_PMAX>());
 }
 
 static int launch_extend(pf_handle* h, long long s, int fuse = 0) {
@@ -406,7 +409,7 @@ static void launch_sweep(pf_handle* h, const dim3& grid, long long t) {
 // two handles pf_run_many accepts, each on its own, can share the launches of a step
 static bool sweep_compatible(const pf_handle* a, const pf_handle* b) {
     const RunPath path = run_path(a, true);
-    const bool x = path == RunPath::SweepXmp || path == RunPath::SweepXl;
+    const bool x = path == RunPath::SweepXmp || path == RunPath::SweepXl || path == RunPath::SweepXlmp;
     // the look-ahead: off in both, or the same level, flags (both bits) and table sizes in both (one kernel instance and one set of loop bounds a launch)
     const bool look = a->A.apf == b->A.apf && (a->A.apf == 0 || (a->la_flags == b->la_flags && a->A.la_D == b->A.la_D && a->A.la_Q == b->A.la_Q));
     return look && a->device == b->device && a->Np == b->Np && a->n == b->n && a->E == b->E && a->P == b->P && is_biased(a) == is_biased(b) &&
@@ -414,7 +417,7 @@ static bool sweep_compatible(const pf_handle* a, const pf_handle* b) {
            (a->A.dt_tab != nullptr) == (b->A.dt_tab != nullptr) &&
            // two launches a step: what they take from the leader (the extend launch's LDS -- n = 12 does not run with n = 16 -- and the capacities)
            (!x || (a->smem_sweep_x == b->smem_sweep_x && a->A.dcap == b->A.dcap && a->A.n_bias == b->A.n_bias)) &&
-           (path != RunPath::SweepXmp || (a->A.mcap == b->A.mcap && a->A.pcap == b->A.pcap));
+           ((path != RunPath::SweepXmp && path != RunPath::SweepXlmp) || (a->A.mcap == b->A.mcap && a->A.pcap == b->A.pcap));
 }
 
 // completion events of the last sixteen extend launches (ev_x) and of the last sixteen launches of the other roles (ev_blc)
@@ -716,11 +719,15 @@ static int run_sweep_split(pf_handle* const* hs, int nh, long long s_begin, long
 // launches), the other roles k_sweep_blc<16, 1, *>, and the table says so with SweepChunk::split = 1 (sweep_plan: the extend role
 // runs ahead).  Everything else -- the table, the seed, the two waits per step, the windows -- is shared line for line, which is why
 // this is one function with two launch sites and not a sibling (tests/test_gpu_sweep_lds.py).
-//   per step t:  [every 8 steps: stream waits blc_done(t - 7)]  k_sweep_xmp / k_sweep_xl(t) signalling x_done(t);
+// And a third pair: structured models on the LDS tree (RunPath::SweepXlmp: 9 to 16 haplotypes, handles created with PF_FLAG_MP_LDS_ROWS, pf_run and
+// pf_run_many alike).  The extend role is k_sweep_xlmp (pf_mp.hip: 64 particles a workgroup, tree and migration list in LDS), the other roles
+// k_sweep_blc<16, 2 or PF_PMAX, *>; the table is that of the structured models in registers (split = 0: sweep_plan knows by P > 1 that the extend
+// role runs ahead).  tests/test_gpu_sweep_structured_lds.py.
+//   per step t:  [every 8 steps: stream waits blc_done(t - 7)]  k_sweep_xmp / k_sweep_xl / k_sweep_xlmp(t) signalling x_done(t);
 //                cstream waits x_done(t - 1) (step 0: the seed); k_sweep_blc(t) signalling blc_done(t)
 static int run_sweep_x(pf_handle* const* hs, int nh, long long s_begin, long long s_end, RunPath path) {
     if (s_begin >= s_end) return 0;
-    const bool xl = path == RunPath::SweepXl;
+    const bool xl = path == RunPath::SweepXl, xlmp = path == RunPath::SweepXlmp;
     SweepFrame F(hs, nh, s_begin, true);
     pf_handle* h = F.h;
     if (F.join()) return -1;
@@ -733,11 +740,13 @@ static int run_sweep_x(pf_handle* const* hs, int nh, long long s_begin, long lon
                 const dim3 gx((unsigned)F.nb, (unsigned)nh), bx(PF_BS);
                 if (is_biased(h)) hipExtLaunchKernelGGL((k_sweep_xl<true>), gx, bx, h->smem_sweep_x, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t);
                 else hipExtLaunchKernelGGL((k_sweep_xl<false>), gx, bx, h->smem_sweep_x, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t);
+            } else if (xlmp) {
+                pf_mp_launch_sweep_xl(h->A, h->d_sweep, nh, t, h->smem_sweep_x, h->stream, F.x_done(t));
             } else {
                 pf_mp_launch_sweep_x(h->A, h->d_sweep, nh, t, h->smem_sweep_x, h->stream, F.x_done(t));
             }
         }
-        if (check_launch(xl ? "k_sweep_xl" : "k_sweep_xmp")) return -1;
+        if (check_launch(xl ? "k_sweep_xl" : (xlmp ? "k_sweep_xlmp" : "k_sweep_xmp"))) return -1;
         hipStreamWaitEvent(h->cstream, t >= 1 ? F.x_done(t - 1) : F.seeded, 0);
         const dim3 grid((unsigned)(1 + F.lc_wgs(t)), (unsigned)nh), blk(PF_BS);
         with_blc_instance(h, [&](auto NM, auto P, auto BIASED) {
@@ -756,16 +765,16 @@ static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles
     for (int k = 0; k < n_handles; ++k) {
         pf_handle* g = handles[k];
         if (!g) return "pf_run_many: null handle";
-        // Out of scope: structured models above 8 haplotypes, -arg above 8 haplotypes, a look-ahead without PF_LA_ROW_PIPELINE (one
+        // Out of scope: structured models above 8 haplotypes without PF_FLAG_MP_LDS_ROWS, -arg above 8 haplotypes, a look-ahead without PF_LA_ROW_PIPELINE (one
         // population) or PF_LA_ROW_PIPELINE_MP (structured) or on a handle that does not qualify for it (look_on_rows, look_on_rows_mp),
         // the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the general kernels
         if (!runs_many(run_path(g, true)))
             return "pf_run_many: the chunks must run on the row pipeline (one population of at most 16 haplotypes, or a structured model of two to "
-                   "four populations with the tree in registers, at most 8 haplotypes; a look-ahead only with PF_LA_ROW_PIPELINE on one "
+                   "four populations with the tree in registers, at most 8 haplotypes, or of 9 to 16 haplotypes created with PF_FLAG_MP_LDS_ROWS -- every chunk of the group then; a look-ahead only with PF_LA_ROW_PIPELINE on one "
                    "population of at most 8 haplotypes or with PF_LA_ROW_PIPELINE_MP on such a structured model, without focused sampling; "
                    "no -arg above 8 haplotypes, no debug switch that selects another path)";
         if (!sweep_compatible(h, g)) return "pf_run_many: the chunks must share device, particle count, haplotypes (and with them the form of the tree: registers up to 8, "
-                                              "LDS columns of one width from 9 to 16), epochs and options (the look-ahead among them: all without, or one level and one table size)";
+                                              "LDS columns of one width from 9 to 16), populations, epochs and options (mig_cap and piece_cap of a structured model among them, and the look-ahead: all without, or one level and one table size)";
         for (int j = 0; j < k; ++j) if (handles[j] == g) return "pf_run_many: a handle appears twice";
     }
     return nullptr;
@@ -814,7 +823,7 @@ static int run_on(RunPath path, pf_handle* const* hs, int nh, long long s_begin,
     case RunPath::KPipe: return run_pipeline(hs[0], s_begin, s_end);
     case RunPath::Sweep: return run_sweep(hs, nh, s_begin, s_end);
     case RunPath::SweepSplit: return run_sweep_split(hs, nh, s_begin, s_end);
-    case RunPath::SweepXmp: case RunPath::SweepXl: return run_sweep_x(hs, nh, s_begin, s_end, path);
+    case RunPath::SweepXmp: case RunPath::SweepXl: case RunPath::SweepXlmp: return run_sweep_x(hs, nh, s_begin, s_end, path);
     }
     return -1;
 }

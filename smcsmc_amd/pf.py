@@ -322,27 +322,31 @@ def probe_wave_prims(xd, xi, device=0):
 
 
 # pf_get_run_path (PF_PATH_* of smcsmc_pf.h, in order)
-RUN_PATHS = ("General", "TwoLaunch", "KPipe", "Sweep", "SweepSplit", "SweepXmp", "SweepXl")
+RUN_PATHS = ("General", "TwoLaunch", "KPipe", "Sweep", "SweepSplit", "SweepXmp", "SweepXl", "SweepXlmp")
 # pf_get_row_form (PF_ROW_FORM_*)
 ROW_FORMS = (None, "single", "paired")
 DEBUG_NO_PAIR = 4096
+FLAG_MP_LDS_ROWS = 8                 # pf_params.flags bit 3 (PF_FLAG_MP_LDS_ROWS): ParticleFilter(..., mp_rows=True)
 DEBUG_SIGNAL_ALL_COUNTS = 16384      # a completion signal on every second launch of a split step (A/B)
 
 
 class ParticleFilter:
     def __init__(self, model, np_particles, ess_fraction=0.5, seed=1, max_trace_events=64, device=0, local_recomb=False,
                  record_trees=False, log_cap=0, gen_cap=0, piece_cap=0, debug=0, mig_cap=0, count_wgs=0, delay_cap=0,
-                 delay_evict=False, count_workers=0):
+                 delay_evict=False, count_workers=0, mp_rows=False):
+        """mp_rows=True (PF_FLAG_MP_LDS_ROWS, off by default): a structured model of 9 to 16 haplotypes runs its rows on the row pipeline with tree
+        and migration list in LDS ("SweepXlmp": two launches a row, run() and run_many() alike) where it qualifies -- at most 131 072 particles, no
+        record_trees, no debug path, gen_cap of at least 20; on any other filter the flag means nothing and run_path() says what runs."""
         self.L = load_library()
         self._pack(model, np_particles, ess_fraction, seed, max_trace_events, local_recomb, record_trees, log_cap, gen_cap, piece_cap, debug,
-                   mig_cap, count_wgs, delay_cap, delay_evict, count_workers)
+                   mig_cap, count_wgs, delay_cap, delay_evict, count_workers, mp_rows)
         self.h = self.L.pf_create(C.byref(self._model), C.byref(self._params), int(device))
         if not self.h:
             raise PfError(_err(self.L))
         self.n_segs = 0
 
     def _pack(self, model, np_particles, ess_fraction=0.5, seed=1, max_trace_events=64, local_recomb=False, record_trees=False, log_cap=0,
-              gen_cap=0, piece_cap=0, debug=0, mig_cap=0, count_wgs=0, delay_cap=0, delay_evict=False, count_workers=0):
+              gen_cap=0, piece_cap=0, debug=0, mig_cap=0, count_wgs=0, delay_cap=0, delay_evict=False, count_workers=0, mp_rows=False):
         """the pf_model and pf_params of a filter, and the arrays behind them"""
         m = model
         self._ct = np.ascontiguousarray(m["change_times"], dtype=np.float64)
@@ -361,7 +365,7 @@ class ParticleFilter:
         _attach_structure(self, self._model, m, E, P)
         self.loci_length = float(m["loci_length"])
         self._params = _Params(self.Np, float(ess_fraction), int(seed), self.max_trace_events,
-                               (1 if local_recomb else 0) | (2 if record_trees else 0) | (4 if delay_evict else 0),
+                               (1 if local_recomb else 0) | (2 if record_trees else 0) | (4 if delay_evict else 0) | (FLAG_MP_LDS_ROWS if mp_rows else 0),
                                int(log_cap), int(gen_cap), int(piece_cap), int(debug), int(mig_cap), int(count_wgs), int(delay_cap), int(count_workers), 0)
         self.mig_cap = int(mig_cap) if mig_cap else 96
 
@@ -421,7 +425,8 @@ class ParticleFilter:
         of a row cover all of them (pf_run_many).  One-population chunks of at most 16 haplotypes (from 9 on the tree lives in LDS:
         one extend launch and one launch of the other roles per row for all chunks, no tree recording above 8 haplotypes, and all chunks of a group
         have the same number of haplotypes), or chunks of a structured model (two to four populations, at most 8 haplotypes: the
-        same two launches); no tree recording with structure.  A look-ahead only when every filter of the group loaded it with
+        same two launches; 9 to 16 haplotypes when every filter of the group was made with mp_rows=True, all with one number of haplotypes,
+        populations and mig_cap); no tree recording with structure.  A look-ahead only when every filter of the group loaded it with
         pipeline=True (one population) or structured=True (structured models) and qualifies for it (load_lookahead), all with the same level and table sizes -- or none has one.  With record_trees, one population of at most 8 haplotypes
         is taken (all filters of the group recording; log_cap / gen_cap may differ between them), and sample_tree_events() after
         run_many + finish returns what it returns after run().  A chunk with fewer rows stops at its end and sits later
@@ -434,7 +439,7 @@ class ParticleFilter:
     @staticmethod
     def can_run_many(filters):
         """True when run_many would take these filters (pf_can_run_many); otherwise run them one after the other with run():
-        more than 16 haplotypes, a structured model above 8, a look-ahead loaded without pipeline=True / structured=True (or on a filter that does
+        more than 16 haplotypes, a structured model above 8 made without mp_rows=True, a look-ahead loaded without pipeline=True / structured=True (or on a filter that does
         not qualify for it, or of another level than its neighbour's, or beside a filter without one), tree recording above 8 haplotypes or with structure,
         a debug path, or chunks that differ in shape (12 haplotypes do not run with 16, nor 9 to 16 with 8 or fewer, nor a
         tree-recording filter with a plain one)."""
@@ -662,7 +667,7 @@ def calibrated_lags(model, lag_fraction=2.0, seed=1, device=0, debug=0):
 # ---- what pf_create refuses and plans, without a device (pf_test_plan) ----
 PLAN_FIELDS = ("rings", "nslots", "draw_table", "smem", "smem_pipe", "ledger_wgs", "ncw", "workers", "split_batch", "mcap", "dcap", "pcap", "RS",
                "ncol", "max_trace_events", "E")
-RINGS = (None, "Reg", "Xmp", "Xl")
+RINGS = (None, "Reg", "Xmp", "Xl", "Xlmp")
 
 
 def plan(model, np_particles, tweak=None, **kw):
