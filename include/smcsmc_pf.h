@@ -189,6 +189,16 @@ typedef struct pf_lookahead {
  * structured one; a later pf_load_lookahead without the bit returns the handle to the general kernels, one with level 0 to the plain
  * rows of PF_PATH_SWEEP_XMP. */
 #define PF_LA_ROW_PIPELINE_MP 2
+/* pf_lookahead.flags bit 2: the same on the per-lane LDS tree, 9 to 16 haplotypes -- run the look-ahead inside the extend role of the
+ * LDS-tree row pipelines (the LOOK instances k_sweep_xl<false, true> and k_sweep_xlmp<false, true>, with the dynamic LDS of the plain
+ * instances; two launches per row as without a look-ahead) where the handle qualifies: one population of 9 to 16 haplotypes with the rings
+ * of PF_PATH_SWEEP_XL (taken by pf_run_many only; pf_run stays on the general kernels as for every such handle), or a structured model
+ * of 9 to 16 haplotypes created with PF_FLAG_MP_LDS_ROWS (PF_PATH_SWEEP_XLMP, pf_run and pf_run_many); no focused sampling, no guide,
+ * no -arg, no debug switch that selects a path.  Any other handle keeps the general kernels, without an error: pf_get_run_path tells.
+ * Same bits either way (tests/test_gpu_lookahead_rows_lds.py).  Bit 2 means nothing on a handle with the tree in registers (at most 8
+ * haplotypes), and bits 0 and 1 mean nothing on these handles; a later pf_load_lookahead without the bit returns the handle to the
+ * general kernels, one with level 0 to the plain rows of its path. */
+#define PF_LA_ROW_PIPELINE_LDS 4
 
 typedef struct pf_handle pf_handle;
 
@@ -250,7 +260,7 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * most 8 haplotypes, no -arg; a look-ahead as said below) are taken too: one extend launch (k_sweep_xmp, grid = particle blocks x chunks) and one
  * launch of the bookkeeping, ledger and count roles (k_sweep_blc) per row for all chunks; such chunks must also share mig_cap,
  * piece_cap, delay_cap and the number of bias bands, and cannot be mixed with one-population chunks.
- * One population with 9 to 16 haplotypes (the tree in per-lane LDS columns; no look-ahead, no -arg, at most 131 072 particles, no debug
+ * One population with 9 to 16 haplotypes (the tree in per-lane LDS columns; a look-ahead only with PF_LA_ROW_PIPELINE_LDS, no -arg, at most 131 072 particles, no debug
  * switch that selects a path) is taken the same way: one extend launch (k_sweep_xl, 256 particles per workgroup x chunks) and one
  * launch of the other roles (k_sweep_blc<16, 1, *>) per row for all chunks.  Such chunks must have the same number of haplotypes (the
  * width of the tree columns is the launch's LDS size: 12 does not run with 16, nor either with 8 or fewer), delay_cap and bias bands.
@@ -259,6 +269,8 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * population, at most 8 haplotypes, no focused sampling, no -arg): k_sweep<..., LOOK>, one launch per row for pf_run and pf_run_many alike,
  * also at four haplotypes and fewer; or with PF_LA_ROW_PIPELINE_MP on a structured handle that qualifies (two to four populations, at most 8
  * haplotypes, no focused sampling, no -arg): k_sweep_xmp<..., LOOK> in place of k_sweep_xmp, for pf_run and pf_run_many alike.  The
+ * same on the LDS tree with PF_LA_ROW_PIPELINE_LDS: one population of 9 to 16 haplotypes (k_sweep_xl<false, true>, pf_run_many only) and
+ * structured models created with PF_FLAG_MP_LDS_ROWS (k_sweep_xlmp<false, true>, pf_run and pf_run_many), no focused sampling.  The
  * handles of a group then agree in it: all without a look-ahead, or all with the same flags, level, max_doubletons and n_quantiles.
  * Structured models of 9 to 16 haplotypes are taken with PF_FLAG_MP_LDS_ROWS (the chunks then agree on haplotypes, populations, mig_cap and the flag).
  * Not taken: structured models above 8 haplotypes without that flag, -arg with structure or above 8 haplotypes, a look-ahead without its bit or on a handle
@@ -271,14 +283,14 @@ int pf_run_many(pf_handle* const* handles, int32_t n_handles, int64_t s_begin, i
  * pipeline does not apply to one of them -- a structured model with more than 8 haplotypes (the LDS tree) without PF_FLAG_MP_LDS_ROWS, -arg with structure
  * (at any number of haplotypes: such handles run on the general path, row kernel -> k_decide -> k_resample),
  * one population with more than 16 haplotypes, or with 9 to 16 and -arg, look-ahead, more than 131 072 particles, a debug path, or a
- * look-ahead loaded without PF_LA_ROW_PIPELINE (one population) or PF_LA_ROW_PIPELINE_MP (structured) or on a handle that does not qualify for it -- or they
+ * look-ahead loaded without PF_LA_ROW_PIPELINE (one population) or PF_LA_ROW_PIPELINE_MP (structured) or PF_LA_ROW_PIPELINE_LDS (9 to 16 haplotypes) or on a handle that does not qualify for it -- or they
  * differ in shape: one with a look-ahead and one without, or look-aheads of two levels, flags or table sizes, haplotypes between 9 and 16 included, or 9 to 16 mixed with 8 or fewer, or structured mixed with one-population chunks,
  * or a tree-recording handle mixed with a plain one).  One population with at most 8 haplotypes and -arg IS taken, whatever the chunks'
  * log_cap / gen_cap. */
 int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 /* Which runner takes the rows of this handle as it stands now (a look-ahead loaded later changes the answer): pf_run's with many == 0,
  * pf_run_many's otherwise, where -1 says that pf_run_many refuses the handle.  DESIGN.md, "Which path runs when". */
-#define PF_PATH_GENERAL     0    /* one launch per role and row, two streams (every model; a look-ahead loaded without PF_LA_ROW_PIPELINE / PF_LA_ROW_PIPELINE_MP, or with it on a handle that does not qualify) */
+#define PF_PATH_GENERAL     0    /* one launch per role and row, two streams (every model; a look-ahead loaded without PF_LA_ROW_PIPELINE / PF_LA_ROW_PIPELINE_MP / PF_LA_ROW_PIPELINE_LDS, or with it on a handle that does not qualify) */
 #define PF_PATH_TWO_LAUNCH  1    /* k_row + k_decide_ledger (PF_DEBUG_TWO_LAUNCH, or more than 131 072 particles) */
 #define PF_PATH_K_PIPE      2    /* k_pipe (PF_DEBUG_K_PIPE) */
 #define PF_PATH_SWEEP       3    /* k_sweep: every role of a step in one launch */
@@ -287,7 +299,9 @@ int pf_can_run_many(pf_handle* const* handles, int32_t n_handles);
 #define PF_PATH_SWEEP_XMP   5    /* k_sweep_xmp + k_sweep_blc: structured models, at most 8 haplotypes */
 /*                               (also a look-ahead loaded with PF_LA_ROW_PIPELINE_MP on a qualifying structured handle: k_sweep_xmp<..., LOOK>) */
 #define PF_PATH_SWEEP_XL    6    /* k_sweep_xl + k_sweep_blc: one population, 9 to 16 haplotypes, pf_run_many only */
+/*                               (also a look-ahead loaded with PF_LA_ROW_PIPELINE_LDS on a qualifying handle: k_sweep_xl<false, true>) */
 #define PF_PATH_SWEEP_XLMP  7    /* k_sweep_xlmp + k_sweep_blc: structured models, 9 to 16 haplotypes, only with PF_FLAG_MP_LDS_ROWS; pf_run and pf_run_many */
+/*                               (also a look-ahead loaded with PF_LA_ROW_PIPELINE_LDS on a qualifying handle: k_sweep_xlmp<false, true>) */
 int pf_get_run_path(pf_handle* h, int many);
 /* Which form of the row kernel the last pf_run / pf_run_many call ran for this handle's rows on PF_PATH_SWEEP_SPLIT: the paired form (a weight
  * wavefront beside each tree wavefront, 128 particles a workgroup) runs when every extend workgroup of the call can have a compute unit of its

@@ -51,7 +51,7 @@ static void dump_model_json(const PfParam& p) {
     }
     cout << "], \"sample_pops\": [";
     for (size_t k = 0; k < m.sample_pops.size(); ++k) cout << (k ? ", " : "") << m.sample_pops[k];
-    cout << "], \"apf\": " << p.apf_level << ", \"apf_pipeline\": " << (p.apf_pipeline ? "true" : "false") << ", \"mp_rows\": " << (p.mp_rows ? "true" : "false") << ", \"record_mask\": [";
+    cout << "], \"apf\": " << p.apf_level << ", \"apf_pipeline\": " << (p.apf_pipeline ? "true" : "false") << ", \"mp_rows\": " << (p.mp_rows ? "true" : "false") << ", \"apf_lds\": " << (p.apf_lds ? "true" : "false") << ", \"record_mask\": [";
     for (size_t k = 0; k < p.record_mask.size(); ++k) cout << (k ? ", " : "") << p.record_mask[k];
     cout << "], \"guide_positions\": [";
     for (size_t k = 0; k < p.guide_positions.size(); ++k) cout << (k ? ", " : "") << p.guide_positions[k];
@@ -304,6 +304,7 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
         memset(&pl, 0, sizeof(pl));
         pl.level = P.apf_level; pl.max_doubletons = la.max_doubletons; pl.n_quantiles = 7; pl.n = sg.n;
         pl.flags = P.apf_pipeline ? (PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP) : 0;      // (each bit means something on its own kind of model only)
+        if (P.apf_lds) pl.flags |= PF_LA_ROW_PIPELINE_LDS;                                  // (9 to 16 haplotypes, the tree in LDS)
         pl.first_singleton_distance = la.first_singleton_distance.data();
         pl.relative_mutation_rate = la.relative_mutation_rate.data();
         pl.is_singleton_unphased = la.is_singleton_unphased.data();
@@ -625,9 +626,12 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
     // the chunks of a structured model too (pf_run_many), but this binary keeps filtering those one after the other
     // until lockstep has been measured not slower than that at four chunks (section 7: not measured yet) -- npop == 1 below is the switch.
     // -mp_rows is the caller's own switch for structured models of 9 to 16 haplotypes: their chunks then share the launches of a row whenever
-    // pf_can_run_many says so (no -arg, no look-ahead); structured chunks of at most 8 haplotypes keep their default
-    const bool one_pop_rows = P.model.npop == 1 && P.model.nsam <= 16 && (P.apf_level == 0 || P.apf_pipeline) && !(P.record_trees && P.model.nsam > 8);
-    const bool mp_rows = P.mp_rows && P.model.npop > 1 && P.model.nsam > 8 && P.model.nsam <= 16 && P.apf_level == 0 && !P.record_trees;
+    // pf_can_run_many says so (no -arg, a look-ahead only with -apf_lds); structured chunks of at most 8 haplotypes keep their default.
+    // -apf_lds is the look-ahead's switch from 9 haplotypes on, as -apf_pipeline is up to 8.  (-apf_pipeline above 8 haplotypes keeps opening
+    // the group that pf_can_run_many then refuses, as it always has: its log line stays what it was.)
+    const bool apf_rows = P.apf_level == 0 || P.apf_pipeline || (P.model.nsam > 8 && P.apf_lds);
+    const bool one_pop_rows = P.model.npop == 1 && P.model.nsam <= 16 && apf_rows && !(P.record_trees && P.model.nsam > 8);
+    const bool mp_rows = P.mp_rows && P.model.npop > 1 && P.model.nsam > 8 && P.model.nsam <= 16 && (P.apf_level == 0 || P.apf_lds) && !P.record_trees;
     const bool lockstep = one_pop_rows || mp_rows;
     std::mutex notes_lock;
     auto rank_main = [&](int r) {

@@ -306,8 +306,13 @@ const std::vector<DriverOption>& driver_options() {
         // not a reference flag: structured models of 9 to 16 haplotypes on the row pipeline with tree and migration list in LDS (pf_params.flags bit 3,
         // PF_FLAG_MP_LDS_ROWS; include/smcsmc_pf.h): two launches a row instead of five, lockstep with -chunks; same bits as without.  Off until
         // measured: DESIGN.md section 7
-        {"-mp_rows", "", "Several chunks", "Structured models of 9 to 16 haplotypes: rows on the row pipeline, chunks of a rank side by side (no -arg, no -apf; same results) [ off ]",
+        {"-mp_rows", "", "Several chunks", "Structured models of 9 to 16 haplotypes: rows on the row pipeline, chunks of a rank side by side (no -arg; -apf only with -apf_lds; same results) [ off ]",
          [](PfParam& p, const std::string&) { p.mp_rows = true; }},
+        // not a reference flag: the look-ahead of -apf in the extend role of the LDS-tree row pipelines (pf_lookahead.flags bit 2,
+        // PF_LA_ROW_PIPELINE_LDS; include/smcsmc_pf.h): one population of 9 to 16 haplotypes in lockstep with -chunks, structured models of that
+        // size with -mp_rows; same bits as without.  Off until measured: DESIGN.md section 7
+        {"-apf_lds", "", "Several chunks", "With -apf: look-ahead inside the row pipeline at 9 to 16 haplotypes (one population with -chunks; structured models with -mp_rows; same results) [ off ]",
+         [](PfParam& p, const std::string&) { p.apf_lds = true; }},
         // not a reference flag: room for migration events on one local tree (the reference's node list is unbounded)
         {"-migcap", "INT", "Several populations", "Migration events one local tree may hold; about 230 fit the LDS with 32 epochs [ 96 ]",
          [](PfParam& p, const std::string& v) { p.mig_cap = convert<int>("-migcap", v); if (p.mig_cap < 1) throw OutOfRange("-migcap", v); }},

@@ -193,7 +193,8 @@ class PfParam {
     bool ancestral_aware = false, dephase = false;
     int apf_level = 0;
     bool mp_rows = false;          // -mp_rows: pf_params.flags bit 3 (PF_FLAG_MP_LDS_ROWS; means something only for a structured model of 9 to 16 haplotypes)
-    bool apf_pipeline = false;     // -apf_pipeline: pf_lookahead.flags = PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP (means something only with -apf > 0)
+    bool apf_lds = false;          // -apf_lds: pf_lookahead.flags |= PF_LA_ROW_PIPELINE_LDS (means something only with -apf > 0 at 9 to 16 haplotypes)
+    bool apf_pipeline = false;    // -apf_pipeline: pf_lookahead.flags = PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP (means something only with -apf > 0)
     double start_position = 1;
     double tmax = 2;
     bool cap_sizes = false;

@@ -414,7 +414,8 @@ static int create_prepare(pf_handle* h, const pf_params* p) {
         most = std::max(most, (int)h->smem);
         if (most > 64 * 1024 &&
             (hipFuncSetAttribute((const void*)k_sweep_xl<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
-             hipFuncSetAttribute((const void*)k_sweep_xl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)) {
+             hipFuncSetAttribute((const void*)k_sweep_xl<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+             hipFuncSetAttribute((const void*)k_sweep_xl<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess)) {
             (void)hipGetLastError();
             demote();
         }

@@ -33,11 +33,12 @@ struct pf_handle {
     long long Np = 0;
     int nblocks = 0;
     size_t smem = 0, smem_la = 0;
+    bool la_xl = false;           // the look-ahead of the general kernels is k_lookahead_xl (15 and 16 haplotypes: k_lookahead's LDS is more than a workgroup has)
     int max_trace_events = 0;
     bool finished = false;
     bool fin_pending = false;     // k_count partials not yet folded into the totals
     Windows step_windows;         // windows of the step being processed
-    int la_flags = 0;             // pf_lookahead.flags of the look-ahead in force (PF_LA_ROW_PIPELINE, PF_LA_ROW_PIPELINE_MP; 0 without one)
+    int la_flags = 0;             // pf_lookahead.flags of the look-ahead in force (PF_LA_ROW_PIPELINE, PF_LA_ROW_PIPELINE_MP, PF_LA_ROW_PIPELINE_LDS; 0 without one)
     bool pair_lds_set = false;    // the LDS limit of k_sweep4p has been raised for this handle's instance (run_sweep_split)
     int row_form = 0;             // PF_ROW_FORM_*: what the last call ran (pf_get_row_form)
     int debug = 0;                // pf_params.debug: the PF_DEBUG_* switches that select a path are read from here (run_path)
@@ -368,9 +369,14 @@ int pf_load_lookahead(pf_handle* h, const pf_lookahead* la) {
     A.la_fsd = fsd; A.la_rmr = rmr; A.la_unph = unph; A.la_nd = nd; A.la_didx = didx; A.la_ddist = ddist;
     A.la_split = split; A.la_salleles = sal; A.la_sk = sk; A.la_q = q; A.la_tbl = tbl;
     A.la_mean_tbl = la->mean_total_branch_length;
-    h->la_flags = la->flags & (PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP);      // (with the load: a later one without the bits returns the handle to the general kernels)
+    h->la_flags = la->flags & (PF_LA_ROW_PIPELINE | PF_LA_ROW_PIPELINE_MP | PF_LA_ROW_PIPELINE_LDS);      // (with the load: a later one without the bits returns the handle to the general kernels)
     h->smem_la = smem_bytes_la(n, h->E);
-    if (h->smem_la > 64 * 1024) hipFuncSetAttribute((const void*)k_lookahead, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_la);
+    // 15 and 16 haplotypes: k_lookahead's scratch columns do not fit beside the tree; k_lookahead_xl keeps them inside the tree's own scratch
+    h->la_xl = h->smem_la > 160 * 1024;
+    if (h->la_xl) {
+        h->smem_la = smem_bytes(n, h->E);
+        if (h->smem_la > 64 * 1024) hipFuncSetAttribute((const void*)k_lookahead_xl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_la);
+    } else if (h->smem_la > 64 * 1024) hipFuncSetAttribute((const void*)k_lookahead, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->smem_la);
     return 0;
 }
 

@@ -2509,7 +2509,8 @@ __global__ __launch_bounds__(PF_BS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 // sits the call out leaves before it touches LDS or memory other than its table entry.  The bookkeeping, ledger and count
 // roles of the step are k_sweep_blc<16, 1, *> on the counting stream: in one launch every count workgroup would be given the
 // extend workgroups' tree columns (100 KB at 16 haplotypes) and one would fit a compute unit.
-template <bool BIASED>
+// (LOOK: with the look-ahead factor in the extend role -- pf_lookahead.flags bit 2; BIASED = false)
+template <bool BIASED, bool LOOK = false>
 __global__ __launch_bounds__(PF_BS) void k_sweep_xl(const SweepChunk* tab_g, long long t) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[pf_chunk()];
@@ -2519,7 +2520,7 @@ __global__ __launch_bounds__(PF_BS) void k_sweep_xl(const SweepChunk* tab_g, lon
     if (!sweep_plan(ch, s, 0, PL)) return;
     if (!(PL.row.extend || PL.row.complete)) return;
     extern __shared__ double smem[];
-    extend_lds_pipe_body<BIASED>(A, s, PL.row, smem);
+    extend_lds_pipe_body<BIASED, LOOK>(A, s, PL.row, smem);
 }
 
 // first step of a call: the seed of k_pipe_seed, and the chunk's window state
@@ -2857,6 +2858,63 @@ __global__ __launch_bounds__(PF_BS) void k_lookahead(KArgs A, long long row) {
             double pp = p_nochange * p_splitdata + (1.0 - p_nochange) * p_correct_split * mut_rate * split_branch_length;
             likelihood *= pp;
         }
+        // removeLookaheadLikelihood + includeLookaheadLikelihood (particle.hpp:182, particle.cpp:614-616)
+        w_pilot = st.w_pilot[p];
+        w_pilot /= st.lookahead[p];
+        double la_w = 1.0;
+        la_w *= likelihood;
+        w_pilot *= likelihood;
+        st.lookahead[p] = la_w;
+        st.w_pilot[p] = w_pilot;
+    }
+    double sq = wave_tree_sum(w_pilot * w_pilot);
+    double sc = wave_hs_scan(w_pilot, lane);
+    double scm = wave_max_scan_d(sc, lane);
+    long long chunk = p >> 6;
+    if (active) { A.scan1[p] = sc; A.scan1m[p] = scm; }
+    if (lane == 63 && chunk < (A.Np + 63) / 64) {
+        A.chunk_sq[chunk] = sq;
+        A.chunk_pil[chunk] = sc;
+        A.chunk_mx1[chunk] = scm;
+    }
+}
+
+// k_lookahead where its scratch columns do not fit beside the tree: at 15 and 16 haplotypes smem_bytes_la is more than the 160 KB a
+// workgroup can have (16 haplotypes, 256 lanes: 100 KB of tree columns and 80 KB of scratch), and the launch above is refused.  The same
+// factor through look_factor_lds (pf_look_lds.h: k_lookahead's statements with the scratch inside the columns t0 / t1), in the LDS of
+// k_extend; the migration events of a structured model are read from the state, as k_lookahead reads them.  Everything around the factor
+// is k_lookahead's, statement for statement.  pf_load_lookahead picks it (pf_handle::la_xl) only where k_lookahead cannot run.
+struct LookMigG {
+    static constexpr bool on = true;
+    const DState& st;
+    long long p, Np;
+    __device__ __forceinline__ int count() const { return st.nm[p]; }
+    __device__ __forceinline__ int branch(int mi) const { return st.Mb[(size_t)mi * Np + p]; }
+    __device__ __forceinline__ double time(int mi) const { return st.Mt[(size_t)mi * Np + p]; }
+};
+__global__ __launch_bounds__(PF_BS) void k_lookahead_xl(KArgs A, long long row) {
+    extern __shared__ double smem[];
+    Smem m = carve(smem, A.n, A.E);
+    load_model(A, m);
+    __syncthreads();
+    const Ctrl* c = A.ctrl;
+    const int n = A.n;
+    const long long p = (long long)blockIdx.x * PF_BS + threadIdx.x;
+    const bool active = p < A.Np;
+    const int lane = threadIdx.x & 63;
+    double w_pilot = 0.0;
+    if (active) {
+        const DState st = state_slot(A, __builtin_amdgcn_readfirstlane(c->cur));
+        Lane ln = make_lane(A, m, p);
+        for (int r = 0; r < n - 1; ++r) {
+            LS(ln, r) = st.S[(size_t)r * A.Np + p];
+            LC(ln, r, 0) = st.C[(size_t)(2 * r) * A.Np + p];
+            LC(ln, r, 1) = st.C[(size_t)(2 * r + 1) * A.Np + p];
+        }
+        const double Ltree = st.Ltree[p];
+        double likelihood;
+        if (A.P > 1) likelihood = look_factor_lds(A, ln, row, Ltree, m.t0 + threadIdx.x, m.t1 + threadIdx.x, LookMigG{st, p, A.Np});
+        else likelihood = look_factor_lds(A, ln, row, Ltree, m.t0 + threadIdx.x, m.t1 + threadIdx.x);
         // removeLookaheadLikelihood + includeLookaheadLikelihood (particle.hpp:182, particle.cpp:614-616)
         w_pilot = st.w_pilot[p];
         w_pilot /= st.lookahead[p];

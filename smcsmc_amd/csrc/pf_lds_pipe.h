@@ -15,6 +15,7 @@
 #include "pf_types.h"
 #include "pf_lane.h"
 #include "pf_pipe.h"
+#include "pf_look_lds.h"
 
 // load_model / make_lane for an argument block in either address space
 template <class KA>
@@ -308,8 +309,14 @@ __device__ __forceinline__ void lds_pipe_partials(const KA& A, const PipeRow& PR
 }
 
 // BIASED: focused sampling or a guide (the delayed-factor store, the guide's segment index)
-template <bool BIASED, class KA>
+// LOOK (without BIASED; k_sweep_xl<false, true>, pf_lookahead.flags bit 2): the auxiliary particle filter's look-ahead factor (look_factor_lds,
+// pf_look_lds.h = k_lookahead) enters the pilot weight behind the site likelihood and in front of the state stores and the wavefront
+// partials, so that the partials lds_pipe_decide reads in the next launch are those k_lookahead leaves.  The previous factor travels with
+// the state: the slot's own, the parent's on a resampling row.  A completion-only launch applies none, reads no look-ahead row (its row may
+// lie past the table) and hands on the factor it carried.  No LDS beyond the plain instance's.
+template <bool BIASED, bool LOOK = false, class KA>
 __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, const PipeRow PR, double* smem) {
+    static_assert(!LOOK || !BIASED, "the look-ahead rides on the plain rows of k_sweep_xl");
     Smem m = carve(smem, A.n, A.E);
     __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
     const Ctrl* c = A.ctrl;
@@ -353,6 +360,8 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
         double x_mark = from.x_mark[a];
         int mark_limit = from.mark_limit[a];
         ln.Ltree = from.Ltree[a];
+        [[maybe_unused]] double la_prev = 1.0;
+        if constexpr (LOOK) la_prev = from.lookahead[a];       // the parent's on a resampling row, the slot's own otherwise
         ln.ctr = R.o_ctr;
         ln.ebuf = R.o_ebuf;
         unsigned widx = R.o_widx;
@@ -511,6 +520,18 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             lik *= norm;
             w_post *= lik;
             w_pilot *= lik;
+        }
+        if constexpr (LOOK) {
+            // removeLookaheadLikelihood + includeLookaheadLikelihood (particle.hpp:182, particle.cpp:614-616), as k_lookahead ends
+            double la_w = la_prev;
+            if (do_extend) {
+                const double likelihood = look_factor_lds(A, ln, s, ln.Ltree, tmp0, tmp1);
+                w_pilot /= la_prev;
+                la_w = 1.0;
+                la_w *= likelihood;
+                w_pilot *= likelihood;
+            }
+            st.lookahead[p] = la_w;          // (the slot the general kernels and the step API read when the call ends here)
         }
 
         for (int r = 0; r < n - 1; ++r) {

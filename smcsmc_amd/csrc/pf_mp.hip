@@ -420,7 +420,8 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
 // pf_mp_pipe.h): step t of the chunk table, blockIdx.y is the chunk, 64 particles a workgroup as in k_extend_mp.  A chunk that is finished or sits
 // the call out leaves before it touches LDS or memory other than its table entry.  The bookkeeping, ledger and count roles of the step are
 // k_sweep_blc<16, 2 or PF_PMAX, *> on the counting stream (pf_hip.hip).
-template <bool BIASED>
+// (LOOK: with the look-ahead factor in the extend role -- pf_lookahead.flags bit 2; BIASED = false)
+template <bool BIASED, bool LOOK = false>
 __global__ __launch_bounds__(PF_BS) void k_sweep_xlmp(const SweepChunk* tab_g, long long t) {
     SweepChunkC* tab = (SweepChunkC*)tab_g;
     SweepChunkC& ch = tab[pf_chunk()];
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(PF_BS) void k_sweep_xlmp(const SweepChunk* tab_g, l
     if (!sweep_plan(ch, s, 0, PL)) return;
     if (!(PL.row.extend || PL.row.complete)) return;
     extern __shared__ double smem[];
-    extend_mp_pipe_body<BIASED>(A, s, PL.row, smem);
+    extend_mp_pipe_body<BIASED, LOOK>(A, s, PL.row, smem);
 }
 
 // ------------------------------------------------------------------ structured models, register-resident tree (n <= 8)
@@ -1322,7 +1323,8 @@ int pf_mp_sweep_xl_prepare(size_t smem) {
     most = most > (int)smem ? most : (int)smem;
     if (most <= 64 * 1024) return 0;
     if (hipFuncSetAttribute((const void*)k_sweep_xlmp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_sweep_xlmp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess) {
+        hipFuncSetAttribute((const void*)k_sweep_xlmp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_sweep_xlmp<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, most) != hipSuccess) {
         (void)hipGetLastError();
         return -1;
     }
@@ -1330,7 +1332,9 @@ int pf_mp_sweep_xl_prepare(size_t smem) {
 }
 void pf_mp_launch_sweep_xl(const KArgs& A, const SweepChunk* tab, int nchunks, long long t, size_t smem, hipStream_t st, hipEvent_t done) {
     const dim3 grid(mp_blocks(A.Np), (unsigned)nchunks), blk(PF_BS);
-    if (A.n_bias > 0 || A.g_K > 0) hipExtLaunchKernelGGL((k_sweep_xlmp<true>), grid, blk, smem, st, nullptr, done, 0, tab, t);
+    // a look-ahead on this path (run_path: look_on_rows_lds, never with focused sampling): the LOOK instance, the same launch otherwise
+    if (A.apf > 0) hipExtLaunchKernelGGL((k_sweep_xlmp<false, true>), grid, blk, smem, st, nullptr, done, 0, tab, t);
+    else if (A.n_bias > 0 || A.g_K > 0) hipExtLaunchKernelGGL((k_sweep_xlmp<true>), grid, blk, smem, st, nullptr, done, 0, tab, t);
     else hipExtLaunchKernelGGL((k_sweep_xlmp<false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
 }
 void pf_mp_launch_init(const KArgs& A, double initial_position, size_t smem, hipStream_t st) {

@@ -7,9 +7,19 @@
 //   the gather: tree, node populations and the migration list of the parent into this lane's LDS columns
 //   the row: k_extend_mp's statements (sample_point*, mp_genealogy_rest and the walk of pf_mp.h), from "the row" on; a fix to one belongs in
 //            both, tests/test_gpu_sweep_structured_lds.py holds them together through the oracle, bit for bit
-// No -arg and no look-ahead on this path (create_plan, run_path).
+// No -arg on this path (create_plan, run_path).  A look-ahead: the LOOK instance (k_sweep_xlmp<false, true>), on handles whose look-ahead was
+// loaded with PF_LA_ROW_PIPELINE_LDS (run_path: look_on_rows_lds); without the bit such a handle goes to the general kernels.
 #pragma once
 #include "pf_lds_pipe.h"
+
+// the lane's migration events (LDS columns, sorted by time) as look_factor_lds reads them
+struct LookMigL {
+    static constexpr bool on = true;
+    const MLane& ml;
+    __device__ __forceinline__ int count() const { return ml.nm; }
+    __device__ __forceinline__ int branch(int mi) const { return LMb(ml, mi); }
+    __device__ __forceinline__ double time(int mi) const { return LMt(ml, mi); }
+};
 
 // Where the decision's tables go: into the lanes' migration-time column (mcap * 64 doubles, loaded once the previous row is decided) when they
 // fit there, behind everything else otherwise (a small mig_cap).  Dynamic LDS of the launch; 0: more than the 160 KB of a workgroup.
@@ -20,8 +30,12 @@ static size_t smem_bytes_mp_pipe(int n, int E, int P, int mcap, int nc) {
 }
 
 // BIASED: focused sampling or a guide (the delayed-factor store, the guide's segment index)
-template <bool BIASED, class KA>
+// LOOK (without BIASED; k_sweep_xlmp<false, true>, pf_lookahead.flags bit 2): the look-ahead factor in the pilot weight, as in
+// extend_lds_pipe_body<..., LOOK>, with the lane's migration events for the height of a leaf's branch (LookMigL).  Its scratch lies in the
+// lane's columns t0 and t1, never in the decision's tables (dead by then, inside the event list or behind the state).
+template <bool BIASED, bool LOOK = false, class KA>
 __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, const PipeRow PR, double* smem) {
+    static_assert(!LOOK || !BIASED, "the look-ahead rides on the plain rows of k_sweep_xlmp");
     Smem m = carve(smem, A.n, A.E);
     SmemMP mm = carve_mp(smem, A.n, A.E, A.P, A.mcap);
     __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
@@ -71,6 +85,8 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
         double x_mark = from.x_mark[a];
         int mark_limit = from.mark_limit[a];
         ln.Ltree = from.Ltree[a];
+        [[maybe_unused]] double la_prev = 1.0;
+        if constexpr (LOOK) la_prev = from.lookahead[a];       // the parent's on a resampling row, the slot's own otherwise
         ln.ctr = R.o_ctr;
         ln.ebuf = R.o_ebuf;
         unsigned widx = R.o_widx;
@@ -238,6 +254,20 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
             lik *= norm;
             w_post *= lik;
             w_pilot *= lik;
+        }
+        if constexpr (LOOK) {
+            // removeLookaheadLikelihood + includeLookaheadLikelihood (particle.hpp:182, particle.cpp:614-616), as k_lookahead ends
+            double la_w = la_prev;
+            // (!ml.err: the one difference from k_lookahead, which takes every particle.  A lane whose event list overflowed left the loop above
+            // in the middle of an update, its tree half edited; the run ends with mp_report's error whatever its weight is)
+            if (do_extend && !ml.err) {
+                const double likelihood = look_factor_lds(A, ln, s, ln.Ltree, tmp0, tmp1, LookMigL{ml});
+                w_pilot /= la_prev;
+                la_w = 1.0;
+                la_w *= likelihood;
+                w_pilot *= likelihood;
+            }
+            st.lookahead[p] = la_w;          // (the slot the general kernels and the step API read when the call ends here)
         }
 
         for (int r = 0; r < n - 1; ++r) {

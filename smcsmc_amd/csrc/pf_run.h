@@ -65,11 +65,29 @@ static bool look_on_rows_mp(const pf_handle* h) {
            !dbg(h, PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_K_PIPE);
 }
 
+// And on the per-lane LDS tree, 9 to 16 haplotypes: the look-ahead was loaded with PF_LA_ROW_PIPELINE_LDS and the handle has the rings the LOOK
+// instances of k_sweep_xl (one population) or k_sweep_xlmp (structured, PF_FLAG_MP_LDS_ROWS) run on -- create_plan gives them to no handle with
+// -arg or a path switch, and the instances take the dynamic LDS of the plain ones, so every handle with the rings qualifies -- no focused
+// sampling and no guide
+static bool look_on_rows_lds(const pf_handle* h) {
+    return (h->la_flags & PF_LA_ROW_PIPELINE_LDS) && (h->rings == Rings::Xl || h->rings == Rings::Xlmp) && !is_biased(h) && !h->A.rec_trees &&
+           !dbg(h, PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_TWO_LAUNCH | PF_DEBUG_K_PIPE);
+}
+
 // `many`: as pf_run_many takes the handle (it refuses General, TwoLaunch and KPipe), otherwise as pf_run does
 static RunPath run_path(const pf_handle* h, bool many) {
     // the look-ahead (loaded after creation): on the general kernels, or by its flag in the extend role of k_sweep -- one launch a step at any
-    // number of haplotypes up to 8, like focused sampling -- or of k_sweep_xmp, the path a structured model has without a look-ahead
-    if (h->A.apf != 0) return look_on_rows(h) ? RunPath::Sweep : (look_on_rows_mp(h) ? RunPath::SweepXmp : RunPath::General);
+    // number of haplotypes up to 8, like focused sampling -- or of k_sweep_xmp, the path a structured model has without a look-ahead, or of
+    // k_sweep_xlmp / k_sweep_xl (the latter for pf_run_many only, as without a look-ahead)
+    if (h->A.apf != 0) {
+        if (look_on_rows(h)) return RunPath::Sweep;
+        if (look_on_rows_mp(h)) return RunPath::SweepXmp;
+        if (look_on_rows_lds(h)) {
+            if (h->rings == Rings::Xlmp) return RunPath::SweepXlmp;
+            if (many) return RunPath::SweepXl;
+        }
+        return RunPath::General;
+    }
     // the register-tree kernels of one population, which complete the previous row while loading the particle (fused k_resample)
     if (h->P == 1 && h->n <= 8 && !h->wide && !dbg(h, PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE)) {
         if (h->rings != Rings::Reg || dbg(h, PF_DEBUG_TWO_LAUNCH)) return RunPath::TwoLaunch;
@@ -146,7 +164,8 @@ static int launch_extend(pf_handle* h, long long s, int fuse = 0) {
     }
     if (check_launch("k_extend")) return -1;
     if (h->A.apf > 0) {
-        hipLaunchKernelGGL(k_lookahead, dim3(h->nblocks), dim3(PF_BS), h->smem_la, h->stream, h->A, s);
+        if (h->la_xl) hipLaunchKernelGGL(k_lookahead_xl, dim3(h->nblocks), dim3(PF_BS), h->smem_la, h->stream, h->A, s);
+        else hipLaunchKernelGGL(k_lookahead, dim3(h->nblocks), dim3(PF_BS), h->smem_la, h->stream, h->A, s);
         return check_launch("k_lookahead");
     }
     return 0;
@@ -738,7 +757,9 @@ static int run_sweep_x(pf_handle* const* hs, int nh, long long s_begin, long lon
             Timed tm(h, 0, timing_on(h, s_begin + t));
             if (xl) {
                 const dim3 gx((unsigned)F.nb, (unsigned)nh), bx(PF_BS);
-                if (is_biased(h)) hipExtLaunchKernelGGL((k_sweep_xl<true>), gx, bx, h->smem_sweep_x, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t);
+                // a look-ahead on this path (run_path: look_on_rows_lds, never with focused sampling): the LOOK instance, the same launch otherwise
+                if (h->A.apf > 0) hipExtLaunchKernelGGL((k_sweep_xl<false, true>), gx, bx, h->smem_sweep_x, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t);
+                else if (is_biased(h)) hipExtLaunchKernelGGL((k_sweep_xl<true>), gx, bx, h->smem_sweep_x, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t);
                 else hipExtLaunchKernelGGL((k_sweep_xl<false>), gx, bx, h->smem_sweep_x, h->stream, nullptr, F.x_done(t), 0, h->d_sweep, t);
             } else if (xlmp) {
                 pf_mp_launch_sweep_xl(h->A, h->d_sweep, nh, t, h->smem_sweep_x, h->stream, F.x_done(t));
@@ -766,13 +787,15 @@ static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles
         pf_handle* g = handles[k];
         if (!g) return "pf_run_many: null handle";
         // Out of scope: structured models above 8 haplotypes without PF_FLAG_MP_LDS_ROWS, -arg above 8 haplotypes, a look-ahead without PF_LA_ROW_PIPELINE (one
-        // population) or PF_LA_ROW_PIPELINE_MP (structured) or on a handle that does not qualify for it (look_on_rows, look_on_rows_mp),
+        // population) or PF_LA_ROW_PIPELINE_MP (structured) or PF_LA_ROW_PIPELINE_LDS (9 to 16 haplotypes) or on a handle that does not qualify for it
+        // (look_on_rows, look_on_rows_mp, look_on_rows_lds),
         // the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the general kernels
         if (!runs_many(run_path(g, true)))
             return "pf_run_many: the chunks must run on the row pipeline (one population of at most 16 haplotypes, or a structured model of two to "
                    "four populations with the tree in registers, at most 8 haplotypes, or of 9 to 16 haplotypes created with PF_FLAG_MP_LDS_ROWS -- every chunk of the group then; a look-ahead only with PF_LA_ROW_PIPELINE on one "
                    "population of at most 8 haplotypes or with PF_LA_ROW_PIPELINE_MP on such a structured model, without focused sampling; "
-                   "no -arg above 8 haplotypes, no debug switch that selects another path)";
+                   "no -arg above 8 haplotypes, no debug switch that selects another path)"
+                   "; at 9 to 16 haplotypes a look-ahead only with PF_LA_ROW_PIPELINE_LDS, one population or a structured model created with PF_FLAG_MP_LDS_ROWS";
         if (!sweep_compatible(h, g)) return "pf_run_many: the chunks must share device, particle count, haplotypes (and with them the form of the tree: registers up to 8, "
                                               "LDS columns of one width from 9 to 16), populations, epochs and options (mig_cap and piece_cap of a structured model among them, and the look-ahead: all without, or one level and one table size)";
         for (int j = 0; j < k; ++j) if (handles[j] == g) return "pf_run_many: a handle appears twice";

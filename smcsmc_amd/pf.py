@@ -77,15 +77,17 @@ class _Lookahead(C.Structure):
 
 LA_ROW_PIPELINE = 1      # pf_lookahead.flags (PF_LA_ROW_PIPELINE)
 LA_ROW_PIPELINE_MP = 2   # (PF_LA_ROW_PIPELINE_MP: the same for structured models)
+LA_ROW_PIPELINE_LDS = 4  # (PF_LA_ROW_PIPELINE_LDS: the same on the LDS tree, 9 to 16 haplotypes)
 
 
 class PackedLookahead:
     """Owns the buffers behind a pf_lookahead / smco_lookahead struct.  `la` = segments.pack_lookahead(...),
     `tbl` = (lengths[nsam][Q], mean_total_branch_length) from terminal_branch_quantiles.  `pipeline` sets flags bit 0
     (PF_LA_ROW_PIPELINE: the look-ahead in the extend role of the row pipeline), `structured` bit 1 (PF_LA_ROW_PIPELINE_MP: the same
-    on the row pipeline of structured models); the oracle has no such thing and gets 0."""
+    on the row pipeline of structured models), `lds` bit 2 (PF_LA_ROW_PIPELINE_LDS: the same on the row pipelines of 9 to 16 haplotypes);
+    the oracle has no such thing and gets 0."""
 
-    def __init__(self, la, level, tbl, quantiles, struct_cls=_Lookahead, pipeline=False, structured=False):
+    def __init__(self, la, level, tbl, quantiles, struct_cls=_Lookahead, pipeline=False, structured=False, lds=False):
         f = lambda a, t: np.ascontiguousarray(a, dtype=t)      # noqa: E731
         self.a = [f(la["first_singleton_distance"], np.float64), f(la["relative_mutation_rate"], np.float64),
                   f(la["is_singleton_unphased"], np.int8), f(la["n_doubletons"], np.int32), f(la["doubleton_idx"], np.int8),
@@ -95,7 +97,8 @@ class PackedLookahead:
         ptr = lambda a: a.ctypes.data_as(C.POINTER({np.dtype(np.float64): C.c_double, np.dtype(np.int8): C.c_int8,      # noqa: E731
                                                     np.dtype(np.int32): C.c_int32}[a.dtype]))
         self.struct = struct_cls(int(level), int(la["max_doubletons"]), len(quantiles),
-                                 (LA_ROW_PIPELINE if pipeline else 0) | (LA_ROW_PIPELINE_MP if structured else 0),
+                                 (LA_ROW_PIPELINE if pipeline else 0) | (LA_ROW_PIPELINE_MP if structured else 0) |
+                                 (LA_ROW_PIPELINE_LDS if lds else 0),
                                  len(la["n_doubletons"]),
                                  *[ptr(a) for a in self.a], float(tbl[1]))
 
@@ -401,7 +404,7 @@ class ParticleFilter:
         self._chk(self.L.pf_load_segments(self.h, C.byref(sg)))
         self.n_segs = n
 
-    def load_lookahead(self, la, level, tbl, quantiles=None, pipeline=False, structured=False):
+    def load_lookahead(self, la, level, tbl, quantiles=None, pipeline=False, structured=False, lds=False):
         """Switches the auxiliary particle filter on (-apf level): `la` from segments.pack_lookahead, `tbl` from
         terminal_branch_quantiles.  Call after load_segments.  pipeline=True (PF_LA_ROW_PIPELINE) asks for the look-ahead in
         the extend role of the row pipeline: a filter that qualifies (one population, at most 8 haplotypes, no focused sampling,
@@ -410,10 +413,14 @@ class ParticleFilter:
         level 0 or without the flag returns the filter to the general kernels.  structured=True (PF_LA_ROW_PIPELINE_MP) asks
         for the same on a structured model: two to four populations, at most 8 haplotypes, no focused sampling, no guide, no
         record_trees, no debug path -- then run() and run_many() take its rows on "SweepXmp", the path such a model has without
-        a look-ahead.  Each flag means nothing on the other kind of model."""
+        a look-ahead.  Each flag means nothing on the other kind of model.  lds=True (PF_LA_ROW_PIPELINE_LDS) asks for the same at 9 to
+        16 haplotypes, where the tree lives in LDS: one population (run_many() then takes the filter on "SweepXl"; run() keeps the general
+        kernels, as for every such filter) and structured models made with mp_rows=True (run() and run_many() on "SweepXlmp"); no focused
+        sampling, no guide, no record_trees, no debug path.  It means nothing at 8 haplotypes and fewer, and the other two flags nothing
+        above 8."""
         from . import segments as segmod
         self._la = PackedLookahead(la, level, tbl, segmod.TBL_QUANTILES if quantiles is None else quantiles, pipeline=pipeline,
-                                   structured=structured)
+                                   structured=structured, lds=lds)
         self._chk(self.L.pf_load_lookahead(self.h, C.byref(self._la.struct)))
 
     def run(self, s_begin=0, s_end=None):
@@ -427,7 +434,7 @@ class ParticleFilter:
         have the same number of haplotypes), or chunks of a structured model (two to four populations, at most 8 haplotypes: the
         same two launches; 9 to 16 haplotypes when every filter of the group was made with mp_rows=True, all with one number of haplotypes,
         populations and mig_cap); no tree recording with structure.  A look-ahead only when every filter of the group loaded it with
-        pipeline=True (one population) or structured=True (structured models) and qualifies for it (load_lookahead), all with the same level and table sizes -- or none has one.  With record_trees, one population of at most 8 haplotypes
+        pipeline=True (one population) or structured=True (structured models) or, at 9 to 16 haplotypes, lds=True and qualifies for it (load_lookahead), all with the same level and table sizes -- or none has one.  With record_trees, one population of at most 8 haplotypes
         is taken (all filters of the group recording; log_cap / gen_cap may differ between them), and sample_tree_events() after
         run_many + finish returns what it returns after run().  A chunk with fewer rows stops at its end and sits later
         calls out.  Every chunk gets the bits of its own run().  Raises PfError for a group can_run_many() refuses."""
@@ -439,7 +446,7 @@ class ParticleFilter:
     @staticmethod
     def can_run_many(filters):
         """True when run_many would take these filters (pf_can_run_many); otherwise run them one after the other with run():
-        more than 16 haplotypes, a structured model above 8 made without mp_rows=True, a look-ahead loaded without pipeline=True / structured=True (or on a filter that does
+        more than 16 haplotypes, a structured model above 8 made without mp_rows=True, a look-ahead loaded without pipeline=True / structured=True / lds=True (or on a filter that does
         not qualify for it, or of another level than its neighbour's, or beside a filter without one), tree recording above 8 haplotypes or with structure,
         a debug path, or chunks that differ in shape (12 haplotypes do not run with 16, nor 9 to 16 with 8 or fewer, nor a
         tree-recording filter with a plain one)."""
