@@ -38,9 +38,9 @@ extern "C" {
 
 typedef struct pf_model {
     int32_t n_epochs;            /* E  (Model::change_times_.size()) */
-    int32_t n_pops;              /* P  (1..4; scrm -I) */
+    int32_t n_pops;              /* P  (scrm -I): 1..4, or 1..8 with PF_MODEL_WIDE_POPS in flags (more than four: n_epochs <= 32, general path with the tree in LDS, no pf_run_many) */
     int32_t nsam;                /* haplotypes n: 2..64 with one population (beyond 16 without -arg and -apf), 2..16 with several (-arg included) */
-    int32_t flags;               /* bit0 -ancestral_aware, bit1 -dephase (pfparam.cpp:143-146) */
+    int32_t flags;               /* bit0 -ancestral_aware, bit1 -dephase (pfparam.cpp:143-146), bit2 PF_MODEL_WIDE_POPS below */
     double loci_length;          /* Model::loci_length() */
     double mutation_rate;        /* per bp per generation */
     double recombination_rate;   /* per bp per generation */
@@ -112,12 +112,19 @@ typedef struct pf_params {
                                   * (pf_run_many), where the launch of a step is several thousand workgroups otherwise. */
     int32_t reserved4;
 } pf_params;
+/* pf_model.flags bit 2: the caller knows the models of five to eight populations and their limits (at most 32 epochs and 16 haplotypes; the
+ * general kernels with the tree in LDS, PF_PATH_GENERAL, at every number of haplotypes; no pf_run_many; no pf_simulate_sites).  pf_create,
+ * pf_test_plan, pf_median_survival* and pf_terminal_branch_quantiles then take n_pops up to 8.  Without the bit nothing changes for any
+ * caller: more than four populations are refused as they always were ("n_pops must be in 1..4").  The bit means nothing on a model of at
+ * most four populations.  bin/smcsmc and the Python binding set it for every model of more than four populations. */
+#define PF_MODEL_WIDE_POPS 4
 /* pf_params.flags bit 3: a structured model (two to four populations) of 9 to 16 haplotypes gets the rings of the row pipeline, and pf_run and
  * pf_run_many take its rows there (PF_PATH_SWEEP_XLMP: k_sweep_xlmp with tree and migration list in LDS + k_sweep_blc, two launches a row where
  * the general kernels need five).  Off by default.  The handle qualifies with at most 131 072 particles, without -arg, without
  * PF_DEBUG_FORCE_LDS / NO_FUSE / K_PIPE / TWO_LAUNCH, with gen_cap >= 20 and where the decision tables of the prologue fit in the LDS of the extend
  * launch.  On every other handle the bit means nothing: path and plan are those without it, never an error -- pf_get_run_path tells.  A
- * look-ahead loaded on such a handle takes it to the general kernels. */
+ * look-ahead loaded on such a handle takes it to the general kernels.  Five to eight populations are among "every other handle": they run on
+ * the general kernels with the tree in LDS at every number of haplotypes (PF_PATH_GENERAL), and pf_run_many refuses them by name. */
 #define PF_FLAG_MP_LDS_ROWS 8
 #define PF_DEBUG_FORCE_LDS 1     /* run the LDS-tree kernels whatever nsam is */
 #define PF_DEBUG_NO_FUSE   2     /* complete every row with the stand-alone k_resample (two-stream pipeline) */
@@ -273,6 +280,7 @@ int pf_run(pf_handle* h, int64_t s_begin, int64_t s_end);
  * structured models created with PF_FLAG_MP_LDS_ROWS (k_sweep_xlmp<false, true>, pf_run and pf_run_many), no focused sampling.  The
  * handles of a group then agree in it: all without a look-ahead, or all with the same flags, level, max_doubletons and n_quantiles.
  * Structured models of 9 to 16 haplotypes are taken with PF_FLAG_MP_LDS_ROWS (the chunks then agree on haplotypes, populations, mig_cap and the flag).
+ * Structured models of five to eight populations are not taken, whatever their flags (pf_can_run_many answers 0): run their chunks one after the other with pf_run.
  * Not taken: structured models above 8 haplotypes without that flag, -arg with structure or above 8 haplotypes, a look-ahead without its bit or on a handle
  * that does not qualify, more than 16 haplotypes (the wide kernels).
  * The reference starts one process per chunk, all at once (smcsmc/model.py:1094-1098);
@@ -384,7 +392,8 @@ int pf_median_survival_opts(const pf_model* model, uint64_t seed, int32_t min_ev
 
 /* Synthetic data next to the path (the reference shells out to scrm and converts, populationmodels.py:440-577): `nchunks`
  * independent chunks of the model's length under the same SMC' process the filter simulates (one population, or a
- * structured model with migration and joins, up to 96 migration events per local tree); per chunk
+ * structured model of at most four populations with migration and joins, up to 96 migration events per local tree -- the filter takes
+ * up to eight, the simulator refuses more than four by name); per chunk
  * ascending continuous site positions pos[c*max_sites + k] and carrier masks (bit i = sample i carries the mutation).
  * n_sites[c] < 0 means more than max_sites sites were drawn (the first max_sites are returned). */
 int pf_simulate_sites(const pf_model* model, uint64_t seed, int32_t nchunks, int64_t max_sites, double* pos, uint32_t* masks,

@@ -170,7 +170,7 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
     HostModel& M = P.model;
     const int E = (int)M.change_times.size();
     const int NP = M.npop;
-    if (NP > 4) throw Unsupported("models with more than four populations");
+    if (NP > 8) throw Unsupported("models with more than eight populations");
 
     std::vector<double> pop_sizes((size_t)E * NP), mig_rates((size_t)E * NP * NP), single_mig((size_t)E * NP * NP);
     for (int e = 0; e < E; ++e)
@@ -194,7 +194,7 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
         }
         pm.vb_coal_counts = vb_cc.data(); pm.vb_mig_counts = vb_mc.data();
     }
-    pm.flags = (P.ancestral_aware ? 1 : 0) | (P.dephase ? 2 : 0);
+    pm.flags = (P.ancestral_aware ? 1 : 0) | (P.dephase ? 2 : 0) | (NP > 4 ? PF_MODEL_WIDE_POPS : 0);
     pm.loci_length = M.loci_length; pm.mutation_rate = M.mutation_rate; pm.recombination_rate = M.recombination_rate;
     pm.change_times = M.change_times.data(); pm.pop_sizes = pop_sizes.data();
     pm.record_flags = P.record_mask.data();

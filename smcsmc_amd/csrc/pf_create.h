@@ -22,13 +22,16 @@ static int refuse_params(const pf_model* m, const pf_params* p) {
 }
 static int refuse_model(const pf_model* m, const pf_params* p) {
     auto fail = [&](const std::string& msg) { g_err = msg; return -1; };
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX) return fail("pf_create: n_pops must be in 1..4");
+    if (m->n_pops < 1 || m->n_pops > PF_POPS_TAKEN(m))
+        return fail((m->flags & PF_MODEL_WIDE_POPS) ? "pf_create: n_pops must be in 1..8" : "pf_create: n_pops must be in 1..4");      // (five to eight: PF_MODEL_WIDE_POPS)
     if (m->nsam < 2 || m->nsam > PF_NMAX_WIDE) return fail("pf_create: nsam must be in 2..64");
     const bool wide = m->n_pops == 1 && (m->nsam > PF_NMAX || (p->debug & PF_DEBUG_FORCE_WIDE));
     if (m->nsam > PF_NMAX && m->n_pops > 1) return fail("pf_create: more than 16 haplotypes need one population (structured models take nsam <= 16)");
     if ((p->debug & PF_DEBUG_FORCE_WIDE) && m->n_pops > 1) return fail("pf_create: PF_DEBUG_FORCE_WIDE applies to one population only");
     if (wide && (p->flags & 2)) return fail("pf_create: tree recording (-arg) needs nsam <= 16 (its descendant masks are 32 bits wide)");
     if (m->n_epochs < 1 || m->n_epochs > PF_EMAX) return fail("pf_create: n_epochs must be in 1..64");
+    if (m->n_pops > PF_PMAX && m->n_epochs > PF_EMAX_PWIDE)
+        return fail("pf_create: a model of more than four populations takes at most 32 epochs (its migration events keep population and epoch in one byte, three bits and five)");
     if (p->np < 1 || p->np > 262144) return fail("pf_create: np must be in 1..262144");
     if (m->n_bias_heights < 0 || m->n_bias_heights > PF_BIAS_MAX) return fail("pf_create: at most 8 bias heights are supported");
     if (m->n_bias_heights > 0 && (!m->bias_heights || !m->bias_strengths || !m->application_delays))
@@ -113,6 +116,8 @@ static CreatePlan create_plan(const pf_model* m, const pf_params* p, long long l
     const bool plain = !(p->flags & 2) && !(p->debug & (PF_DEBUG_FORCE_LDS | PF_DEBUG_NO_FUSE | PF_DEBUG_K_PIPE));     // no -arg, no switch to another path
     if (P == 1 && n <= 8 && fits) pl.rings = Rings::Reg;      // (with a switch or a look-ahead that takes the rows elsewhere the rings are there, unused)
     // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_x)
+    // (more than PF_PMAX populations: no rings -- the general path on the LDS-tree kernels at every number of haplotypes, the wide walk of pf_mp.h)
+    else if (P > PF_PMAX) pl.rings = Rings::None;
     else if (P > 1 && n <= 8 && fits && plain) pl.rings = Rings::Xmp;
     // one population on the LDS tree, several chunks in lockstep (pf_run_many): the same rings, the extend role k_sweep_xl.  Not with a
     // generation ring too short for an extend role that runs ahead of the counts (what pf_create refuses for structured models; here the
@@ -132,7 +137,7 @@ static CreatePlan create_plan(const pf_model* m, const pf_params* p, long long l
     // leave after 2 us of a slot each; with 32 instead of 192 eight chunks gain 3 %, one chunk is the same either way: 28.7 us per row)
     pl.ledger_wgs = p->count_wgs > 0 ? 32 : std::max(16, std::min(PF_LEDGER_BLOCKS, 192));
     {
-        const int PT = P <= 2 ? P : PF_PMAX;     // k_count is instantiated for 1, 2 and PF_PMAX populations
+        const int PT = pf_count_pops(P);         // k_count is instantiated for 1, 2, PF_PMAX and PF_PWIDE populations
         pl.ncol = PT == 1 ? 6 : 3 * PT + 3 + PT * PT + 2 * PT;
     }
     pl.dcap = p->delay_cap > 0 ? p->delay_cap : PF_DCAP_DEFAULT;
@@ -392,7 +397,8 @@ static int create_prepare(pf_handle* h, const pf_params* p) {
     }
     // structured models: the LDS-tree kernels serve the prior tree and calibration for every n, the row kernel is the
     // register-tree one for n <= 8
-    const bool lds_rows = P > 1 && (n > 8 || (p->debug & PF_DEBUG_FORCE_LDS));
+    // (and the only one beyond PF_PMAX populations, where they are the row kernel at every n)
+    const bool lds_rows = P > 1 && (n > 8 || P > PF_PMAX || (p->debug & PF_DEBUG_FORCE_LDS));
     if (h->smem > 160 * 1024 || (P > 1 && pf_mp_prepare(h->smem, A.mcap)) ||
         (P > 1 && !lds_rows && pf_mp_reg_smem_bytes(E, P, A.mcap) > 160 * 1024))
         return fail(P > 1 ? "pf_create: the local-tree state (tree, epoch tables and pf_params.mig_cap migration events per lane) does not fit the LDS of one workgroup"

@@ -65,8 +65,8 @@ int pf_get_counts(pf_handle* h, double* out, int32_t n) {
         tail = out + 6 * E;
     } else {
         // device layout: totals[column][epoch]; columns as AccT<P>.  A kernel compiled for PF_PMAX populations
-        // (P == 3) still uses the column numbering of its template parameter.
-        const int PT = P == 2 ? 2 : PF_PMAX;
+        // (P == 3) still uses the column numbering of its template parameter, and so does that of PF_PWIDE (P == 5 .. 7).
+        const int PT = pf_count_pops(P);
         const int ncol = h->A.ncol;
         std::vector<double> tot;
         if (download(tot, h->A.totals, (size_t)ncol * E)) return -1;
@@ -130,7 +130,7 @@ int pf_get_migrations(pf_handle* h, int32_t* n_events, double* times, int8_t* br
             bool ok = k < nm[p] && k < mcap;
             if (times) times[p * cap + k] = ok ? mt[(size_t)k * Np + p] : 0.0;
             if (branch) branch[p * cap + k] = ok ? mb[(size_t)k * Np + p] : 0;
-            if (newpop) newpop[p * cap + k] = ok ? (mq[(size_t)k * Np + p] & 3) : 0;      // the upper bits hold the event's epoch
+            if (newpop) newpop[p * cap + k] = ok ? (mq[(size_t)k * Np + p] & (h->P > PF_PMAX ? 7 : 3)) : 0;      // the upper bits hold the event's epoch
         }
         if (node_pops) for (int r = 0; r < n - 1; ++r) node_pops[p * (n - 1) + r] = pn[(size_t)r * Np + p];
     }

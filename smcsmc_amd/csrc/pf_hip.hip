@@ -1298,13 +1298,27 @@ __device__ __forceinline__ void decide_body(const KA& A, long long s, int mode, 
 // composite ancestor maps) of every generation whose positions intersect the epoch's window.
 // per-thread statistics of one epoch: [coal count, opp, weight][P], recomb count, opp, weight and -- for
 // structured models -- [migration count][P][P], [migration opp, weight][P]  (count.hpp:95-110)
+// NC columns in this order are what a workgroup adds to its accumulator (KArgs::partial) and what pf_get_counts reads.
+// More than PF_PMAX populations (MIG_LDS, the instance of PF_PWIDE): a thread keeps the per-population statistics only -- NR = 5P + 3 = 43
+// doubles at P = 8, next to the 39 of P = 4 -- and the P x P migration counts, which would make it 107 doubles (214 VGPRs before anything
+// else), are collected per workgroup in LDS (count_mig) and meet the others at the workgroup's reduction.  CC .. RW, MO, MW index v[];
+// MC is the first column of the migration counts in both arrangements, and the reduction of count_body puts v[k] behind them for k >= MC.
 template <int P>
 struct AccT {
+    static constexpr bool MIG_LDS = P > PF_PMAX;
     static constexpr int NC = P == 1 ? 6 : 3 * P + 3 + P * P + 2 * P;
+    static constexpr int NR = MIG_LDS ? NC - P * P : NC;
     static constexpr int CC = 0, CO = P, CW = 2 * P, RC = 3 * P, RO = 3 * P + 1, RW = 3 * P + 2;
-    static constexpr int MC = 3 * P + 3, MO = 3 * P + 3 + P * P, MW = 3 * P + 3 + P * P + P;
-    double v[NC];
+    static constexpr int MC = 3 * P + 3, MO = 3 * P + 3 + (MIG_LDS ? 0 : P * P), MW = MO + P;
+    double v[NR];
 };
+// the migration counts of a count workgroup of the PF_PWIDE instance: [from][to], zeroed at its entry, added to with ds_add_f64
+// (the address space is in the pointer's type, as in lmap_add: a flat atomic would find out per lane)
+typedef __attribute__((address_space(3))) double pf_lds_double;
+__device__ __forceinline__ double* count_mig() {
+    __shared__ double mig[PF_PWIDE * PF_PWIDE];
+    return mig;
+}
 
 __device__ __forceinline__ double ovl(double a0, double a1, double b0, double b1) {
     double lo = a0 > b0 ? a0 : b0;
@@ -1486,9 +1500,13 @@ __device__ __forceinline__ void record_contrib_one(AccT<P>& acc, const KA& A, co
                             acc.v[AC::MW + pp] += w * w * mo;
                             if (ev && (kind & 1)) acc.v[AC::CC + pp] += w;
                             if (ev && (kind & 2)) {
+                                if constexpr (AC::MIG_LDS) {
+                                    if (to < P) __hip_atomic_fetch_add((pf_lds_double*)count_mig() + pp * P + to, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                } else {
 #pragma unroll
                                 for (int qq = 0; qq < P; ++qq)
                                     if (qq == to) acc.v[AC::MC + pp * P + qq] += w;
+                                }
                             }
                         }
                 }
@@ -1663,7 +1681,8 @@ __device__ __forceinline__ void count_body(const KA& A, const CountSrc& Q, int e
     const long long nthreads = (long long)nbxg * PF_BS;
     AC acc;
 #pragma unroll
-    for (int k = 0; k < AC::NC; ++k) acc.v[k] = 0.0;
+    for (int k = 0; k < AC::NR; ++k) acc.v[k] = 0.0;
+    if constexpr (AC::MIG_LDS) { if (threadIdx.x < P * P) count_mig()[threadIdx.x] = 0.0; }       // (the barrier that opens the first tile is between this and the first addition)
     // Work = all (generation, run) pairs of the window plus the live particles, flattened into one task index
     // space with an LDS prefix sum of the run counts: every thread takes tasks gtid, gtid+nthreads, ... so deep
     // windows are spread over the grid column instead of being walked generation by generation.
@@ -1833,13 +1852,24 @@ __device__ __forceinline__ void count_body(const KA& A, const CountSrc& Q, int e
         }
     }
 #pragma unroll
-    for (int k = 0; k < AC::NC; ++k) acc.v[k] = wave_tree_sum(acc.v[k]);
+    for (int k = 0; k < AC::NR; ++k) acc.v[k] = wave_tree_sum(acc.v[k]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x < AC::NC) {
         const int k = threadIdx.x;
-        double t = red[0].v[k];
+        double t;
+        if constexpr (AC::MIG_LDS) {
+            // column k: a migration count from the workgroup's LDS table, or the register statistic that lands there (AccT::column)
+            if (k >= AC::MC && k < AC::MC + P * P) t = count_mig()[k - AC::MC];
+            else {
+                const int kr = k < AC::MC ? k : k - P * P;
+                t = red[0].v[kr];
+                for (int w = 1; w < PF_BS / 64; ++w) t += red[w].v[kr];
+            }
+        } else {
+        t = red[0].v[k];
         for (int w = 1; w < PF_BS / 64; ++w) t += red[w].v[k];
+        }
         // this workgroup's own accumulator (folded by k_count_fin)
         if constexpr (ACC_AT_ENTRY) A.partial[((size_t)e * A.nbx + bx) * AC::NC + k] = acc_before + t;
         else A.partial[((size_t)e * A.nbx + bx) * AC::NC + k] += t;

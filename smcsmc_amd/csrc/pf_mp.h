@@ -10,6 +10,8 @@
 // stores the population it happened in (Pn), and the migration events of the local tree live in one list
 // sorted by time: event m sits on the branch above node id Mb[m] and moves that lineage to population Mq[m] & 3
 // at time Mt[m]; the upper six bits of Mq[m] hold the epoch of the event (the walk needs it at every event it passes).  Likelihood, branch-length and recombination-opportunity code never see the events.
+// Models of five to eight populations (the wide walk, PW = PF_PWIDE below) split the byte 3 / 5: population Mq[m] & 7, epoch in the
+// upper five bits, hence at most 32 epochs there (pf_create refuses more).
 // While a genealogy update is in flight, the events picked up by the floating lineage, by the root's own
 // lineage and the events of the cut branch's stub carry the temporary branch tags below.
 #pragma once
@@ -107,12 +109,17 @@ __device__ __forceinline__ void plog_flush_r(PLog& pl, int kind, int to) {
 __device__ __forceinline__ int mp_pop_base(const Lane& ln, const MLane& ml, int id) {
     return id < ln.n ? ml.SP[id] : (int)LPn(ml, id - ln.n);
 }
+// PW, the population width of the walk and of the event byte: PF_PMAX (two bits of population, six of epoch) or PF_PWIDE (three and five)
+template <int PW>
+__device__ __forceinline__ int mp_ev_pop(int byte) { return byte & (PW > PF_PMAX ? 7 : 3); }
+template <int PW = PF_PMAX>
 __device__ __forceinline__ int mp_pop_at(const Lane& ln, const MLane& ml, int id, double time) {
     int pop = mp_pop_base(ln, ml, id);
     for (int m = 0; m < ml.nm; ++m)
-        if (LMb(ml, m) == id && LMt(ml, m) <= time) pop = LMq(ml, m) & 3;
+        if (LMb(ml, m) == id && LMt(ml, m) <= time) pop = mp_ev_pop<PW>(LMq(ml, m));
     return pop;
 }
+template <int PW = PF_PMAX>
 __device__ __forceinline__ int mp_lineages_in_pop(const Lane& ln, const MLane& ml, int ni, double time, int pop, int want,
                                                   int* pr, int* ps) {
     int R = 0;
@@ -121,15 +128,16 @@ __device__ __forceinline__ int mp_lineages_in_pop(const Lane& ln, const MLane& m
     for (int r = R; r < ni; ++r)
         for (int s = 0; s < 2; ++s) {
             int id = LC(ln, r, s);
-            if ((id < ln.n || id - ln.n < R) && mp_pop_at(ln, ml, id, time) == pop) {
+            if ((id < ln.n || id - ln.n < R) && mp_pop_at<PW>(ln, ml, id, time) == pop) {
                 if (cnt == want) { *pr = r; *ps = s; }
                 ++cnt;
             }
         }
     return cnt;
 }
-// `newpop` arrives packed: population | epoch of the event << 2 (mp_ev_byte)
-__device__ __forceinline__ int mp_ev_byte(int pop, int epoch) { return pop | (epoch << 2); }
+// `newpop` arrives packed: population | epoch of the event << 2 (mp_ev_byte; << 3 in the wide walk)
+template <int PW = PF_PMAX>
+__device__ __forceinline__ int mp_ev_byte(int pop, int epoch) { return pop | (epoch << (PW > PF_PMAX ? 3 : 2)); }
 template <class ML>
 __device__ __forceinline__ void mp_ev_insert(ML& ml, double time, int branch, int newpop) {
     if (ml.nm >= ml.mcap) { ml.err = 1; return; }
@@ -226,7 +234,8 @@ __device__ __forceinline__ unsigned piece_span(int e0, int e1) { return (unsigne
 // The floating lineage starts at height h in population pf0 and moves up through the stored tree (ni internal
 // nodes, root_id its top node or the single leaf); above the root the root's own lineage is the second active
 // lineage.  Migration events picked up on the way enter the list under PF_TAG_PATH / PF_TAG_RPATH.
-template <bool LOG>
+// PW = PF_PWIDE: eight counters and the 3 / 5 split of the event byte; the instances of PF_PMAX are the code they were before there was a choice.
+template <bool LOG, int PW = PF_PMAX>
 __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int root_id, double h, int pf0, PLog& pl,
                                             int limit, MWalk& W) {
     MP_TICK(tw0);
@@ -243,17 +252,23 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
     // Lineages of the stored tree per population, kept up to date while the walk moves up (the restatement
     // recounts them in every interval; the numbers are the same).  Bp[id] = current population of the lineage
     // above node id; a lineage is counted from its lower node until its parent node.
+    // (scalars, not an array: a dynamically indexed array would be placed in scratch memory -- the wide walk has eight of them)
     int cnt0 = 0, cnt1 = 0, cnt2 = 0, cnt3 = 0;
+    [[maybe_unused]] int cnt4 = 0, cnt5 = 0, cnt6 = 0, cnt7 = 0;
     auto bump = [&](int q, int d) __attribute__((always_inline)) {
         cnt0 += q == 0 ? d : 0; cnt1 += q == 1 ? d : 0; cnt2 += q == 2 ? d : 0; cnt3 += q == 3 ? d : 0;
+        if constexpr (PW > PF_PMAX) { cnt4 += q == 4 ? d : 0; cnt5 += q == 5 ? d : 0; cnt6 += q == 6 ? d : 0; cnt7 += q == 7 ? d : 0; }
     };
-    auto count_of = [&](int q) __attribute__((always_inline)) { return q == 0 ? cnt0 : q == 1 ? cnt1 : q == 2 ? cnt2 : cnt3; };
+    auto count_of = [&](int q) __attribute__((always_inline)) {
+        if constexpr (PW > PF_PMAX) return q == 0 ? cnt0 : q == 1 ? cnt1 : q == 2 ? cnt2 : q == 3 ? cnt3 : q == 4 ? cnt4 : q == 5 ? cnt5 : q == 6 ? cnt6 : cnt7;
+        else return q == 0 ? cnt0 : q == 1 ? cnt1 : q == 2 ? cnt2 : cnt3;
+    };
     for (int id = 0; id < n; ++id) LBp(ml, id) = (int8_t)ml.SP[id];
     for (int r = 0; r < ni; ++r) LBp(ml, n + r) = LPn(ml, r);
     while (i < ni && LS(ln, i) <= tt) ++i;
     while (j < ml.nm && LMt(ml, j) <= tt) {
         int b = LMb(ml, j);
-        if (b < PF_TAG_MIN) LBp(ml, b) = (int8_t)(LMq(ml, j) & 3);
+        if (b < PF_TAG_MIN) LBp(ml, b) = (int8_t)mp_ev_pop<PW>(LMq(ml, j));
         ++j;
     }
     for (int r = i; r < ni; ++r)
@@ -270,7 +285,7 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
         else nS = PF_INF;
     };
     auto fetch_event = [&]() __attribute__((always_inline)) {
-        if (j < ml.nm) { eT = LMt(ml, j); eB = LMb(ml, j); eQ = LMq(ml, j) & 3; }
+        if (j < ml.nm) { eT = LMt(ml, j); eB = LMb(ml, j); eQ = mp_ev_pop<PW>(LMq(ml, j)); }
         else eT = PF_INF;
     };
     fetch_node();
@@ -383,10 +398,10 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
             advance(tt);
             if (at_join) {
                 int q = ml.JM[e * P + pf];
-                if (q != pf) { PF_MP_BUF_PUSH(tt, PF_TAG_PATH, mp_ev_byte(q, e)); pf = q; }
+                if (q != pf) { PF_MP_BUF_PUSH(tt, PF_TAG_PATH, mp_ev_byte<PW>(q, e)); pf = q; }
                 if (tt >= Hr) {
                     int qr = ml.JM[e * P + pr];
-                    if (qr != pr) { PF_MP_BUF_PUSH(tt, PF_TAG_RPATH, mp_ev_byte(qr, e)); pr = qr; }
+                    if (qr != pr) { PF_MP_BUF_PUSH(tt, PF_TAG_RPATH, mp_ev_byte<PW>(qr, e)); pr = qr; }
                 }
             }
             if (ml.err) break;
@@ -447,7 +462,7 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
                 W.e1 = (ee + 1 < ln.E && !(t1 < ln.T[ee + 1])) ? ee + 1 : ee;       // an event placed at the end of its epoch counts in the next
                 done = true;
             } else {
-                PF_MP_BUF_PUSH(t1, kind == 2 ? PF_TAG_PATH : PF_TAG_RPATH, mp_ev_byte(to, ee));
+                PF_MP_BUF_PUSH(t1, kind == 2 ? PF_TAG_PATH : PF_TAG_RPATH, mp_ev_byte<PW>(to, ee));
                 if (kind == 2) pf = to; else pr = to;
                 tt = t1;
                 e = ee;
@@ -474,7 +489,7 @@ __device__ __forceinline__ void mp_retag(MLane& ml, int from, int to) {
 // Forest::buildInitialTree(true) for a structured model.  `emit(i, pstart, npieces, tc, below)` logs the record of leaf i;
 // `below` = the samples under the node leaf i creates (computed when `tmp`, n-1 doubles of per-lane LDS scratch, is given;
 // otherwise the epoch span of the walk's pieces, piece_span).
-template <bool LOG, class Emit>
+template <bool LOG, int PW = PF_PMAX, class Emit>
 __device__ __forceinline__ void mp_build_initial_tree(Lane& ln, MLane& ml, PLog& pl, Emit emit, double* tmp = nullptr) {
     const int n = ln.n;
     ml.nm = 0;
@@ -483,7 +498,7 @@ __device__ __forceinline__ void mp_build_initial_tree(Lane& ln, MLane& ml, PLog&
         int ni = i - 1;
         MWalk W;
         unsigned p0 = LOG ? pl.idx : 0u;
-        mp_coalesce<LOG>(ln, ml, ni, root, 0.0, ml.SP[i], pl, ln.E - 1, W);
+        mp_coalesce<LOG, PW>(ln, ml, ni, root, 0.0, ml.SP[i], pl, ln.E - 1, W);
         if (ml.err) return;
         const unsigned np_ = LOG ? pl.idx - p0 : 0u;
         double tc = W.tc;
@@ -516,18 +531,18 @@ __device__ __forceinline__ void mp_build_initial_tree(Lane& ln, MLane& ml, PLog&
 // TREES (-arg): *span_out receives, instead of the epoch span of the pieces, the samples below the node the update
 // creates -- the cut samples `cut` plus those below the lineage it lands on (masks of the tree before the cut), all of
 // them above the root, its own only when it falls back into its branch; `tmp` = n-1 doubles of per-lane LDS scratch
-template <bool LOG, bool TREES = false>
+template <bool LOG, bool TREES = false, int PW = PF_PMAX>
 __device__ __forceinline__ void mp_genealogy_rest(Lane& ln, MLane& ml, PLog& pl, int limit, int rp, int sb, double h,
                                                   double* tc_out, double* sp_out, bool* changed_out, double* tfirst_out = nullptr,
                                                   unsigned* span_out = nullptr, unsigned cut = 0, double* tmp = nullptr) {
     const int n = ln.n;
     MP_TICK(tg0);
     int b_id = LC(ln, rp, sb), s_id = LC(ln, rp, 1 - sb);
-    const int pf0 = mp_pop_at(ln, ml, b_id, h);
+    const int pf0 = mp_pop_at<PW>(ln, ml, b_id, h);
     MP_TICK(tg1);
     MP_ACC(ml, 1, tg0, tg1);
     MWalk W;
-    mp_coalesce<LOG>(ln, ml, n - 1, n + n - 2, h, pf0, pl, limit, W);
+    mp_coalesce<LOG, PW>(ln, ml, n - 1, n + n - 2, h, pf0, pl, limit, W);
     MP_TICK(tg2);
     const double tc = W.tc;
     *tc_out = tc;

@@ -83,6 +83,9 @@ __device__ __forceinline__ void store_mp_state(const KA& A, const DState& st, co
     }
 }
 
+// PW: the population width of the walk (pf_mp.h) in k_init_mp, k_extend_mp, k_calibrate_mp and k_tbl_mp: PF_PMAX, or PF_PWIDE for the models
+// of five to eight populations (chosen by KArgs::P where they are launched).  The instances of PF_PMAX are, instruction for instruction, the kernels from before there was a choice.
+template <int PW = PF_PMAX>
 __global__ __launch_bounds__(PF_BS) void k_init_mp(KArgs A, double initial_position) {
     extern __shared__ double smem[];
     Smem m = carve(smem, A.n, A.E);
@@ -112,7 +115,7 @@ __global__ __launch_bounds__(PF_BS) void k_init_mp(KArgs A, double initial_posit
     pl.base = A.plog + (size_t)p * A.pcap * 3; pl.cap = A.pcap; pl.idx = 0; pl.pos = 0; pl.on = true; pl.fopen = false; pl.ropen = false;
     // every coalescence of the initial tree is logged as a type-2 record at position 0 (particle.cpp:251-300)
     double w0 = 1.0 / (double)A.Np;
-    mp_build_initial_tree<true>(ln, ml, pl, [&](int i, unsigned p0, unsigned np_, double tc, unsigned below) {
+    mp_build_initial_tree<true, PW>(ln, ml, pl, [&](int i, unsigned p0, unsigned np_, double tc, unsigned below) {
         if (ln.vbc) { w0 *= ln.upd_fac; ln.upd_fac = 1.0; }
         double* rec = rec_ptr(A, p, widx);
         rec[0] = 0.0; rec[1] = 0.0; rec[2] = 0.0;
@@ -149,7 +152,8 @@ __global__ __launch_bounds__(PF_BS) void k_init_mp(KArgs A, double initial_posit
 // BIASED = false: no focused sampling and no guide; their code is compiled out
 // TREES (-arg): every record carries the samples below the cut branch and below the node the update creates (where the
 // other instances store the epoch span of the record's pieces), and neither the record ring nor the piece ring may wrap
-template <bool BIASED, bool TREES = false>
+// PW = PF_PWIDE: five to eight populations, at every number of haplotypes (the register-tree kernel stays at PF_PMAX)
+template <bool BIASED, bool TREES = false, int PW = PF_PMAX>
 __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
     extern __shared__ double smem[];
     Smem m = carve(smem, A.n, A.E);
@@ -275,7 +279,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
                 MP_TICK(tu1);
                 MP_ACC(ml, 8, tu0, tu1);
                 unsigned span = 0;
-                mp_genealogy_rest<true, TREES>(ln, ml, pl, limit, rp, sb, h, &tc, &sp_removed, &changed, &tfirst, &span, desc, tmp0);
+                mp_genealogy_rest<true, TREES, PW>(ln, ml, pl, limit, rp, sb, h, &tc, &sp_removed, &changed, &tfirst, &span, desc, tmp0);
                 if (ln.vbc) { w_post *= ln.upd_fac; w_pilot *= ln.upd_fac; ln.upd_fac = 1.0; }
                 rec[2] = h;
                 rec[3] = piece_ref(p0, pl.idx - p0);
@@ -1123,6 +1127,7 @@ __global__ __launch_bounds__(64 * (64 / LA)) void k_sweep_xmp(const SweepChunk* 
     if (PL.row.extend || PL.row.complete) extend_mpr_body<NM, BIASED, LA, TREES, true, LOOK>(A, s, 0, PL.row);
 }
 
+template <int PW = PF_PMAX>
 __global__ __launch_bounds__(PF_BS) void k_calibrate_mp(KArgs A, unsigned long long seed, long long rep0, long long nrep,
                                                         int* out_epoch, double* out_dist, int* out_err) {
     extern __shared__ double smem[];
@@ -1141,7 +1146,7 @@ __global__ __launch_bounds__(PF_BS) void k_calibrate_mp(KArgs A, unsigned long l
     ln.ebuf = -dlog(uni(ln));
     PLog nolog;
     nolog.on = false;
-    mp_build_initial_tree<false>(ln, ml, nolog, [&](int, unsigned, unsigned, double, unsigned) {});
+    mp_build_initial_tree<false, PW>(ln, ml, nolog, [&](int, unsigned, unsigned, double, unsigned) {});
     double* orig = m.t0 + threadIdx.x;
     int alive = n - 1;
     for (int j = 0; j < n - 1; ++j) {
@@ -1158,7 +1163,7 @@ __global__ __launch_bounds__(PF_BS) void k_calibrate_mp(KArgs A, unsigned long l
         double h, tc, sp;
         bool changed;
         sample_point(ln, &rp, &sb, &h);
-        mp_genealogy_rest<false>(ln, ml, nolog, -1, rp, sb, h, &tc, &sp, &changed);
+        mp_genealogy_rest<false, false, PW>(ln, ml, nolog, -1, rp, sb, h, &tc, &sp, &changed);
         if (ml.err) break;
         if (changed) {
             for (int j = 0; j < n - 1; ++j)
@@ -1233,6 +1238,7 @@ __global__ __launch_bounds__(PF_BS) void k_simulate_mp(KArgs A, unsigned long lo
 
 // calculate_terminal_branch_length_quantiles (smcsmc.cpp:128-166) for a structured model: the parent height of every
 // leaf in nrep prior trees (migrations ignored: parent_height_ignoring_migrations, smcsmc.cpp:115-125) and the tree length
+template <int PW = PF_PMAX>
 __global__ __launch_bounds__(PF_BS) void k_tbl_mp(KArgs A, unsigned long long seed, long long nrep, double* out_h /* [n][nrep] */,
                                                   double* out_len /* [nrep] */, int* out_err) {
     extern __shared__ double smem[];
@@ -1251,7 +1257,7 @@ __global__ __launch_bounds__(PF_BS) void k_tbl_mp(KArgs A, unsigned long long se
     ln.ebuf = -dlog(uni(ln));
     PLog nolog;
     nolog.on = false;
-    mp_build_initial_tree<false>(ln, ml, nolog, [&](int, unsigned, unsigned, double, unsigned) {});
+    mp_build_initial_tree<false, PW>(ln, ml, nolog, [&](int, unsigned, unsigned, double, unsigned) {});
     out_len[r] = ln.Ltree;
     for (int i = 0; i < n; ++i) {
         int pr = -1;
@@ -1281,10 +1287,18 @@ int pf_mp_prepare(size_t smem, int mcap) {
         if (hipFuncSetAttribute((const void*)k_extend_mp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_extend_mp<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_extend_mp<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
-        if (hipFuncSetAttribute((const void*)k_init_mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
-        if (hipFuncSetAttribute((const void*)k_calibrate_mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
-        if (hipFuncSetAttribute((const void*)k_tbl_mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_init_mp<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_calibrate_mp<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_tbl_mp<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_simulate_mp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        // the wide walk's instances (five to eight populations; 16 KB of migration rates alone at 32 epochs and 8 populations)
+        if (hipFuncSetAttribute((const void*)k_extend_mp<false, false, PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_extend_mp<true, false, PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_extend_mp<false, true, PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_extend_mp<true, true, PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_init_mp<PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_calibrate_mp<PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_tbl_mp<PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
     }
     return 0;
 }
@@ -1338,12 +1352,14 @@ void pf_mp_launch_sweep_xl(const KArgs& A, const SweepChunk* tab, int nchunks, l
     else hipExtLaunchKernelGGL((k_sweep_xlmp<false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
 }
 void pf_mp_launch_init(const KArgs& A, double initial_position, size_t smem, hipStream_t st) {
-    hipLaunchKernelGGL(k_init_mp, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
+    if (A.P > PF_PMAX) hipLaunchKernelGGL(k_init_mp<PF_PWIDE>, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
+    else hipLaunchKernelGGL(k_init_mp<>, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
 }
-bool pf_mp_can_fuse(const KArgs& A, bool lds_tree) { return !lds_tree && A.n <= 8; }
+// (more than PF_PMAX populations: the LDS-tree kernels at every number of haplotypes)
+bool pf_mp_can_fuse(const KArgs& A, bool lds_tree) { return !lds_tree && A.n <= 8 && A.P <= PF_PMAX; }
 size_t pf_mp_reg_smem_bytes(int E, int P, int mcap) { return smem_mpr_bytes(E, P, mcap); }
 void pf_mp_launch_extend(const KArgs& A, long long s, size_t smem, hipStream_t st, bool lds_tree, int fuse) {
-    if (!lds_tree && A.n <= 8) {
+    if (!lds_tree && A.n <= 8 && A.P <= PF_PMAX) {
         const size_t sm = smem_mpr_bytes(A.E, A.P, A.mcap);
         const bool biased = A.n_bias > 0 || A.g_K > 0;
         const dim3 grid(mp_blocks(A.Np)), blk(64 * (64 / (biased ? PF_MPR_LANES_BIASED : PF_MPR_LANES_PLAIN)));
@@ -1355,6 +1371,13 @@ void pf_mp_launch_extend(const KArgs& A, long long s, size_t smem, hipStream_t s
     }
     const bool biased = A.n_bias > 0 || A.g_K > 0;
     const dim3 grid(mp_blocks(A.Np)), blk(PF_BS);
+    if (A.P > PF_PMAX) {
+        if (biased && A.rec_trees) hipLaunchKernelGGL((k_extend_mp<true, true, PF_PWIDE>), grid, blk, smem, st, A, s);
+        else if (biased) hipLaunchKernelGGL((k_extend_mp<true, false, PF_PWIDE>), grid, blk, smem, st, A, s);
+        else if (A.rec_trees) hipLaunchKernelGGL((k_extend_mp<false, true, PF_PWIDE>), grid, blk, smem, st, A, s);
+        else hipLaunchKernelGGL((k_extend_mp<false, false, PF_PWIDE>), grid, blk, smem, st, A, s);
+        return;
+    }
     if (biased && A.rec_trees) hipLaunchKernelGGL((k_extend_mp<true, true>), grid, blk, smem, st, A, s);
     else if (biased) hipLaunchKernelGGL(k_extend_mp<true>, grid, blk, smem, st, A, s);
     else if (A.rec_trees) hipLaunchKernelGGL((k_extend_mp<false, true>), grid, blk, smem, st, A, s);
@@ -1362,13 +1385,15 @@ void pf_mp_launch_extend(const KArgs& A, long long s, size_t smem, hipStream_t s
 }
 void pf_mp_launch_calibrate(const KArgs& A, unsigned long long seed, long long rep0, long long nrep, int* out_epoch,
                             double* out_dist, int* out_err, size_t smem, hipStream_t st) {
-    hipLaunchKernelGGL(k_calibrate_mp, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist,
+    if (A.P > PF_PMAX) hipLaunchKernelGGL(k_calibrate_mp<PF_PWIDE>, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist, out_err);
+    else hipLaunchKernelGGL(k_calibrate_mp<>, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist,
                        out_err);
 }
 
 void pf_mp_launch_tbl(const KArgs& A, unsigned long long seed, long long nrep, double* out_h, double* out_len, int* out_err,
                       size_t smem, hipStream_t st) {
-    hipLaunchKernelGGL(k_tbl_mp, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, nrep, out_h, out_len, out_err);
+    if (A.P > PF_PMAX) hipLaunchKernelGGL(k_tbl_mp<PF_PWIDE>, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, nrep, out_h, out_len, out_err);
+    else hipLaunchKernelGGL(k_tbl_mp<>, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, nrep, out_h, out_len, out_err);
 }
 
 void pf_mp_launch_simulate(const KArgs& A, unsigned long long seed, int nchunks, long long max_sites, double* pos, unsigned* masks,

@@ -4,7 +4,13 @@
 
 #include "pf_types.h"
 
-#define PF_PMAX 4             // populations supported by the HIP path
+#define PF_PMAX 4             // populations of the narrow instances: the register-tree kernel, the row pipelines, every walk up to four
+#define PF_PWIDE 8            // populations supported by the HIP path: five to eight run the wide walk on the LDS-tree kernels (general path)
+#define PF_EMAX_PWIDE 32      // epochs of a model of more than PF_PMAX populations: the event byte keeps five bits for the epoch there
+// the populations an entry point takes from this caller's model: PF_PWIDE where it set PF_MODEL_WIDE_POPS (smcsmc_pf.h), PF_PMAX as ever otherwise
+#define PF_POPS_TAKEN(m) (((m)->flags & PF_MODEL_WIDE_POPS) ? PF_PWIDE : PF_PMAX)
+// the population count k_count is instantiated for when the model has P (the column numbering of its AccT: create_plan, pf_get_counts)
+static inline int pf_count_pops(int P) { return P <= 2 ? P : (P <= PF_PMAX ? PF_PMAX : PF_PWIDE); }
 #define PF_MMAX 96            // migration events kept per local tree
 
 size_t pf_mp_smem_bytes(int n, int E, int P, int mcap);       // LDS-tree kernels

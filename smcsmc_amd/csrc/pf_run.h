@@ -123,17 +123,19 @@ static void with_row_instance(const pf_handle* h, F&& f) {
     else { if (biased) pick(ic<8>(), std::true_type()); else pick(ic<8>(), std::false_type()); }
 }
 
-// k_count<NM, P>: the record width (4, 8, PF_NMAX, or the wide kernels' own) and 1, 2 or PF_PMAX populations
+// k_count<NM, P>: the record width (4, 8, PF_NMAX, or the wide kernels' own) and 1, 2, PF_PMAX or PF_PWIDE populations (five to eight share the
+// last as three and four share PF_PMAX)
 template <class F>
 static void with_count_instance(const pf_handle* h, F&& f) {
     auto pick = [&](auto P) {
-        if constexpr (P != PF_PMAX) { if (h->n <= 4) return f(ic<4>(), P); }       // (three and four populations share the instances of four: none for NM = 4)
+        if constexpr (P < PF_PMAX) { if (h->n <= 4) return f(ic<4>(), P); }       // (three and four populations share the instances of four: none for NM = 4)
         if (h->n <= 8) f(ic<8>(), P); else f(ic<PF_NMAX>(), P);
     };
     if (h->P == 1 && h->wide) f(ic<PF_NMAX_WIDE>(), ic<1>());      // the wide records (descendants in their own word)
     else if (h->P == 1) pick(ic<1>());
     else if (h->P == 2) pick(ic<2>());
-    else pick(ic<PF_PMAX>());
+    else if (h->P <= PF_PMAX) pick(ic<PF_PMAX>());
+    else pick(ic<PF_PWIDE>());
 }
 
 // k_sweep_blc<NM, P, BIASED>, the second launch of run_sweep_x: the LDS tree of one population, or a structured model in registers or on the LDS tree
@@ -790,6 +792,8 @@ static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles
         // population) or PF_LA_ROW_PIPELINE_MP (structured) or PF_LA_ROW_PIPELINE_LDS (9 to 16 haplotypes) or on a handle that does not qualify for it
         // (look_on_rows, look_on_rows_mp, look_on_rows_lds),
         // the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the general kernels
+        if (g->P > PF_PMAX)
+            return "pf_run_many: a model of more than four populations runs on the general kernels (pf_run), one chunk after the other: the row pipelines stop at four populations";
         if (!runs_many(run_path(g, true)))
             return "pf_run_many: the chunks must run on the row pipeline (one population of at most 16 haplotypes, or a structured model of two to "
                    "four populations with the tree in registers, at most 8 haplotypes, or of 9 to 16 haplotypes created with PF_FLAG_MP_LDS_ROWS -- every chunk of the group then; a look-ahead only with PF_LA_ROW_PIPELINE on one "

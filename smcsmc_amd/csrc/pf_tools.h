@@ -112,8 +112,9 @@ int pf_test_search_lut(const double* tab, int32_t n, uint8_t* lut, int32_t* kbas
 int pf_terminal_branch_quantiles(const pf_model* m, uint64_t seed, int64_t n_trees, const double* quantiles, int32_t nq,
                                  double* lengths_out, double* mean_total_out, int device) {
     if (test_setup(device)) return -1;
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX || n_trees < 1) {
-        g_err = "pf_terminal_branch_quantiles: unsupported model";
+    if (m->n_pops < 1 || m->n_pops > PF_POPS_TAKEN(m) || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX ||
+        (m->n_pops > PF_PMAX && m->n_epochs > PF_EMAX_PWIDE) || n_trees < 1) {
+        g_err = "pf_terminal_branch_quantiles: unsupported model (1..4 populations, 1..8 with PF_MODEL_WIDE_POPS; 2..16 haplotypes, 1..64 epochs, at most 32 with more than four populations)";
         return -1;
     }
     const int E = m->n_epochs, n = m->nsam, P = m->n_pops;
@@ -164,9 +165,9 @@ int pf_terminal_branch_quantiles(const pf_model* m, uint64_t seed, int64_t n_tre
 static int median_survival_impl(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
                                 int64_t* trees_used, int32_t debug, int device) {
     if (test_setup(device)) return -1;
-    if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > (m->n_pops == 1 ? PF_NMAX_WIDE : PF_NMAX) || m->n_epochs < 1 ||
-        m->n_epochs > PF_EMAX) {
-        g_err = "pf_median_survival: unsupported model (nsam 2..64 with one population, 2..16 with several)";
+    if (m->n_pops < 1 || m->n_pops > PF_POPS_TAKEN(m) || m->nsam < 2 || m->nsam > (m->n_pops == 1 ? PF_NMAX_WIDE : PF_NMAX) || m->n_epochs < 1 ||
+        m->n_epochs > PF_EMAX || (m->n_pops > PF_PMAX && m->n_epochs > PF_EMAX_PWIDE)) {
+        g_err = "pf_median_survival: unsupported model (nsam 2..64 with one population, 2..16 with several; 1..4 populations, 1..8 with PF_MODEL_WIDE_POPS and then at most 32 epochs with more than four)";
         return -1;
     }
     // one population beyond 16 haplotypes (or PF_DEBUG_FORCE_WIDE): the wide kernel, same trees and walk
@@ -298,7 +299,8 @@ int pf_simulate_sites(const pf_model* m, uint64_t seed, int32_t nchunks, int64_t
                       int64_t* n_sites, int device) {
     if (test_setup(device)) return -1;
     if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX || nchunks < 1 || max_sites < 1) {
-        g_err = "pf_simulate_sites: 1..4 populations, 2..16 haplotypes, 1..64 epochs";
+        g_err = m->n_pops > PF_PMAX && m->n_pops <= PF_PWIDE ? "pf_simulate_sites: the site simulator takes at most four populations (the filter takes up to eight)"
+                                                              : "pf_simulate_sites: 1..4 populations, 2..16 haplotypes, 1..64 epochs";
         return -1;
     }
     const int E = m->n_epochs, n = m->nsam, P = m->n_pops;

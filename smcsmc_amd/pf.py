@@ -215,7 +215,10 @@ def _attach_bias(owner, cmodel, m):
 
 def _attach_structure(owner, cmodel, m, E, P):
     """Structured models (scrm -I / -eM / -ema / -ej): migration matrix [E][P][P] (backward rate p -> q per
-    generation), fixed-time moves [E][P][P] applied at the start of an epoch, and the samples' populations."""
+    generation), fixed-time moves [E][P][P] applied at the start of an epoch, and the samples' populations.  More than four populations:
+    pf_model.flags says that this caller knows them (PF_MODEL_WIDE_POPS; without it the library refuses them as it always did)."""
+    if P > 4:
+        cmodel.flags |= MODEL_WIDE_POPS
     if m.get("mig_rates") is not None:
         owner._mig = np.ascontiguousarray(m["mig_rates"], dtype=np.float64).reshape(E * P * P)
         cmodel.mig_rates = _dp(owner._mig)
@@ -329,6 +332,7 @@ RUN_PATHS = ("General", "TwoLaunch", "KPipe", "Sweep", "SweepSplit", "SweepXmp",
 # pf_get_row_form (PF_ROW_FORM_*)
 ROW_FORMS = (None, "single", "paired")
 DEBUG_NO_PAIR = 4096
+MODEL_WIDE_POPS = 4                  # pf_model.flags bit 2 (PF_MODEL_WIDE_POPS): set for every model of more than four populations
 FLAG_MP_LDS_ROWS = 8                 # pf_params.flags bit 3 (PF_FLAG_MP_LDS_ROWS): ParticleFilter(..., mp_rows=True)
 DEBUG_SIGNAL_ALL_COUNTS = 16384      # a completion signal on every second launch of a split step (A/B)
 
