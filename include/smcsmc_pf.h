@@ -40,7 +40,7 @@ typedef struct pf_model {
     int32_t n_epochs;            /* E  (Model::change_times_.size()) */
     int32_t n_pops;              /* P  (scrm -I): 1..4, or 1..8 with PF_MODEL_WIDE_POPS in flags (more than four: n_epochs <= 32, general path with the tree in LDS, no pf_run_many) */
     int32_t nsam;                /* haplotypes n: 2..64 with one population (beyond 16 without -arg and -apf), 2..16 with several (-arg included) */
-    int32_t flags;               /* bit0 -ancestral_aware, bit1 -dephase (pfparam.cpp:143-146), bit2 PF_MODEL_WIDE_POPS below */
+    int32_t flags;               /* bit0 -ancestral_aware, bit1 -dephase (pfparam.cpp:143-146), bit2 PF_MODEL_WIDE_POPS, bit3 PF_MODEL_SAMPLE_TIMES below */
     double loci_length;          /* Model::loci_length() */
     double mutation_rate;        /* per bp per generation */
     double recombination_rate;   /* per bp per generation */
@@ -72,6 +72,8 @@ typedef struct pf_model {
     const double* rate_positions;     /* [K] segment starts (0-based, first = 0, no gaps) */
     const double* rate_values;        /* [K] sampling recombination rate per bp per generation */
     const double* leaf_rel_rates;     /* [K*nsam] relative rate of every sample's lineage */
+    /* ancient samples (scrm -eI): read only when flags has PF_MODEL_SAMPLE_TIMES (a struct that ends above is never read past its end) */
+    const double* sample_times;       /* [nsam] generations, or NULL */
 } pf_model;
 
 typedef struct pf_params {
@@ -118,6 +120,17 @@ typedef struct pf_params {
  * caller: more than four populations are refused as they always were ("n_pops must be in 1..4").  The bit means nothing on a model of at
  * most four populations.  bin/smcsmc and the Python binding set it for every model of more than four populations. */
 #define PF_MODEL_WIDE_POPS 4
+/* pf_model.flags bit 3: pf_model.sample_times is there and is read (-eI: samples that are not from the present).  Sample i enters at
+ * sample_times[i] generations in sample_pops[i]; below that time its lineage does not exist (no recombination and no mutation on it, nobody
+ * coalesces into it, it is nobody's partner).  A fixed-time move (single_mig) at the start of an epoch moves the lineages that exist already: a
+ * sample that enters at that same epoch start enters in sample_pops[i] as given.  Every time must be an entry of change_times, the smallest 0, and
+ * the times ascend with the sample index (what the front-end writes); all zero is a valid model and computes, bit for bit, what the model
+ * without times does.  pf_create, pf_test_plan and pf_median_survival* take such a model with two to eight populations: general path
+ * (PF_PATH_GENERAL) on the LDS-tree kernels at every number of haplotypes, no rings.  Refused, each by name: one population (its kernels count
+ * lineages by rank), -arg, focused sampling, a guide, pf_load_lookahead, pf_run_many (pf_can_run_many answers 0), pf_simulate_sites and
+ * pf_terminal_branch_quantiles.  Without the bit the field is not read, so nothing changes for a caller whose struct ends before it.  A NULL
+ * pointer with the bit set is a model without sample times. */
+#define PF_MODEL_SAMPLE_TIMES 8
 /* pf_params.flags bit 3: a structured model (two to four populations) of 9 to 16 haplotypes gets the rings of the row pipeline, and pf_run and
  * pf_run_many take its rows there (PF_PATH_SWEEP_XLMP: k_sweep_xlmp with tree and migration list in LDS + k_sweep_blc, two launches a row where
  * the general kernels need five).  Off by default.  The handle qualifies with at most 131 072 particles, without -arg, without

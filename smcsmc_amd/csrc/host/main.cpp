@@ -51,6 +51,8 @@ static void dump_model_json(const PfParam& p) {
     }
     cout << "], \"sample_pops\": [";
     for (size_t k = 0; k < m.sample_pops.size(); ++k) cout << (k ? ", " : "") << m.sample_pops[k];
+    cout << "], \"sample_times\": [";
+    for (size_t k = 0; k < m.sample_times.size(); ++k) cout << (k ? ", " : "") << m.sample_times[k];
     cout << "], \"apf\": " << p.apf_level << ", \"apf_pipeline\": " << (p.apf_pipeline ? "true" : "false") << ", \"mp_rows\": " << (p.mp_rows ? "true" : "false") << ", \"apf_lds\": " << (p.apf_lds ? "true" : "false") << ", \"record_mask\": [";
     for (size_t k = 0; k < p.record_mask.size(); ++k) cout << (k ? ", " : "") << p.record_mask[k];
     cout << "], \"guide_positions\": [";
@@ -195,6 +197,7 @@ static void open_filter(ChunkFilter& F, PfParam& P, const HostModel& M0, int dev
         pm.vb_coal_counts = vb_cc.data(); pm.vb_mig_counts = vb_mc.data();
     }
     pm.flags = (P.ancestral_aware ? 1 : 0) | (P.dephase ? 2 : 0) | (NP > 4 ? PF_MODEL_WIDE_POPS : 0);
+    if (!M.sample_times.empty()) { pm.sample_times = M.sample_times.data(); pm.flags |= PF_MODEL_SAMPLE_TIMES; }     // -eI
     pm.loci_length = M.loci_length; pm.mutation_rate = M.mutation_rate; pm.recombination_rate = M.recombination_rate;
     pm.change_times = M.change_times.data(); pm.pop_sizes = pop_sizes.data();
     pm.record_flags = P.record_mask.data();
@@ -709,6 +712,7 @@ static void run_chunks(ChunkPlan& C, PfParam& P, const HostModel& M0) {
                     std::ostringstream note;
                     note << " rank " << r << ": chunks " << my_chunks[k0] << " to " << my_chunks[k1 - 1] << ": " << group.size()
                          << (together ? " chunk(s) ran side by side" : " chunk(s) ran one after the other");
+                    if (!P.model.sample_times.empty()) note << " (chunks in lockstep are not supported with ancient samples, -eI)";
                     std::lock_guard<std::mutex> hold(notes_lock);
                     clog << note.str() << endl;
                     P.chunk_notes.push_back(note.str());

@@ -81,6 +81,12 @@ void HostModel::parse(const std::vector<std::string>& tok) {
     };
     auto operand_follows = [&]() { return i + 1 < tok.size() && !is_flag(tok[i + 1]); };
     sample_pops.assign(nsam, 0);
+    sample_times.clear();
+    // -I and -eI: the samples of -I come first in the .seg columns, those of every -eI follow in the order of the command line
+    // (populationmodels.py:277-296); the counts are checked against -nsam once all are known
+    struct SampleGroup { double t; std::vector<int> count; };
+    std::vector<SampleGroup> groups;
+    bool have_I = false, have_eI = false;
     while (i < tok.size()) {
         const string f = tok[i];
         if (f == "-N0") {
@@ -91,13 +97,10 @@ void HostModel::parse(const std::vector<std::string>& tok) {
             need(f, 2); R = convert<double>(f, tok[++i]); loci_length = convert<double>(f, tok[++i]); have_r = true;
         } else if (f == "-I") {
             need(f, 1 + (size_t)P); ++i;
-            int idx = 0, total = 0;
-            for (int p = 0; p < P; ++p) {
-                int c = convert<int>(f, tok[++i]);
-                total += c;
-                for (int k = 0; k < c && idx < nsam; ++k) sample_pops[idx++] = p;
-            }
-            if (total != nsam) throw InvalidInput("Sample sizes in -I do not add up to -nsam");
+            SampleGroup g{0.0, {}};
+            for (int p = 0; p < P; ++p) g.count.push_back(convert<int>(f, tok[++i]));
+            groups.insert(groups.begin(), g);
+            have_I = true;
             if (operand_follows()) {   // optional symmetric migration rate
                 double M = convert<double>(f, tok[++i]);
                 Change& c = at(0.0);
@@ -180,11 +183,30 @@ void HostModel::parse(const std::vector<std::string>& tok) {
         } else if (f == "-bias_strengths") {
             while (operand_follows()) bias_strengths.push_back(convert<double>(f, tok[++i]));
         } else if (f == "-eI") {
-            throw Unsupported("-eI (ancient samples)");
+            // scrm -eI t n_1 .. n_P: samples that enter at t (units of 4 N0); a sample time is a change point like every other -e flag's
+            need(f, 1 + (size_t)P);
+            SampleGroup g{convert<double>(f, tok[++i]) * 4 * N0, {}};
+            if (!(g.t >= 0)) throw InvalidInput("Negative sample time in -eI");
+            for (int p = 0; p < P; ++p) g.count.push_back(convert<int>(f, tok[++i]));
+            at(g.t);
+            groups.push_back(g);
+            have_eI = true;
         } else {
             throw UnknowArg(f);
         }
         ++i;
+    }
+    if (have_I || have_eI) {
+        int idx = 0, total = 0;
+        std::vector<double> times;
+        for (const SampleGroup& g : groups)
+            for (int p = 0; p < P; ++p) {
+                if (g.count[p] < 0) throw InvalidInput("Negative sample size in -I / -eI");
+                total += g.count[p];
+                for (int k = 0; k < g.count[p] && idx < nsam; ++k) { sample_pops[idx++] = p; times.push_back(g.t); }
+            }
+        if (total != nsam) throw InvalidInput(have_eI ? "Sample sizes in -I and -eI do not add up to -nsam" : "Sample sizes in -I do not add up to -nsam");
+        if (have_eI) sample_times = times;
     }
     if (!have_r) throw std::invalid_argument("The option -r is required");     // pfparam.cpp:266-270
     if (!have_t) throw std::invalid_argument("The option -t is required");     // pfparam.cpp:258-263
@@ -503,6 +525,18 @@ void PfParam::finalize() {
         if (model.npop > 1) throw Unsupported("-nsam " + to_string(nsam) + " with " + to_string(model.npop) + " populations (more than 16 haplotypes need one population)");
         if (record_trees) throw Unsupported("-arg with more than 16 haplotypes");
         if (apf_level > 0) throw Unsupported("-apf with more than 16 haplotypes");
+    }
+    if (!model.sample_times.empty()) {
+        // ancient samples run on the general path of a structured model; what that path does not do with them is refused here, before any work
+        if (model.npop < 2) throw Unsupported("-eI (ancient samples) with one population");
+        // the -eI groups keep the order of the command line, which is the order of the .seg columns; the library wants ascending times
+        if (!std::is_sorted(model.sample_times.begin(), model.sample_times.end()))
+            throw Unsupported("-eI times that do not ascend in the order of the command line (the samples' columns follow that order)");
+        if (record_trees) throw Unsupported("-arg with ancient samples (-eI)");
+        if (apf_level > 0) throw Unsupported("-apf with ancient samples (-eI)");
+        if (!model.bias_heights.empty() || !model.bias_strengths.empty()) throw Unsupported("-bias_heights with ancient samples (-eI)");
+        if (!guide_path.empty()) throw Unsupported("-guide with ancient samples (-eI)");
+        if (mp_rows) throw Unsupported("-mp_rows (chunks in lockstep) with ancient samples (-eI)");
     }
     if (!guide_path.empty()) {
         read_guide_file(guide_path);

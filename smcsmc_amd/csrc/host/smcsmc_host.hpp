@@ -105,6 +105,7 @@ struct HostModel {
     std::vector<std::vector<double>> coal_counts; // [E][P]   -vb event counts (1e10 when not given)
     std::vector<std::vector<double>> mig_counts;  // [E][P*P]
     std::vector<int> sample_pops;
+    std::vector<double> sample_times;            // -eI: generations at which the samples enter, [nsam] in .seg column order; empty without -eI
     std::vector<double> bias_heights, bias_strengths;
     bool vb = false;
     uint64_t seed = 0;

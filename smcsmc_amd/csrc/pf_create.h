@@ -48,6 +48,16 @@ static int refuse_model(const pf_model* m, const pf_params* p) {
         }
     }
     if (p->mig_cap > 4096) return fail("pf_create: mig_cap out of range");
+    // ancient samples (PF_MODEL_SAMPLE_TIMES): the times themselves, then what does not run with them
+    {
+        std::string why;
+        if (sample_times_refusal(m, why, "pf_create")) return fail(why);
+        if (model_sample_times(m)) {
+            if (p->flags & 2) return fail("pf_create: tree recording (-arg) is not supported with sample times (-eI, ancient samples)");
+            if (m->n_bias_heights > 0) return fail("pf_create: focused sampling (bias_heights) is not supported with sample times (-eI, ancient samples)");
+            if (m->n_rate_segments > 0) return fail("pf_create: a recombination guide is not supported with sample times (-eI, ancient samples)");
+        }
+    }
     if (m->vb_coal_counts) {
         const size_t nc = (size_t)m->n_epochs * m->n_pops, nm = nc * m->n_pops;
         for (size_t i = 0; i < nc; ++i) if (!(m->vb_coal_counts[i] > 0)) return fail("pf_create: variational-Bayes event counts must be positive");
@@ -97,7 +107,8 @@ static CreatePlan create_plan(const pf_model* m, const pf_params* p, long long l
     pl.wide = wide;
     pl.nblocks = (int)((Np + PF_BS - 1) / PF_BS);
     pl.mcap = p->mig_cap > 0 ? p->mig_cap : PF_MMAX;
-    pl.smem = P > 1 ? pf_mp_smem_bytes(n, E, P, pl.mcap) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
+    const bool anc = model_sample_times(m) != nullptr;      // ancient samples (refuse_model: structured, no -arg): the ANC instances' LDS
+    pl.smem = P > 1 ? (anc ? pf_mp_smem_bytes_anc(n, E, P, pl.mcap) : pf_mp_smem_bytes(n, E, P, pl.mcap)) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
     pl.max_trace_events = std::max(0, p->max_trace_events);
     if (p->flags & 2) {
         // -arg: the parent table of every resampling is kept (it is the ancestry the tree dump walks back through).
@@ -117,7 +128,8 @@ static CreatePlan create_plan(const pf_model* m, const pf_params* p, long long l
     if (P == 1 && n <= 8 && fits) pl.rings = Rings::Reg;      // (with a switch or a look-ahead that takes the rows elsewhere the rings are there, unused)
     // structured models with the tree in registers: the same pipeline, the extend role as its own launch (run_sweep_x)
     // (more than PF_PMAX populations: no rings -- the general path on the LDS-tree kernels at every number of haplotypes, the wide walk of pf_mp.h)
-    else if (P > PF_PMAX) pl.rings = Rings::None;
+    // (sample times: the same -- no rings, the general path on the ANC instances of the LDS-tree kernels at every number of haplotypes)
+    else if (P > PF_PMAX || anc) pl.rings = Rings::None;
     else if (P > 1 && n <= 8 && fits && plain) pl.rings = Rings::Xmp;
     // one population on the LDS tree, several chunks in lockstep (pf_run_many): the same rings, the extend role k_sweep_xl.  Not with a
     // generation ring too short for an extend role that runs ahead of the counts (what pf_create refuses for structured models; here the
@@ -398,7 +410,7 @@ static int create_prepare(pf_handle* h, const pf_params* p) {
     // structured models: the LDS-tree kernels serve the prior tree and calibration for every n, the row kernel is the
     // register-tree one for n <= 8
     // (and the only one beyond PF_PMAX populations, where they are the row kernel at every n)
-    const bool lds_rows = P > 1 && (n > 8 || P > PF_PMAX || (p->debug & PF_DEBUG_FORCE_LDS));
+    const bool lds_rows = P > 1 && (n > 8 || P > PF_PMAX || A.anc || (p->debug & PF_DEBUG_FORCE_LDS));
     if (h->smem > 160 * 1024 || (P > 1 && pf_mp_prepare(h->smem, A.mcap)) ||
         (P > 1 && !lds_rows && pf_mp_reg_smem_bytes(E, P, A.mcap) > 160 * 1024))
         return fail(P > 1 ? "pf_create: the local-tree state (tree, epoch tables and pf_params.mig_cap migration events per lane) does not fit the LDS of one workgroup"

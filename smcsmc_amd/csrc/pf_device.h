@@ -406,6 +406,10 @@ struct Lane {
     double Ltree;
     const double* vbc;        // variational-Bayes factor per (epoch[, population]) of a coalescence, or null
     double upd_fac;           // product of the factors of the events of the current walk
+    // ancient samples (the ANC instances of the structured kernels, pf_mp.hip): ST[i] = the time at which sample i enters (LDS), STsum their sum.
+    // Null in every other kernel, where the tests below are decided when it is compiled: leaves at height 0, as ever.
+    const double* ST = nullptr;
+    double STsum = 0.0;
 };
 
 #define LS(ln, r) ((ln).S[(r) * PF_BS])
@@ -433,7 +437,9 @@ __device__ __forceinline__ int epoch_of(const Lane& ln, double t) {
     return e;
 }
 __device__ __forceinline__ double epoch_end(const Lane& ln, int e) { return e + 1 < ln.E ? ln.T[e + 1] : PF_INF; }
-__device__ __forceinline__ double node_h(const Lane& ln, int id) { return id < ln.n ? 0.0 : LS(ln, id - ln.n); }
+__device__ __forceinline__ double node_h(const Lane& ln, int id) { return id < ln.n ? (ln.ST ? ln.ST[id] : 0.0) : LS(ln, id - ln.n); }
+// sample `id` (< n) is not in the tree at `time` yet (ancient samples only)
+__device__ __forceinline__ bool leaf_absent(const Lane& ln, int id, double time) { return ln.ST && id < ln.n && ln.ST[id] > time; }
 
 __device__ __forceinline__ double tree_length(const Lane& ln, int nleaves) {
     double acc = 0.0, prev = 0.0;
@@ -442,6 +448,7 @@ __device__ __forceinline__ double tree_length(const Lane& ln, int nleaves) {
         acc += (double)(nleaves - r) * (s - prev);
         prev = s;
     }
+    if (ln.ST) acc -= ln.STsum;          // the branch above sample i starts at ST[i]
     return acc;
 }
 
@@ -454,7 +461,7 @@ __device__ __forceinline__ int lineages_at(const Lane& ln, int ni, double time, 
     for (int r = R; r < ni; ++r)
         for (int s = 0; s < 2; ++s) {
             int id = LC(ln, r, s);
-            if (id < ln.n || id - ln.n < R) {
+            if ((id < ln.n || id - ln.n < R) && !leaf_absent(ln, id, time)) {
                 if (cnt == want) { *pr = r; *ps = s; }
                 ++cnt;
             }

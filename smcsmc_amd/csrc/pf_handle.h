@@ -157,6 +157,28 @@ int pf_device_cus(int device) {
     return cus[(size_t)device];
 }
 
+// Ancient samples (-eI): the model's sample times where the caller says that the field is there (PF_MODEL_SAMPLE_TIMES), else null -- the field is
+// never read without the bit.
+static const double* model_sample_times(const pf_model* m) { return (m->flags & PF_MODEL_SAMPLE_TIMES) ? m->sample_times : nullptr; }
+// What every entry point that takes sample times asks of them (null: they are fine), in the words of `who`.  One population is not in scope: its
+// kernels count the lineages of an interval by rank.
+static const char* sample_times_refusal(const pf_model* m, std::string& msg, const char* who) {
+    const double* st = model_sample_times(m);
+    if (!st) return nullptr;
+    auto fail = [&](const std::string& what) { msg = std::string(who) + ": " + what; return msg.c_str(); };
+    if (m->n_pops < 2) return fail("sample times (-eI, ancient samples) need a structured model: the one-population kernels count lineages by rank");
+    double lo = st[0];
+    for (int i = 0; i < m->nsam; ++i) {
+        bool found = false;
+        for (int e = 0; e < m->n_epochs; ++e) found |= m->change_times[e] == st[i];
+        if (!found) return fail("sample time " + std::to_string(st[i]) + " of sample " + std::to_string(i) + " is not an entry of change_times (a sample enters at the start of an epoch)");
+        if (i && st[i] < st[i - 1]) return fail("sample times must ascend with the sample index");
+        lo = std::min(lo, st[i]);
+    }
+    if (lo != 0.0) return fail("the smallest sample time must be 0");
+    return nullptr;
+}
+
 // per-epoch, per-population tables of a structured model (scrm Model::population_size / migration_rate /
 // single_mig_pop), prepared exactly as the oracle's fill_model does
 struct MpTables {
@@ -207,9 +229,12 @@ static int build_mp_tables(const pf_model* m, MpTables& t) {
         }
     t.next_join.assign(E, INFINITY);
     t.next_join_epoch.assign(E, E);
+    const double* tau = model_sample_times(m);
     for (int e = E - 2; e >= 0; --e) {
         bool moves = false;
         for (int a = 0; a < P; ++a) moves |= t.jmap[(size_t)(e + 1) * P + a] != a;
+        // ancient samples: the walk ends a stretch where samples enter too (mp_coalesce counts them in there)
+        for (int i = 0; i < n && tau; ++i) moves |= tau[i] > 0.0 && tau[i] == m->change_times[e + 1];
         t.next_join[e] = moves ? m->change_times[e + 1] : t.next_join[e + 1];
         t.next_join_epoch[e] = moves ? e + 1 : t.next_join_epoch[e + 1];
     }
@@ -238,6 +263,18 @@ static int upload_model_tables(const pf_model* m, KArgs& A, DevMem& mem, hipStre
              mem.upload(&A.next_join, t.next_join.data(), t.next_join.size(), stream) || mem.upload(&A.inv2Np, t.inv2Np.data(), t.inv2Np.size(), stream) ||
              mem.upload(&A.mig_rate, t.mrate.data(), t.mrate.size(), stream) || mem.upload(&A.mig_tot, t.mtot.data(), t.mtot.size(), stream) ||
              mem.upload(&A.join_map, t.jmap.data(), t.jmap.size(), stream) || mem.upload(&A.sample_pop, t.spop.data(), t.spop.size(), stream);
+    // ancient samples: [n] times, [E] the length of epoch e times the samples that enter after it (what k_count_anc takes off a tree's length inside e)
+    std::vector<double> anc;
+    if (!rc && P > 1 && model_sample_times(m)) {
+        const double* st = model_sample_times(m);
+        anc.assign(st, st + m->nsam);
+        for (int e = 0; e < E; ++e) {
+            int later = 0;
+            for (int i = 0; i < m->nsam; ++i) later += st[i] > m->change_times[e];
+            anc.push_back(later && e + 1 < E ? (double)later * (m->change_times[e + 1] - m->change_times[e]) : 0.0);
+        }
+        rc = mem.upload(&A.anc, anc.data(), anc.size(), stream);
+    }
     // (after a failure too: the copies queued so far read this function's vectors)
     const hipError_t synchronised = hipStreamSynchronize(stream);
     if (rc) return -1;
@@ -339,6 +376,7 @@ int pf_load_lookahead(pf_handle* h, const pf_lookahead* la) {
     if (la->level < 0 || la->level > 4) { g_err = "-apf must be in 0..4"; return -1; }
     if (la->n != h->n_segs) { g_err = "pf_load_lookahead: one look-ahead record per segment expected"; return -1; }
     if (la->level == 0) { h->A.apf = 0; h->la_flags = 0; return 0; }
+    if (h->A.anc) { g_err = "pf_load_lookahead: -apf (the auxiliary particle filter) is not supported with sample times (-eI, ancient samples)"; return -1; }
     if (h->wide) { g_err = "-apf (the auxiliary particle filter) needs nsam <= 16"; return -1; }
     const long long S = la->n;
     const int n = h->n, D = la->max_doubletons, Q = la->n_quantiles;

@@ -1347,7 +1347,9 @@ __device__ __forceinline__ double slice_len(const double (&S)[NI], int nint, int
     return acc;
 }
 
-struct Win { int e, rf; double T0, T1, a_e, b_e; bool end_seq; };
+// (dead: ancient samples -- the part of slice_len's answer for the whole epoch that does not exist yet, KArgs::anc; 0.0, known when the kernel is
+// compiled, in every count body but that of k_count_anc)
+struct Win { int e, rf; double T0, T1, a_e, b_e; bool end_seq; double dead; };
 
 // local recombination map (record_local_recomb_events, count.cpp:559-613): per workgroup the differential
 // opportunity of its window is collected in LDS bins and flushed with one global atomic per touched bin
@@ -1433,7 +1435,7 @@ __device__ __forceinline__ void stretch_contrib(AccT<P>& acc, const KA& A, const
     if (!(W.rf & REC_RECOMB) || W.e > lim_start) return;
     double xs = ovl(x0, x1, W.a_e, W.b_e);
     if (!(xs > 0.0)) return;
-    double len = slice_len<NI>(S, A.n - 1, A.n, W.T0, W.T1, 0.0, PF_INF, false);
+    double len = slice_len<NI>(S, A.n - 1, A.n, W.T0, W.T1, 0.0, PF_INF, false) - W.dead;
     // a tree that does not reach the epoch has no opportunity there: nothing to add to the sums (adding zero leaves them as
     // they are) and nothing to the map -- most (record, epoch) pairs of the old epochs, whose windows hold the most records
     if (!(len > 0.0)) return;
@@ -1645,7 +1647,8 @@ __device__ __forceinline__ int* count_flat_prefix() {
 // ACC_AT_ENTRY (k_sweep_blc4): the workgroup's accumulator -- it belongs to the position (e, bx), and the launches that write it are serial on one
 // stream -- is requested here, with the first loads, and not read, added to and written back behind the last sum, where the round trip of
 // the read was the tail of every count workgroup.  The same addition on the same two numbers; a workgroup that leaves early stores nothing.
-template <int NM, int P, bool EXACT = false, bool ACC_AT_ENTRY = false, class KA>
+// ANC (k_count_anc): the model has sample times; the recombination opportunity of a record leaves out the length of the samples that enter later.
+template <int NM, int P, bool EXACT = false, bool ACC_AT_ENTRY = false, bool ANC = false, class KA>
 __device__ __forceinline__ void count_body(const KA& A, const CountSrc& Q, int e, double win_a, double win_b, int bx, int nbxg) {
     constexpr int NI = NM - 1;
     using AC = AccT<P>;
@@ -1665,6 +1668,7 @@ __device__ __forceinline__ void count_body(const KA& A, const CountSrc& Q, int e
     W.T0 = A.T[e]; W.T1 = e + 1 < A.E ? A.T[e + 1] : PF_INF;
     W.a_e = win_a; W.b_e = win_b;
     W.end_seq = (A.L == W.b_e);
+    if constexpr (ANC) W.dead = A.anc[A.n + e]; else W.dead = 0.0;
     double* const s_lbins = count_bins();
     LMap L;
     L.lds = s_lbins; L.b0 = (long long)(W.a_e / 100.0); L.gopp = A.lmap_opp; L.gcnt = A.lmap_cnt; L.nbins = A.lmap_bins;
@@ -1886,6 +1890,14 @@ __global__ __launch_bounds__(PF_BS) void k_count(KArgs A, int e0, Windows Wn) {
     const int e = e0 + (int)blockIdx.y;
     if (e < Wn.first || e >= A.E) return;
     count_body<NM, P>(A, count_src_parity(A, A.sp, e), e, Wn.a[e], Wn.b[e], (int)blockIdx.x, (int)gridDim.x);
+}
+
+// k_count for a model with sample times (KArgs::anc; structured models on the general path only)
+template <int NM, int P>
+__global__ __launch_bounds__(PF_BS) void k_count_anc(KArgs A, int e0, Windows Wn) {
+    const int e = e0 + (int)blockIdx.y;
+    if (e < Wn.first || e >= A.E) return;
+    count_body<NM, P, false, false, true>(A, count_src_parity(A, A.sp, e), e, Wn.a[e], Wn.b[e], (int)blockIdx.x, (int)gridDim.x);
 }
 
 // k_count with the column widths of the row pipeline (KArgs::cw_off: pf_params.count_wgs was set): grid = (widest column, epochs).

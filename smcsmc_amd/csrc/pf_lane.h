@@ -117,6 +117,40 @@ __device__ __forceinline__ Lane make_lane(const KArgs& A, Smem& m, long long p) 
     return ln;
 }
 
+// sample_point (below) for ancient samples (ln.ST; the ANC instances of pf_mp.hip call it in its place): the cut is uniform on the length
+// that exists.  The intervals of sample_point's walk are split at the times at which samples enter (ascending with the sample index), and k
+// is the number of lineages present: samples entered minus nodes passed.  With all times zero every sample has entered before the first
+// interval, and the intervals, their k and the arithmetic are those of sample_point.
+__device__ __forceinline__ void sample_point_anc(Lane& ln, int* rp_out, int* sb_out, double* h_out) {
+    const int n = ln.n;
+    double r = uni(ln) * ln.Ltree;
+    double prev = 0.0, h = 0.0;
+    int lin = 0, ri = 0, si = 0;
+    while (si < n && ln.ST[si] <= 0.0) ++si;
+    for (;;) {
+        const int k = si - ri;
+        const double sr = LS(ln, ri);
+        const double tn = si < n ? ln.ST[si] : PF_INF;
+        const bool at_node = !(tn < sr);                  // the interval ends at the next node (else: at the next entry)
+        const double top = at_node ? sr : tn;
+        const double d = top - prev;
+        const double seg = (double)k * d;
+        if (r < seg || (at_node && ri == n - 2)) {
+            double q = r / d;
+            lin = min((int)q, k - 1);
+            h = prev + (q - (double)lin) * d;
+            if (!(h < top)) h = prev;
+            break;
+        }
+        r -= seg;
+        prev = top;
+        if (at_node) ++ri;
+        else while (si < n && ln.ST[si] <= prev) ++si;
+    }
+    lineages_at(ln, n - 1, h, lin, rp_out, sb_out);
+    *h_out = h;
+}
+
 // One genealogy update (SMC'): sample the recombination point, coalesce the floating lineage
 // against the old tree, re-attach.  Mirrors oracle Filter::genealogy_update step by step.
 __device__ __forceinline__ void sample_point(Lane& ln, int* rp_out, int* sb_out, double* h_out) {

@@ -235,9 +235,13 @@ __device__ __forceinline__ unsigned piece_span(int e0, int e1) { return (unsigne
 // nodes, root_id its top node or the single leaf); above the root the root's own lineage is the second active
 // lineage.  Migration events picked up on the way enter the list under PF_TAG_PATH / PF_TAG_RPATH.
 // PW = PF_PWIDE: eight counters and the 3 / 5 split of the event byte; the instances of PF_PMAX are the code they were before there was a choice.
-template <bool LOG, int PW = PF_PMAX>
+// ANC (ancient samples, ln.ST): a sample of the stored tree (its leaves are 0 .. ni) is a lineage from the time at which it enters.  Those
+// times are epoch starts and stand in ml.TJ next to the epochs with a fixed-time move (build_mp_tables), so a stretch ends there; the walk then
+// counts every leaf that enters at that time into its population -- as given: the move of that epoch start does not apply to it.
+// pr_start >= 0: the population of the root's lineage at h where the walk starts above the root (mp_root_wait), else that of the root node.
+template <bool LOG, int PW = PF_PMAX, bool ANC = false>
 __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int root_id, double h, int pf0, PLog& pl,
-                                            int limit, MWalk& W) {
+                                            int limit, MWalk& W, int pr_start = -1) {
     MP_TICK(tw0);
     const int P = ml.P;
     const int n = ln.n;
@@ -245,7 +249,7 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
     double tt = h;
     int e = epoch_of(ln, tt);
     int i = 0, j = 0;
-    int pf = pf0, pr = mp_pop_base(ln, ml, root_id);
+    int pf = pf0, pr = pr_start >= 0 ? pr_start : mp_pop_base(ln, ml, root_id);
     W.tfirst = -1.0;
     W.e0 = e; W.e1 = ln.E - 1;
     if (LOG) { pl.fopen = false; pl.ropen = false; }
@@ -274,7 +278,7 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
     for (int r = i; r < ni; ++r)
         for (int s = 0; s < 2; ++s) {
             int id = LC(ln, r, s);
-            if (id < n || id - n < i) bump(LBp(ml, id), 1);
+            if ((id < n || id - n < i) && !(ANC && leaf_absent(ln, id, tt))) bump(LBp(ml, id), 1);
         }
     // The next node and the next event are held in registers, fetched with independent LDS reads when i / j move,
     // so crossing a boundary costs one LDS round trip instead of a chain of dependent ones.
@@ -396,6 +400,11 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
             tt = tn;
             e = en;
             advance(tt);
+            if constexpr (ANC) {
+                if (at_join)
+                    for (int id = 0; id <= ni; ++id)
+                        if (ln.ST[id] == tt) bump(ml.SP[id], 1);
+            }
             if (at_join) {
                 int q = ml.JM[e * P + pf];
                 if (q != pf) { PF_MP_BUF_PUSH(tt, PF_TAG_PATH, mp_ev_byte<PW>(q, e)); pf = q; }
@@ -481,6 +490,55 @@ __device__ __forceinline__ void mp_coalesce(Lane& ln, MLane& ml, int ni, int roo
 #undef PF_MP_FLUSH_BUFFER
 #undef PF_MP_BUF_PUSH
 
+// Ancient samples: the root's lineage of the partial tree between the root (height t0, population pr) and the time t_end > t0 at which the next
+// sample enters -- an epoch start.  It is alone: it migrates at the rate of its population and epoch and takes the fixed-time moves of the epoch
+// starts it reaches, that of t_end included (it exists there; the sample that enters does not move).  Its events enter the list under
+// PF_TAG_RPATH and its stretches the piece ring as pieces of the root's lineage, as in the walk.  Returns its population at t_end.
+template <bool LOG, int PW>
+__device__ __forceinline__ int mp_root_wait(Lane& ln, MLane& ml, PLog& pl, double t0, int pr, double t_end) {
+    const int P = ml.P;
+    double tt = t0, open = t0;
+    int e = epoch_of(ln, tt);
+    auto piece = [&](double t1, int kind, int to) __attribute__((always_inline)) {
+        if (LOG && pl.on && (t1 > open || kind)) plog_write(pl, pr, kind | 4, to, 0, open, t1);
+        open = t1;
+    };
+    for (int guard = 0; guard < 4096 && tt < t_end && !ml.err; ++guard) {
+        const double up = epoch_end(ln, e);               // <= t_end: t_end is an epoch start above tt
+        const double rate = ml.MT[e * P + pr];
+        const double need = rate * (up - tt);
+        if (ln.ebuf > need) {
+            ln.ebuf -= need;
+            tt = up;
+            ++e;
+            const int q = ml.JM[e * P + pr];
+            if (q != pr) { piece(tt, 0, 0); mp_ev_insert(ml, tt, PF_TAG_RPATH, mp_ev_byte<PW>(q, e)); pr = q; }
+            continue;
+        }
+        double t1 = tt + ln.ebuf / rate;
+        if (t1 > up) t1 = up;
+        double v = philox_uniform(ln.seed, ln.slot, ln.stream, ln.ctr) * rate;
+        ln.ebuf = -dlog(philox_uniform(ln.seed, ln.slot, ln.stream, ln.ctr + 1));
+        ln.ctr += 2;
+        int to = -1;
+        for (int q = 0; q < P; ++q) {
+            const double mr = ml.MR[(e * P + pr) * P + q];
+            if (q == pr || mr == 0.0) continue;
+            to = q;
+            if (v < mr) break;
+            v -= mr;
+        }
+        piece(t1, 2, to);
+        if (ln.vbc) ln.upd_fac *= ml.vbm[(e * P + pr) * P + to];
+        mp_ev_insert(ml, t1, PF_TAG_RPATH, mp_ev_byte<PW>(to, e));
+        pr = to;
+        tt = t1;
+    }
+    if (tt < t_end && !ml.err) ml.err = 3;                // the guard ran out, as in mp_coalesce
+    piece(t_end, 0, 0);
+    return pr;
+}
+
 __device__ __forceinline__ void mp_retag(MLane& ml, int from, int to) {
     for (int m = 0; m < ml.nm; ++m)
         if (LMb(ml, m) == from) LMb(ml, m) = (int8_t)to;
@@ -489,7 +547,9 @@ __device__ __forceinline__ void mp_retag(MLane& ml, int from, int to) {
 // Forest::buildInitialTree(true) for a structured model.  `emit(i, pstart, npieces, tc, below)` logs the record of leaf i;
 // `below` = the samples under the node leaf i creates (computed when `tmp`, n-1 doubles of per-lane LDS scratch, is given;
 // otherwise the epoch span of the walk's pieces, piece_span).
-template <bool LOG, int PW = PF_PMAX, class Emit>
+// ANC (ancient samples): the walk of leaf i starts at the time at which it enters.  The times ascend with the index, so every leaf of the partial tree
+// has entered by then; where the partial tree's root lies below that time its lineage is taken up to it first (mp_root_wait).
+template <bool LOG, int PW = PF_PMAX, bool ANC = false, class Emit>
 __device__ __forceinline__ void mp_build_initial_tree(Lane& ln, MLane& ml, PLog& pl, Emit emit, double* tmp = nullptr) {
     const int n = ln.n;
     ml.nm = 0;
@@ -498,6 +558,14 @@ __device__ __forceinline__ void mp_build_initial_tree(Lane& ln, MLane& ml, PLog&
         int ni = i - 1;
         MWalk W;
         unsigned p0 = LOG ? pl.idx : 0u;
+        if constexpr (ANC) {
+            const double h0 = ln.ST[i], Hr = node_h(ln, root);
+            int pr0 = -1, e0 = ln.E;
+            if (h0 > Hr) { e0 = epoch_of(ln, Hr); pr0 = mp_root_wait<LOG, PW>(ln, ml, pl, Hr, mp_pop_base(ln, ml, root), h0); }
+            if (ml.err) return;
+            mp_coalesce<LOG, PW, true>(ln, ml, ni, root, h0, ml.SP[i], pl, ln.E - 1, W, pr0);
+            if (e0 < W.e0) W.e0 = e0;                     // the pieces of the root's wait lie in earlier epochs
+        } else
         mp_coalesce<LOG, PW>(ln, ml, ni, root, 0.0, ml.SP[i], pl, ln.E - 1, W);
         if (ml.err) return;
         const unsigned np_ = LOG ? pl.idx - p0 : 0u;
@@ -531,7 +599,7 @@ __device__ __forceinline__ void mp_build_initial_tree(Lane& ln, MLane& ml, PLog&
 // TREES (-arg): *span_out receives, instead of the epoch span of the pieces, the samples below the node the update
 // creates -- the cut samples `cut` plus those below the lineage it lands on (masks of the tree before the cut), all of
 // them above the root, its own only when it falls back into its branch; `tmp` = n-1 doubles of per-lane LDS scratch
-template <bool LOG, bool TREES = false, int PW = PF_PMAX>
+template <bool LOG, bool TREES = false, int PW = PF_PMAX, bool ANC = false>
 __device__ __forceinline__ void mp_genealogy_rest(Lane& ln, MLane& ml, PLog& pl, int limit, int rp, int sb, double h,
                                                   double* tc_out, double* sp_out, bool* changed_out, double* tfirst_out = nullptr,
                                                   unsigned* span_out = nullptr, unsigned cut = 0, double* tmp = nullptr) {
@@ -542,7 +610,7 @@ __device__ __forceinline__ void mp_genealogy_rest(Lane& ln, MLane& ml, PLog& pl,
     MP_TICK(tg1);
     MP_ACC(ml, 1, tg0, tg1);
     MWalk W;
-    mp_coalesce<LOG, PW>(ln, ml, n - 1, n + n - 2, h, pf0, pl, limit, W);
+    mp_coalesce<LOG, PW, ANC>(ln, ml, n - 1, n + n - 2, h, pf0, pl, limit, W);
     MP_TICK(tg2);
     const double tc = W.tc;
     *tc_out = tc;

@@ -63,6 +63,20 @@ __device__ __forceinline__ MLane make_mlane(const KA& A, SmemMP& m) {
     ml.err = 0;
     return ml;
 }
+// Ancient samples (the PF_ANC instances of k_init_mp, k_extend_mp and k_calibrate_mp below; KArgs::anc): the times at which the samples enter, n doubles
+// BEHIND the carve-up above, which stays what it is for every other instance (the launch of an ANC instance asks for smem_anc_extra more).
+__host__ __device__ static size_t smem_anc_extra(int n) { return (size_t)n * 8; }
+__device__ __forceinline__ double* carve_anc(const SmemMP& m, int n) { return (double*)(m.Bp + (size_t)2 * n * PF_BS); }
+__device__ __forceinline__ void load_model_anc(const KArgs& A, const SmemMP& m) {
+    double* st = carve_anc(m, A.n);
+    for (int i = threadIdx.x; i < A.n; i += blockDim.x) st[i] = A.anc[i];
+}
+__device__ __forceinline__ void lane_bind_anc(Lane& ln, const SmemMP& m) {
+    ln.ST = carve_anc(m, ln.n);
+    double sum = 0.0;
+    for (int i = 0; i < ln.n; ++i) sum += ln.ST[i];
+    ln.STsum = sum;
+}
 template <class KA>      // (the argument block by value, or in the constant address space: k_sweep_xlmp)
 __device__ __forceinline__ void mp_report(const KA& A, const MLane& ml) {
     // an error of an earlier row stays the one reported (what follows it on a broken state is a consequence)
@@ -85,13 +99,20 @@ __device__ __forceinline__ void store_mp_state(const KA& A, const DState& st, co
 
 // PW: the population width of the walk (pf_mp.h) in k_init_mp, k_extend_mp, k_calibrate_mp and k_tbl_mp: PF_PMAX, or PF_PWIDE for the models
 // of five to eight populations (chosen by KArgs::P where they are launched).  The instances of PF_PMAX are, instruction for instruction, the kernels from before there was a choice.
-template <int PW = PF_PMAX>
+// PW + PF_ANC: the instance for a model with sample times (KArgs::anc, PF_MODEL_SAMPLE_TIMES) of k_init_mp, k_extend_mp<false, false, .> and
+// k_calibrate_mp.  Everything that reads the times hangs on this one switch -- it binds Lane::ST, null otherwise, and picks the ANC forms of the
+// walk.  It rides in the template argument the kernels had, so that the instances without it keep their names and are the kernels they were.
+#define PF_ANC 16
+template <int PWA = PF_PMAX>
 __global__ __launch_bounds__(PF_BS) void k_init_mp(KArgs A, double initial_position) {
+    constexpr int PW = PWA & ~PF_ANC;
+    constexpr bool ANC = (PWA & PF_ANC) != 0;
     extern __shared__ double smem[];
     Smem m = carve(smem, A.n, A.E);
     SmemMP mm = carve_mp(smem, A.n, A.E, A.P, A.mcap);
     load_model(A, m);
     load_model_mp(A, mm);
+    if constexpr (ANC) load_model_anc(A, mm);
     __syncthreads();
     long long p = (long long)blockIdx.x * PF_BS + threadIdx.x;
     if (p == 0) {
@@ -109,13 +130,14 @@ __global__ __launch_bounds__(PF_BS) void k_init_mp(KArgs A, double initial_posit
     const int n = A.n;
     Lane ln = make_lane(A, m, p);
     MLane ml = make_mlane(A, mm);
+    if constexpr (ANC) lane_bind_anc(ln, mm);
     ln.ebuf = -dlog(uni(ln));
     unsigned widx = 0;
     PLog pl;
     pl.base = A.plog + (size_t)p * A.pcap * 3; pl.cap = A.pcap; pl.idx = 0; pl.pos = 0; pl.on = true; pl.fopen = false; pl.ropen = false;
     // every coalescence of the initial tree is logged as a type-2 record at position 0 (particle.cpp:251-300)
     double w0 = 1.0 / (double)A.Np;
-    mp_build_initial_tree<true, PW>(ln, ml, pl, [&](int i, unsigned p0, unsigned np_, double tc, unsigned below) {
+    mp_build_initial_tree<true, PW, ANC>(ln, ml, pl, [&](int i, unsigned p0, unsigned np_, double tc, unsigned below) {
         if (ln.vbc) { w0 *= ln.upd_fac; ln.upd_fac = 1.0; }
         double* rec = rec_ptr(A, p, widx);
         rec[0] = 0.0; rec[1] = 0.0; rec[2] = 0.0;
@@ -153,13 +175,18 @@ __global__ __launch_bounds__(PF_BS) void k_init_mp(KArgs A, double initial_posit
 // TREES (-arg): every record carries the samples below the cut branch and below the node the update creates (where the
 // other instances store the epoch span of the record's pieces), and neither the record ring nor the piece ring may wrap
 // PW = PF_PWIDE: five to eight populations, at every number of haplotypes (the register-tree kernel stays at PF_PMAX)
-template <bool BIASED, bool TREES = false, int PW = PF_PMAX>
+// PW + PF_ANC: ancient samples (see k_init_mp); without focused sampling, guide and -arg
+template <bool BIASED, bool TREES = false, int PWA = PF_PMAX>
 __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
+    constexpr int PW = PWA & ~PF_ANC;
+    constexpr bool ANC = (PWA & PF_ANC) != 0;
+    static_assert(!ANC || (!BIASED && !TREES), "sample times run without focused sampling, guide and -arg");
     extern __shared__ double smem[];
     Smem m = carve(smem, A.n, A.E);
     SmemMP mm = carve_mp(smem, A.n, A.E, A.P, A.mcap);
     load_model(A, m);
     load_model_mp(A, mm);
+    if constexpr (ANC) load_model_anc(A, mm);
     __shared__ double sBH[PF_BIAS_MAX + 2], sBS[PF_BIAS_MAX + 1];      // focused sampling: band boundaries / strengths
     if (threadIdx.x < PF_BIAS_MAX + 2) {
         sBH[threadIdx.x] = A.bias_H[threadIdx.x];
@@ -186,6 +213,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
         const DState st = state_slot(A, cur);
         Lane ln = make_lane(A, m, p);
         MLane ml = make_mlane(A, mm);
+        if constexpr (ANC) lane_bind_anc(ln, mm);
         DStore ds;
         d_bind(ds, A, st, p);
         ds.count = 0; ds.total = 1.0;
@@ -272,6 +300,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
                     sample_point_guided(ln, sBH, sBS, A.n_bias + 1, A.g_leaf + (size_t)ridx * n, A.rho / A.g_rho[ridx], &rp, &sb, &h,
                                         &iw, &rbiw, tmp0);
                 else if (biased) { sample_point_biased(ln, sBH, sBS, A.n_bias + 1, &rp, &sb, &h, &iw); rbiw = iw; }
+                else if constexpr (ANC) sample_point_anc(ln, &rp, &sb, &h);
                 else sample_point(ln, &rp, &sb, &h);
                 const unsigned desc = (TREES || A.lmap_opp) ? lane_desc_mask(ln, LC(ln, rp, sb), tmp0) : 0u;
                 unsigned p0 = pl.idx;
@@ -279,7 +308,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
                 MP_TICK(tu1);
                 MP_ACC(ml, 8, tu0, tu1);
                 unsigned span = 0;
-                mp_genealogy_rest<true, TREES, PW>(ln, ml, pl, limit, rp, sb, h, &tc, &sp_removed, &changed, &tfirst, &span, desc, tmp0);
+                mp_genealogy_rest<true, TREES, PW, ANC>(ln, ml, pl, limit, rp, sb, h, &tc, &sp_removed, &changed, &tfirst, &span, desc, tmp0);
                 if (ln.vbc) { w_post *= ln.upd_fac; w_pilot *= ln.upd_fac; ln.upd_fac = 1.0; }
                 rec[2] = h;
                 rec[3] = piece_ref(p0, pl.idx - p0);
@@ -1127,26 +1156,30 @@ __global__ __launch_bounds__(64 * (64 / LA)) void k_sweep_xmp(const SweepChunk* 
     if (PL.row.extend || PL.row.complete) extend_mpr_body<NM, BIASED, LA, TREES, true, LOOK>(A, s, 0, PL.row);
 }
 
-template <int PW = PF_PMAX>
+template <int PWA = PF_PMAX>
 __global__ __launch_bounds__(PF_BS) void k_calibrate_mp(KArgs A, unsigned long long seed, long long rep0, long long nrep,
                                                         int* out_epoch, double* out_dist, int* out_err) {
+    constexpr int PW = PWA & ~PF_ANC;
+    constexpr bool ANC = (PWA & PF_ANC) != 0;
     extern __shared__ double smem[];
     Smem m = carve(smem, A.n, A.E);
     SmemMP mm = carve_mp(smem, A.n, A.E, A.P, A.mcap);
     load_model(A, m);
     load_model_mp(A, mm);
+    if constexpr (ANC) load_model_anc(A, mm);
     __syncthreads();
     long long r = (long long)blockIdx.x * PF_BS + threadIdx.x;
     if (r >= nrep) return;
     const int n = A.n;
     Lane ln = make_lane(A, m, rep0 + r);
     MLane ml = make_mlane(A, mm);
+    if constexpr (ANC) lane_bind_anc(ln, mm);
     ln.seed = seed;
     ln.stream = 2;
     ln.ebuf = -dlog(uni(ln));
     PLog nolog;
     nolog.on = false;
-    mp_build_initial_tree<false, PW>(ln, ml, nolog, [&](int, unsigned, unsigned, double, unsigned) {});
+    mp_build_initial_tree<false, PW, ANC>(ln, ml, nolog, [&](int, unsigned, unsigned, double, unsigned) {});
     double* orig = m.t0 + threadIdx.x;
     int alive = n - 1;
     for (int j = 0; j < n - 1; ++j) {
@@ -1162,8 +1195,8 @@ __global__ __launch_bounds__(PF_BS) void k_calibrate_mp(KArgs A, unsigned long l
         int rp = 0, sb = 0;
         double h, tc, sp;
         bool changed;
-        sample_point(ln, &rp, &sb, &h);
-        mp_genealogy_rest<false, false, PW>(ln, ml, nolog, -1, rp, sb, h, &tc, &sp, &changed);
+        if constexpr (ANC) sample_point_anc(ln, &rp, &sb, &h); else sample_point(ln, &rp, &sb, &h);
+        mp_genealogy_rest<false, false, PW, ANC>(ln, ml, nolog, -1, rp, sb, h, &tc, &sp, &changed);
         if (ml.err) break;
         if (changed) {
             for (int j = 0; j < n - 1; ++j)
@@ -1270,6 +1303,7 @@ __global__ __launch_bounds__(PF_BS) void k_tbl_mp(KArgs A, unsigned long long se
 
 // ------------------------------------------------------------------ launchers (called from pf_hip.hip)
 size_t pf_mp_smem_bytes(int n, int E, int P, int mcap) { return smem_bytes_mp(n, E, P, mcap); }
+size_t pf_mp_smem_bytes_anc(int n, int E, int P, int mcap) { return smem_bytes_mp(n, E, P, mcap) + smem_anc_extra(n); }
 
 int pf_mp_prepare(size_t smem, int mcap) {
     if (smem > 160 * 1024) return -1;
@@ -1299,6 +1333,13 @@ int pf_mp_prepare(size_t smem, int mcap) {
         if (hipFuncSetAttribute((const void*)k_init_mp<PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_calibrate_mp<PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
         if (hipFuncSetAttribute((const void*)k_tbl_mp<PF_PWIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        // the instances of the models with sample times
+        if (hipFuncSetAttribute((const void*)k_extend_mp<false, false, PF_PMAX + PF_ANC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_extend_mp<false, false, PF_PWIDE + PF_ANC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_init_mp<PF_PMAX + PF_ANC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_init_mp<PF_PWIDE + PF_ANC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_calibrate_mp<PF_PMAX + PF_ANC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
+        if (hipFuncSetAttribute((const void*)k_calibrate_mp<PF_PWIDE + PF_ANC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) return -1;
     }
     return 0;
 }
@@ -1352,13 +1393,23 @@ void pf_mp_launch_sweep_xl(const KArgs& A, const SweepChunk* tab, int nchunks, l
     else hipExtLaunchKernelGGL((k_sweep_xlmp<false>), grid, blk, smem, st, nullptr, done, 0, tab, t);
 }
 void pf_mp_launch_init(const KArgs& A, double initial_position, size_t smem, hipStream_t st) {
-    if (A.P > PF_PMAX) hipLaunchKernelGGL(k_init_mp<PF_PWIDE>, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
+    if (A.anc && A.P > PF_PMAX) hipLaunchKernelGGL((k_init_mp<PF_PWIDE + PF_ANC>), dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
+    else if (A.anc) hipLaunchKernelGGL((k_init_mp<PF_PMAX + PF_ANC>), dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
+    else if (A.P > PF_PMAX) hipLaunchKernelGGL(k_init_mp<PF_PWIDE>, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
     else hipLaunchKernelGGL(k_init_mp<>, dim3(mp_blocks(A.Np)), dim3(PF_BS), smem, st, A, initial_position);
 }
 // (more than PF_PMAX populations: the LDS-tree kernels at every number of haplotypes)
-bool pf_mp_can_fuse(const KArgs& A, bool lds_tree) { return !lds_tree && A.n <= 8 && A.P <= PF_PMAX; }
+// (sample times: the same)
+bool pf_mp_can_fuse(const KArgs& A, bool lds_tree) { return !lds_tree && A.n <= 8 && A.P <= PF_PMAX && !A.anc; }
 size_t pf_mp_reg_smem_bytes(int E, int P, int mcap) { return smem_mpr_bytes(E, P, mcap); }
 void pf_mp_launch_extend(const KArgs& A, long long s, size_t smem, hipStream_t st, bool lds_tree, int fuse) {
+    if (A.anc) {
+        // sample times (pf_create has refused focused sampling, guide and -arg): the ANC instance of the LDS-tree kernel at every number of haplotypes
+        const dim3 grid(mp_blocks(A.Np)), blk(PF_BS);
+        if (A.P > PF_PMAX) hipLaunchKernelGGL((k_extend_mp<false, false, PF_PWIDE + PF_ANC>), grid, blk, smem, st, A, s);
+        else hipLaunchKernelGGL((k_extend_mp<false, false, PF_PMAX + PF_ANC>), grid, blk, smem, st, A, s);
+        return;
+    }
     if (!lds_tree && A.n <= 8 && A.P <= PF_PMAX) {
         const size_t sm = smem_mpr_bytes(A.E, A.P, A.mcap);
         const bool biased = A.n_bias > 0 || A.g_K > 0;
@@ -1385,7 +1436,9 @@ void pf_mp_launch_extend(const KArgs& A, long long s, size_t smem, hipStream_t s
 }
 void pf_mp_launch_calibrate(const KArgs& A, unsigned long long seed, long long rep0, long long nrep, int* out_epoch,
                             double* out_dist, int* out_err, size_t smem, hipStream_t st) {
-    if (A.P > PF_PMAX) hipLaunchKernelGGL(k_calibrate_mp<PF_PWIDE>, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist, out_err);
+    if (A.anc && A.P > PF_PMAX) hipLaunchKernelGGL((k_calibrate_mp<PF_PWIDE + PF_ANC>), dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist, out_err);
+    else if (A.anc) hipLaunchKernelGGL((k_calibrate_mp<PF_PMAX + PF_ANC>), dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist, out_err);
+    else if (A.P > PF_PMAX) hipLaunchKernelGGL(k_calibrate_mp<PF_PWIDE>, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist, out_err);
     else hipLaunchKernelGGL(k_calibrate_mp<>, dim3(mp_blocks(nrep)), dim3(PF_BS), smem, st, A, seed, rep0, nrep, out_epoch, out_dist,
                        out_err);
 }

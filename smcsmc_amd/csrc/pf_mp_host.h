@@ -14,6 +14,7 @@ static inline int pf_count_pops(int P) { return P <= 2 ? P : (P <= PF_PMAX ? PF_
 #define PF_MMAX 96            // migration events kept per local tree
 
 size_t pf_mp_smem_bytes(int n, int E, int P, int mcap);       // LDS-tree kernels
+size_t pf_mp_smem_bytes_anc(int n, int E, int P, int mcap);   // their instances for models with sample times (KArgs::anc)
 size_t pf_mp_reg_smem_bytes(int E, int P, int mcap);          // register-tree row kernel
 int pf_mp_prepare(size_t smem, int mcap);      // raises the dynamic-LDS limit of the kernels; -1 if the state does not fit
 void pf_mp_launch_init(const KArgs& A, double initial_position, size_t smem, hipStream_t st);

@@ -202,6 +202,12 @@ static void enqueue_count(pf_handle* h, hipStream_t st, const Windows& W) {
                 return;
             }
         }
+        if constexpr (P > 1) {
+            if (h->A.anc) {                                    // sample times: the recombination opportunity without the samples that enter later
+                hipLaunchKernelGGL((k_count_anc<NM, P>), dim3(h->nblocks, h->E - first), dim3(PF_BS), 0, st, h->A, first, W);
+                return;
+            }
+        }
         hipLaunchKernelGGL((k_count<NM, P>), dim3(h->nblocks, h->E - first), dim3(PF_BS), 0, st, h->A, first, W);
     });
     h->fin_pending = true;
@@ -794,6 +800,8 @@ static const char* run_many_refusal(pf_handle* const* handles, int32_t n_handles
         // the wide kernels (more than 16 haplotypes); pf_run on one such handle stays on the general kernels
         if (g->P > PF_PMAX)
             return "pf_run_many: a model of more than four populations runs on the general kernels (pf_run), one chunk after the other: the row pipelines stop at four populations";
+        if (g->A.anc)
+            return "pf_run_many: a model with sample times (-eI, ancient samples) runs on the general kernels (pf_run), one chunk after the other: the row pipelines have no instance for them";
         if (!runs_many(run_path(g, true)))
             return "pf_run_many: the chunks must run on the row pipeline (one population of at most 16 haplotypes, or a structured model of two to "
                    "four populations with the tree in registers, at most 8 haplotypes, or of 9 to 16 haplotypes created with PF_FLAG_MP_LDS_ROWS -- every chunk of the group then; a look-ahead only with PF_LA_ROW_PIPELINE on one "

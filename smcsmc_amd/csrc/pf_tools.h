@@ -111,6 +111,7 @@ int pf_test_search_lut(const double* tab, int32_t n, uint8_t* lut, int32_t* kbas
 
 int pf_terminal_branch_quantiles(const pf_model* m, uint64_t seed, int64_t n_trees, const double* quantiles, int32_t nq,
                                  double* lengths_out, double* mean_total_out, int device) {
+    if (model_sample_times(m)) { g_err = "pf_terminal_branch_quantiles: not supported with sample times (-eI, ancient samples)"; return -1; }
     if (test_setup(device)) return -1;
     if (m->n_pops < 1 || m->n_pops > PF_POPS_TAKEN(m) || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX ||
         (m->n_pops > PF_PMAX && m->n_epochs > PF_EMAX_PWIDE) || n_trees < 1) {
@@ -164,6 +165,10 @@ int pf_terminal_branch_quantiles(const pf_model* m, uint64_t seed, int64_t n_tre
 
 static int median_survival_impl(const pf_model* m, uint64_t seed, int32_t min_events, int64_t max_trees, double* median_out,
                                 int64_t* trees_used, int32_t debug, int device) {
+    {
+        std::string why;
+        if (sample_times_refusal(m, why, "pf_median_survival")) { g_err = why; return -1; }
+    }
     if (test_setup(device)) return -1;
     if (m->n_pops < 1 || m->n_pops > PF_POPS_TAKEN(m) || m->nsam < 2 || m->nsam > (m->n_pops == 1 ? PF_NMAX_WIDE : PF_NMAX) || m->n_epochs < 1 ||
         m->n_epochs > PF_EMAX || (m->n_pops > PF_PMAX && m->n_epochs > PF_EMAX_PWIDE)) {
@@ -189,7 +194,8 @@ static int median_survival_impl(const pf_model* m, uint64_t seed, int32_t min_ev
     std::vector<int> hep(PF_CAL_GROUP * per_batch);
     std::vector<double> hdist(PF_CAL_GROUP * per_batch);
     long long trees = 0;
-    const size_t smem = P > 1 ? pf_mp_smem_bytes(n, E, P, PF_MMAX) : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
+    const size_t smem = P > 1 ? (model_sample_times(m) ? pf_mp_smem_bytes_anc(n, E, P, PF_MMAX) : pf_mp_smem_bytes(n, E, P, PF_MMAX))
+                              : (wide ? pf_wide_smem_bytes(n, E) : smem_bytes(n, E));
     if (P > 1 && pf_mp_prepare(smem, PF_MMAX)) { g_err = "pf_median_survival: the local-tree state does not fit the LDS"; return -1; }
     if (wide && pf_wide_prepare(smem)) { g_err = "pf_median_survival: the local-tree state does not fit the LDS"; return -1; }
     const size_t smem_cal = smem + (size_t)(2 * PF_EPAD + E) * 8;          // + the padded epoch tables of the register path
@@ -297,6 +303,7 @@ int pf_simulate_sites_wide(const pf_model* m, uint64_t seed, int32_t nchunks, in
 // masks per chunk (k_simulate).  n_sites[c] < 0: more than max_sites sites (the first max_sites are valid).
 int pf_simulate_sites(const pf_model* m, uint64_t seed, int32_t nchunks, int64_t max_sites, double* pos, uint32_t* masks,
                       int64_t* n_sites, int device) {
+    if (model_sample_times(m)) { g_err = "pf_simulate_sites: the site simulator is not supported with sample times (-eI, ancient samples)"; return -1; }
     if (test_setup(device)) return -1;
     if (m->n_pops < 1 || m->n_pops > PF_PMAX || m->nsam < 2 || m->nsam > PF_NMAX || m->n_epochs < 1 || m->n_epochs > PF_EMAX || nchunks < 1 || max_sites < 1) {
         g_err = m->n_pops > PF_PMAX && m->n_pops <= PF_PWIDE ? "pf_simulate_sites: the site simulator takes at most four populations (the filter takes up to eight)"

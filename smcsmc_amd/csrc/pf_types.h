@@ -151,7 +151,9 @@ struct KArgs {
     double bias_S[PF_BIAS_MAX + 1];
     const double* app_delays;
     int* chunk_dpend;              // [nc] particles with pending delayed factors, per wavefront
-    double delayed_count_unused;
+    // ancient samples (PF_MODEL_SAMPLE_TIMES; the PF_ANC instances of the structured LDS-tree kernels (pf_mp.hip) and k_count_anc read it, nobody else): [n] the times
+    // at which the samples enter, then [E] the tree length that does not exist yet in epoch e -- (samples that enter after e) x (length of e); null otherwise
+    const double* anc;
     // state: every array of DState holds `nslots` copies back to back and st0 points at copy 0 (state_slot() below gives
     // copy k).  Copies 0 and 1 are the double buffer of the general kernels; the single-launch pipeline uses four as a
     // ring indexed by row & (PF_RING - 1) (a row's raw weights, tree and stretch stay readable for the counts two launches later).

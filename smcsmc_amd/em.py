@@ -26,7 +26,7 @@ class PopulationModel:
 
     def __init__(self, N0=10000, mutation_rate=2.5e-8, recombination_rate=1e-8, sequence_length=1e6, num_samples=2,
                  change_points=(0.0,), population_sizes=((1.0,),), num_populations=1, migration_rates=None,
-                 sample_populations=None, migration_commands=None):
+                 sample_populations=None, migration_commands=None, sample_times=None):
         self.N0 = N0
         self.mutation_rate = mutation_rate
         self.recombination_rate = recombination_rate
@@ -40,6 +40,11 @@ class PopulationModel:
                                 else [[[0] * P for _ in range(P)] for _ in range(E)])
         self.sample_populations = list(sample_populations) if sample_populations is not None else [1] * num_samples
         self.migration_commands = list(migration_commands) if migration_commands is not None else [None] * E
+        # ancient samples (-eI): per sample the time it enters, in 4*N0 generations, ascending with the sample index, the smallest 0
+        # (populationmodels.py:209-219); every such time has to be a change point, as the front-end's _parse_time makes it one
+        self.sample_times = [float(t) for t in sample_times] if sample_times is not None else [0.0] * num_samples
+        assert len(self.sample_times) == num_samples and min(self.sample_times) == 0.0
+        assert all(a <= b for a, b in zip(self.sample_times, self.sample_times[1:])) and all(t in self.change_points for t in self.sample_times)
         # event counts carried along for the variational-Bayes command line (populationmodels.py:259-268)
         self.population_event_counts = [[1e10] * P for _ in range(E)]
         self.migration_event_counts = [[[1e10] * P for _ in range(P)] for _ in range(E)]
@@ -49,10 +54,14 @@ class PopulationModel:
     # binary parses them; the reference builds the same string in populationmodels.py:272-437 and
     # tests/golden/cmdlines.json holds its output); it is assembled here from per-epoch directives.
     def _sample_tokens(self):
-        if self.num_populations == 1:
+        if self.num_populations == 1 and max(self.sample_times) == 0.0:
             return []
-        per_pop = np.bincount(np.asarray(self.sample_populations, int), minlength=self.num_populations + 1)[1:]
-        return ["-I", self.num_populations] + per_pop.tolist()
+        out = []
+        for when in sorted(set(self.sample_times)):          # -I for the present, one -eI per earlier time (populationmodels.py:277-296)
+            pops = [q for q, t in zip(self.sample_populations, self.sample_times) if t == when]
+            per_pop = np.bincount(np.asarray(pops, int), minlength=self.num_populations + 1)[1:]
+            out += (["-I", self.num_populations] if when == 0.0 else ["-eI", when]) + per_pop.tolist()
+        return out
 
     def _size_tokens(self, epoch, vb):
         """-eN t x when all populations share a size, else one -en t pop x per population; -vb appends the event count."""
@@ -128,6 +137,8 @@ class PopulationModel:
         if vb:        # the event counts the -vb command line carries (populationmodels.py:335-398)
             m.update(vb_coal_counts=np.array(self.population_event_counts, float).reshape(E, P),
                      vb_mig_counts=np.array(self.migration_event_counts, float).reshape(E, P, P))
+        if max(self.sample_times) > 0.0:        # ancient samples: generations, like change_times (pf_model.sample_times)
+            m.update(sample_times=[float(ct[self.change_points.index(t)]) for t in self.sample_times])
         m.update(extra)
         return m
 

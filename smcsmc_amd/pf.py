@@ -42,6 +42,7 @@ class _Model(C.Structure):
         ("n_rate_segments", C.c_int32), ("reserved2", C.c_int32),
         ("rate_positions", C.POINTER(C.c_double)), ("rate_values", C.POINTER(C.c_double)),
         ("leaf_rel_rates", C.POINTER(C.c_double)),
+        ("sample_times", C.POINTER(C.c_double)),      # read by the library only with MODEL_SAMPLE_TIMES in flags
     ]
 
 
@@ -216,9 +217,17 @@ def _attach_bias(owner, cmodel, m):
 def _attach_structure(owner, cmodel, m, E, P):
     """Structured models (scrm -I / -eM / -ema / -ej): migration matrix [E][P][P] (backward rate p -> q per
     generation), fixed-time moves [E][P][P] applied at the start of an epoch, and the samples' populations.  More than four populations:
-    pf_model.flags says that this caller knows them (PF_MODEL_WIDE_POPS; without it the library refuses them as it always did)."""
+    pf_model.flags says that this caller knows them (PF_MODEL_WIDE_POPS; without it the library refuses them as it always did).
+    Ancient samples (scrm -eI): model key sample_times, the generations at which the samples enter -- entries of change_times, the smallest 0,
+    ascending with the sample index (PF_MODEL_SAMPLE_TIMES; the library says what it does not run with them)."""
     if P > 4:
         cmodel.flags |= MODEL_WIDE_POPS
+    if m.get("sample_times") is not None:
+        owner._stimes = np.ascontiguousarray(m["sample_times"], dtype=np.float64)
+        if len(owner._stimes) != cmodel.nsam:
+            raise PfError("sample_times needs one entry per sample")
+        cmodel.sample_times = _dp(owner._stimes)
+        cmodel.flags |= MODEL_SAMPLE_TIMES
     if m.get("mig_rates") is not None:
         owner._mig = np.ascontiguousarray(m["mig_rates"], dtype=np.float64).reshape(E * P * P)
         cmodel.mig_rates = _dp(owner._mig)
@@ -332,6 +341,7 @@ RUN_PATHS = ("General", "TwoLaunch", "KPipe", "Sweep", "SweepSplit", "SweepXmp",
 # pf_get_row_form (PF_ROW_FORM_*)
 ROW_FORMS = (None, "single", "paired")
 DEBUG_NO_PAIR = 4096
+MODEL_SAMPLE_TIMES = 8               # pf_model.flags bit 3 (PF_MODEL_SAMPLE_TIMES): set for every model with the key sample_times
 MODEL_WIDE_POPS = 4                  # pf_model.flags bit 2 (PF_MODEL_WIDE_POPS): set for every model of more than four populations
 FLAG_MP_LDS_ROWS = 8                 # pf_params.flags bit 3 (PF_FLAG_MP_LDS_ROWS): ParticleFilter(..., mp_rows=True)
 DEBUG_SIGNAL_ALL_COUNTS = 16384      # a completion signal on every second launch of a split step (A/B)
