@@ -35,7 +35,15 @@
  *   D14 structured models: the walk of the floating lineage compares its budget with differences of per-population
  *      cumulative intensities once per stretch between two changes of the configuration (node, migration event on
  *      the tree, fixed-time move) instead of once per epoch; same distribution (mp_coalesce below)
+ *   D15 sample times: the tree's length is the rank sum minus the sum of the times, added in sample order (tree_length below)
+ *   D16 sample times: the root's lineage that waits alone for the next sample spends its budget epoch by epoch (root_wait below)
  *   (D7-D11, R1, R2: DESIGN.md section 6)
+ *
+ * Sample times (ancient samples, scrm -eI; smco_model.sample_times with flags bit 3): structured models only.  A leaf's height is its
+ * time and it is a lineage only from then on -- node_h, lineages_at / lineages_in_pop, M.Tjoin, the cut-point walk of
+ * genealogy_update, mp_build_initial_tree with root_wait, tree_length and open_stretch carry all of it; with every time zero each of
+ * them is the operation it was.  What pins this part: the Monte Carlo fixture tests/golden/mc_model_ancient.json
+ * (tests/test_oracle_ancient_cpu.py); DESIGN.md section 6 "Sample times in the oracle".
  */
 #include "smc_oracle.h"
 #include "smc_math.h"
@@ -165,6 +173,17 @@ struct Model {
     std::vector<double> Cc, Cm;      /* [E*P]   integrals of inv2Np / Mtot from 0 to the epoch starts (the one-population Hc, per population) */
     std::vector<double> Tjoin;       /* [E]     start of the next epoch after e whose jmap moves a population, +inf if none */
     std::vector<int> sample_pop;     /* [n] */
+    /* ancient samples (-eI): the time at which each sample enters; empty = every sample at time 0.  Each is an epoch start, the
+     * smallest is 0, they ascend with the sample index (fill_model refuses anything else) */
+    std::vector<double> stime;       /* [n] or empty */
+    double leaf_time(int i) const { return stime.empty() ? 0.0 : stime[i]; }
+    /* number of samples that have entered by time t */
+    int entered(double t) const {
+        if (stime.empty()) return n;
+        int c = 0;
+        for (int i = 0; i < n; ++i) c += stime[i] <= t;
+        return c;
+    }
     /* variational-Bayes weight factors exp_digamma(c)/c per event (particle.cpp:266-272); empty = off */
     std::vector<double> vb_coal;     /* [E*P] */
     std::vector<double> vb_mig;      /* [E*P*P] */
@@ -366,14 +385,25 @@ struct Filter {
     }
 
     /* ---------------- tree helpers ---------------- */
-    inline double node_h(const Tree& t, int id) const { return id < M.n ? 0.0 : t.S[id - M.n]; }
+    /* a leaf's height is the time at which its sample enters (0 without sample times) */
+    inline double node_h(const Tree& t, int id) const { return id < M.n ? M.leaf_time(id) : t.S[id - M.n]; }
+    /* the lineage above node `id` can be met at `time` as far as its lower end goes: a sample is a lineage only from its time on */
+    inline bool entered_by(int id, double time) const { return id >= M.n || M.leaf_time(id) <= time; }
 
-    /* local tree length by time slices: sum_r (n-r) * (S[r]-S[r-1])   (Forest::getLocalTreeLength) */
+    /* local tree length by time slices: sum_r (n-r) * (S[r]-S[r-1])   (Forest::getLocalTreeLength).
+     * With sample times the branch above sample i starts at its time, so the length is that rank sum minus the sum of the times.
+     * D15 (arithmetic order only): the times are added in sample order and their sum is subtracted once, as the device does
+     * (tree_length in pf_device.h with Lane::STsum), instead of one subtraction per sample. */
     double tree_length(const Tree& t, int nleaves) const {
         double acc = 0.0, prev = 0.0;
         for (int r = 0; r < nleaves - 1; ++r) {
             acc += (double)(nleaves - r) * (t.S[r] - prev);
             prev = t.S[r];
+        }
+        if (!M.stime.empty()) {
+            double tau = 0.0;
+            for (int i = 0; i < nleaves; ++i) tau += M.stime[i];
+            acc -= tau;
         }
         return acc;
     }
@@ -389,7 +419,7 @@ struct Filter {
         for (int r = R; r < ni; ++r)
             for (int s = 0; s < 2; ++s) {
                 int id = t.C[r][s];
-                if (id < M.n || id - M.n < R) {
+                if ((id < M.n || id - M.n < R) && entered_by(id, time)) {
                     if (cnt == want) { *pr = r; *ps = s; }
                     ++cnt;
                 }
@@ -489,7 +519,7 @@ struct Filter {
         for (int r = R; r < ni; ++r)
             for (int s = 0; s < 2; ++s) {
                 int id = t.C[r][s];
-                if ((id < M.n || id - M.n < R) && pop_at(t, id, time) == pop) {
+                if ((id < M.n || id - M.n < R) && entered_by(id, time) && pop_at(t, id, time) == pop) {
                     if (cnt == want) { *pr = r; *ps = s; }
                     ++cnt;
                 }
@@ -573,9 +603,15 @@ struct Filter {
      * same step D12 takes for one population with Hc.  The budget is compared with that difference once per
      * stretch; in the stretch in which it runs out the epoch of the event is found by comparing the budget with the
      * same difference taken to the epoch starts of the stretch.  The event records are still cut per epoch (one Ev
-     * per epoch of the stretch), as record_all_event makes them. */
+     * per epoch of the stretch), as record_all_event makes them.
+     *
+     * Sample times.  A sample of the tree is a partner only from its time on (lineages_in_pop), and the number of partners changes
+     * where one enters: M.Tjoin holds the entry times next to the epoch starts with a fixed-time move, so a stretch ends there too.
+     * The move of such an epoch start applies to the two active lineages as at any other; a sample that enters there is in its own
+     * population sample_pop as given.  pr_start >= 0: the walk starts above the root (h > its height) after root_wait has taken the
+     * root's lineage up to h -- its population there is pr_start, and its events so far are already in W.rt / W.rq. */
     void mp_coalesce(int64_t slot, Particle* rec_p, const Tree& t, int ni, int root_id, double h, int pf0,
-                     double x, int limit, Walk& W) {
+                     double x, int limit, Walk& W, int pr_start = -1) {
         SlotRng& g = rng[slot];
         const int P = M.P;
         const double Hr = node_h(t, root_id);
@@ -584,8 +620,9 @@ struct Filter {
         int i = 0, j = 0;
         while (i < ni && t.S[i] <= tt) ++i;
         while (j < t.nm && t.Mt[j] <= tt) ++j;
-        int pf = pf0, pr = pop_base(t, root_id);
-        W.npath = W.nrpath = 0;
+        int pf = pf0, pr = pr_start >= 0 ? pr_start : pop_base(t, root_id);
+        W.npath = 0;
+        if (pr_start < 0) W.nrpath = 0;
         W.tfirst = -1.0;
         auto ci = [&](int q, int ee, double tm) { return M.Cc[ee * P + q] + (tm - M.T[ee]) * M.inv2Np[ee * P + q]; };
         auto cm = [&](int q, int ee, double tm) { return M.Cm[ee * P + q] + (tm - M.T[ee]) * M.Mtot[ee * P + q]; };
@@ -722,6 +759,73 @@ struct Filter {
         }
     }
 
+    /* Sample times, first tree: the root's lineage of the partial tree from the root (height t0, population pr) up to t_end > t0,
+     * the time at which the next sample enters (an epoch start).  Nothing else exists in between: the lineage cannot coalesce, it
+     * migrates at the total rate of its population and takes the fixed-time moves of every epoch start it reaches, t_end's
+     * included (it is there when the move happens; the sample that enters is not moved).  Per event one uniform picks the target,
+     * the next refreshes the unit exponential.  Its events go to W.rt / W.rq (the root's branch, as in mp_coalesce), its records are
+     * those of the root's lineage there: no partners, migration opportunity only; the -vb factor of a migration applies.
+     * Returns the lineage's population at t_end.
+     * D16 (arithmetic order only): the budget is spent epoch by epoch as rate x length, not against a difference of Cm, and the
+     * event is placed by one division from the last point reached -- the order of mp_root_wait on the device. */
+    int root_wait(int64_t slot, Particle* rec_p, double t0, int pr, double t_end, Walk& W) {
+        SlotRng& g = rng[slot];
+        const int P = M.P;
+        auto record = [&](double a, double b, int ea, int to) {       /* to < 0: no event at b */
+            if (!(rec_p && record_events)) return;
+            for (int ee = ea; ee < M.E; ++ee) {
+                double lo = std::max(a, M.T[ee]), hi = std::min(b, M.epoch_end(ee));
+                const bool last = !(M.epoch_end(ee) <= b) || ee + 1 == M.E;       /* an event at an epoch's end counts in the next */
+                if ((M.recflags[ee] & REC_COALMIGR) && (hi > lo || (last && to >= 0))) {
+                    if (hi < lo) hi = lo;
+                    Ev* ev = new_event(*rec_p, ee, 1, lo, hi, 0.0, 0.0, 0);
+                    ev->pop = (int8_t)pr;
+                    if (last && to >= 0) { ev->event = 2; ev->mig_to = (int8_t)to; }
+                }
+                if (last || to < 0) break;
+            }
+        };
+        auto push = [&](double time, int q) {
+            if (W.nrpath >= MMAX) throw std::runtime_error("too many migration events on one local tree");
+            W.rt[W.nrpath] = time; W.rq[W.nrpath] = (int8_t)q; ++W.nrpath;
+        };
+        W.nrpath = 0;
+        double tt = t0;
+        int e = M.epoch_of(tt);
+        while (tt < t_end) {
+            const double up = M.epoch_end(e);             /* <= t_end */
+            const double rate = M.Mtot[e * P + pr];
+            const double need = rate * (up - tt);
+            if (g.ebuf > need) {
+                g.ebuf -= need;
+                record(tt, up, e, -1);
+                tt = up;
+                ++e;
+                const int q = M.jmap[e * P + pr];
+                if (q != pr) { push(tt, q); pr = q; }
+                continue;
+            }
+            double t1 = tt + g.ebuf / rate;
+            if (t1 > up) t1 = up;
+            double v = uni(slot) * rate;
+            g.ebuf = -smc_log(uni(slot));
+            int to = -1;
+            for (int q = 0; q < P; ++q) {
+                const double m = M.Mrate[(e * P + pr) * P + q];
+                if (q == pr || m == 0.0) continue;
+                to = q;
+                if (v < m) break;
+                v -= m;
+            }
+            record(tt, t1, e, to);
+            if (rec_p && !M.vb_coal.empty()) upd_fac *= M.vb_mig[(e * P + pr) * P + to];
+            push(t1, to);
+            pr = to;
+            tt = t1;
+        }
+        return pr;
+    }
+
     void mp_build_initial_tree(int64_t slot, Particle& p) {
         const int n = M.n;
         Tree& t = p.tr;
@@ -731,7 +835,12 @@ struct Filter {
             int ni = i - 1;
             Walk W;
             tree_fl_desc = 1u << i; tree_rt_desc = (1u << i) - 1u;
-            mp_coalesce(slot, &p, t, ni, root, 0.0, M.sample_pop[i], 0.0, M.E - 1, W);
+            /* sample i starts where it enters; the samples before it have entered by then (the times ascend).  A root of the partial
+             * tree below that time first waits for it */
+            const double h0 = M.leaf_time(i);
+            int pr0 = -1;
+            if (h0 > node_h(t, root)) pr0 = root_wait(slot, &p, node_h(t, root), pop_base(t, root), h0, W);
+            mp_coalesce(slot, &p, t, ni, root, h0, M.sample_pop[i], 0.0, M.E - 1, W, pr0);
             apply_vb(p);
             double tc = W.tc;
             for (int m = 0; m < W.nrpath; ++m) ev_insert(t, W.rt[m], root, W.rq[m]);
@@ -840,7 +949,10 @@ struct Filter {
     }
 
     /* record_recomb_extension (particle.cpp:305-357): one rectangle per (tree time-slice x epoch)
-     * with weight = number of local contemporaries; opened at x = p.x_mark, closed later (D6). */
+     * with weight = number of local contemporaries; opened at x = p.x_mark, closed later (D6).
+     * With sample times the contemporaries of a rectangle are the lineages present in it: samples entered minus nodes passed.  A
+     * sample enters at an epoch start and the rectangles are cut there anyway, so k is constant inside each.  (The device subtracts
+     * the length that does not exist from the whole tree's instead, k_count_anc; the two sums agree to rounding.) */
     void open_stretch(Particle& p, double x, int limit) {
         p.x_mark = x;
         p.mark_limit = limit;
@@ -849,11 +961,11 @@ struct Filter {
         double prev = 0.0;
         for (int r = 0; r < n - 1; ++r) {
             double top = p.tr.S[r];
-            int k = n - r;
             double t = prev;
             int e = M.epoch_of(t);
             while (t < top) {
                 double t1 = std::min(top, M.epoch_end(e));
+                const int k = M.entered(t) - r;
                 if ((M.recflags[e] & REC_RECOMB) && e <= limit)
                     p.open.push_back(new_event(p, e, 0, t, t1, x, HUGE_VAL, k));
                 t = t1;
@@ -1063,6 +1175,32 @@ struct Filter {
                 while (idx + 1 < nbands && M.bias_H[idx + 1] < h) ++idx;
                 double recomb_density = M.bias_S[idx] / Lrw;
                 last_rbiw = target / recomb_density;
+            }
+        } else if (!M.stime.empty()) {
+            /* sample times: the point is uniform on the length that exists.  The intervals of the walk below are cut at the
+             * times at which samples enter as well as at the nodes, and an interval starting at `prev` carries the lineages
+             * present there: samples entered minus nodes passed. */
+            double r = uni(slot) * p.Ltree;
+            int ri = 0;                                           /* nodes passed */
+            for (;;) {
+                double top = t.S[ri];                             /* the interval ends at the next node ... */
+                bool at_node = true;
+                for (int i = 0; i < n; ++i)                       /* ... unless a sample enters before it */
+                    if (M.stime[i] > prev && M.stime[i] < top) { top = M.stime[i]; at_node = false; }
+                const int k = M.entered(prev) - ri;
+                const double d = top - prev;
+                const double seg = (double)k * d;
+                if (r < seg || (at_node && ri == n - 2)) {
+                    double q = r / d;
+                    lin = std::min((int)q, k - 1);
+                    h = prev + (q - (double)lin) * d;
+                    if (!(h < top)) h = prev;
+                    slice = ri;
+                    break;
+                }
+                r -= seg;
+                prev = top;
+                if (at_node) ++ri;
             }
         } else if (!M.biased) {
             double r = uni(slot) * p.Ltree;
@@ -1965,10 +2103,29 @@ static void fill_model(Model& M, const smco_model* m) {
             M.Cc[(e + 1) * P + a] = M.Cc[e * P + a] + dt * M.inv2Np[e * P + a];
             M.Cm[(e + 1) * P + a] = M.Cm[e * P + a] + dt * M.Mtot[e * P + a];
         }
+    /* ancient samples: read only with flags bit 3; what the device path refuses is refused here (pf_create) */
+    M.stime.clear();
+    if (m->flags & 8) {
+        if (!m->sample_times) throw std::runtime_error("oracle: flags bit 3 is set but sample_times is null");
+        if (P < 2) throw std::runtime_error("oracle: sample times (-eI, ancient samples) need a structured model (one population is not restated)");
+        M.stime.assign(m->sample_times, m->sample_times + M.n);
+        for (int i = 0; i < M.n; ++i) {
+            bool found = false;
+            for (int e = 0; e < E; ++e) found |= M.T[e] == M.stime[i];
+            if (!found)
+                throw std::runtime_error("oracle: sample time " + std::to_string(M.stime[i]) + " of sample " + std::to_string(i) +
+                                         " is not an entry of change_times (a sample enters at the start of an epoch)");
+            if (i && M.stime[i] < M.stime[i - 1]) throw std::runtime_error("oracle: sample times must ascend with the sample index");
+        }
+        if (M.stime[0] != 0.0) throw std::runtime_error("oracle: the smallest sample time must be 0");
+    }
+    /* where a stretch of the walk must end whatever the tree: the epoch starts with a fixed-time move, and those at which a sample
+     * enters (the number of partners changes there) */
     M.Tjoin.assign(E, HUGE_VAL);
     for (int e = E - 2; e >= 0; --e) {
         bool moves = false;
         for (int a = 0; a < P; ++a) moves |= M.jmap[(e + 1) * P + a] != a;
+        for (double tau : M.stime) moves |= tau > 0.0 && tau == M.T[e + 1];
         M.Tjoin[e] = moves ? M.T[e + 1] : M.Tjoin[e + 1];
     }
     if (m->vb_coal_counts) {
@@ -1988,6 +2145,10 @@ void* smco_create(const smco_model* m, const smco_params* p) {
         Filter* f = new Filter();
         Model& M = f->M;
         fill_model(M, m);
+        if (!M.stime.empty() && m->n_bias_heights > 0)
+            throw std::runtime_error("oracle: focused sampling (bias_heights) is not supported with sample times (-eI, ancient samples)");
+        if (!M.stime.empty() && m->n_rate_segments > 0)
+            throw std::runtime_error("oracle: a recombination guide is not supported with sample times (-eI, ancient samples)");
         if (p->mig_cap > MMAX) throw std::runtime_error("oracle: mig_cap above the storage of the restatement");
         if (p->mig_cap > 0) f->mig_cap = p->mig_cap;
         if (p->delay_cap > 0) f->delay_cap = p->delay_cap;
@@ -2035,6 +2196,7 @@ int smco_load_lookahead(void* h, const smco_lookahead* la) {
         const int n = f->M.n;
         const int64_t S = la->n;
         if (n > NMAX_NARROW) throw std::runtime_error("oracle: the look-ahead (-apf) takes nsam <= 16");
+        if (!f->M.stime.empty()) throw std::runtime_error("oracle: the look-ahead (-apf) is not supported with sample times (-eI, ancient samples)");
         if (la->level < 0 || la->level > 4) throw std::runtime_error("-apf must be 0..4");
         f->apf = la->level; f->la_D = la->max_doubletons; f->la_Q = la->n_quantiles;
         f->la_fsd.assign(la->first_singleton_distance, la->first_singleton_distance + S * n);
@@ -2055,6 +2217,8 @@ int smco_load_lookahead(void* h, const smco_lookahead* la) {
 int smco_terminal_branch_quantiles(const smco_model* m, uint64_t seed, int64_t n_trees, const double* quantiles, int32_t nq,
                                    double* lengths_out, double* mean_total_out) {
     GUARD(
+        if (m->flags & 8)
+            throw std::runtime_error("oracle: terminal branch quantiles are not supported with sample times (-eI, ancient samples)");
         Filter f;
         fill_model(f.M, m);
         f.M.recflags.assign(f.M.E, 3);
@@ -2192,6 +2356,7 @@ int smco_enable_tree_recording(void* h) {
     GUARD(
         Filter* f = (Filter*)h;
         if (f->M.n > NMAX_NARROW) throw std::runtime_error("oracle: tree recording (-arg) takes nsam <= 16");
+        if (!f->M.stime.empty()) throw std::runtime_error("oracle: tree recording (-arg) is not supported with sample times (-eI, ancient samples)");
         f->record_trees = true;
     )
 }

@@ -16,6 +16,8 @@
  *     transcribed from test/old/newtests by tests/golden/make_reference_bands.py): the no-data classes are
  *     asserted on this oracle in tests/test_oracle_cpu.py, all of them through the GPU path in
  *     tests/test_gpu_reference_bands.py; DESIGN.md section 6 has the pass/fail table.
+ * Sample times (ancient samples, smco_model.sample_times) are pinned by the independent Monte Carlo statement of that model,
+ * tests/mc_model_ancient.py, through tests/golden/mc_model_ancient.json (tests/test_oracle_ancient_cpu.py).
  *
  * The struct layouts below are deliberately identical to include/smcsmc_pf.h so the
  * parity tests can feed both sides the same buffers.
@@ -33,7 +35,8 @@ typedef struct smco_model {
     int32_t n_pops;              /* P (1..8) */
     int32_t nsam;                /* number of haplotypes n: 2..64 with one population, 2..16 with several populations, with tree
                                   * recording and with the look-ahead (the limits of the device path; the calls say which) */
-    int32_t flags;               /* bit0 ancestral_aware, bit1 dephase */
+    int32_t flags;               /* bit0 ancestral_aware, bit1 dephase, bit3 (8) sample_times below is given; bit2 (more than four
+                                  * populations on the device path) means nothing here */
     double loci_length;          /* L, bp */
     double mutation_rate;        /* per bp per generation */
     double recombination_rate;   /* per bp per generation */
@@ -62,6 +65,11 @@ typedef struct smco_model {
     const double* rate_positions;     /* [K] segment starts (0-based, first = 0, no gaps) */
     const double* rate_values;        /* [K] sampling recombination rate per bp per generation */
     const double* leaf_rel_rates;     /* [K*nsam] relative rate of every sample's lineage */
+    /* ancient samples (scrm -eI): sample i enters at sample_times[i] generations in sample_pops[i]; below that time its lineage does
+     * not exist.  Read only with flags bit 3, the position and meaning of pf_model.sample_times / PF_MODEL_SAMPLE_TIMES.  Every
+     * time is an entry of change_times, the smallest is 0 and the times ascend with the sample index; structured models only,
+     * without tree recording, look-ahead, focused sampling and guide (smco_create and the calls below say so). */
+    const double* sample_times;       /* [nsam] */
 } smco_model;
 
 typedef struct smco_params {
@@ -125,7 +133,7 @@ void smco_destroy(void* h);
 const char* smco_last_error(void);
 
 int smco_load_lookahead(void* h, const smco_lookahead* la);            /* switches the auxiliary particle filter on */
-/* calculate_terminal_branch_length_quantiles (smcsmc.cpp:128-166) over n_trees prior trees (Philox stream 3) */
+/* calculate_terminal_branch_length_quantiles (smcsmc.cpp:128-166) over n_trees prior trees (Philox stream 3); refuses sample times */
 int smco_terminal_branch_quantiles(const smco_model* m, uint64_t seed, int64_t n_trees, const double* quantiles, int32_t nq,
                                    double* lengths_out, double* mean_total_out);
 int smco_init_prior(void* h, double initial_position);               /* particleContainer.cpp:33-65 */

@@ -29,7 +29,11 @@ class Model(C.Structure):
         ("n_rate_segments", C.c_int32), ("reserved2", C.c_int32),
         ("rate_positions", C.POINTER(C.c_double)), ("rate_values", C.POINTER(C.c_double)),
         ("leaf_rel_rates", C.POINTER(C.c_double)),
+        ("sample_times", C.POINTER(C.c_double)),      # read by the oracle only with MODEL_SAMPLE_TIMES in flags
     ]
+
+
+MODEL_SAMPLE_TIMES = 8      # smco_model.flags bit 3, as pf_model's PF_MODEL_SAMPLE_TIMES: set for every model with the key sample_times
 
 
 class Params(C.Structure):
@@ -120,7 +124,13 @@ def attach_bias(owner, cmodel, m):
 
 
 def attach_structure(owner, cmodel, m, E, P):
-    """Per-epoch migration matrix [E][P][P], fixed-time moves [E][P][P] and the samples' populations."""
+    """Per-epoch migration matrix [E][P][P], fixed-time moves [E][P][P], the samples' populations and (ancient samples, model key
+    sample_times) the generations at which the samples enter."""
+    if m.get("sample_times") is not None:
+        owner._stimes = np.ascontiguousarray(m["sample_times"], dtype=np.float64)
+        assert len(owner._stimes) == cmodel.nsam
+        cmodel.sample_times = _dp(owner._stimes)
+        cmodel.flags |= MODEL_SAMPLE_TIMES
     if m.get("mig_rates") is not None:
         owner._mig = np.ascontiguousarray(m["mig_rates"], dtype=np.float64).reshape(E * P * P)
         cmodel.mig_rates = _dp(owner._mig)

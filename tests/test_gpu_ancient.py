@@ -3,8 +3,12 @@ of k_init_mp / k_extend_mp / k_calibrate_mp for sample times (PW + PF_ANC, pf_mp
 
   * target: the filter against tests/golden/mc_model_ancient.json, the brute-force Monte Carlo statement of the model in
     tests/mc_model_ancient.py, under the rules of tests/mc_model_check.py (combine / verdict, unchanged);
-  * all times zero: the model without times, bit for bit (the oracle has no sample times: it runs the model without);
+  * all times zero: the oracle's run of the model without times, bit for bit;
   * no internal node at or below an ancient leaf under it; the prior's rates from a run without data; the binary with -eI.
+
+With a time above zero the device is held to the oracle bit for bit in tests/test_gpu_ancient_parity.py (the oracle takes sample times
+since then; tests/test_oracle_ancient_cpu.py holds it to the same fixture and to the checks of this file, on the CPU).  The tests here
+judge the device on its own, against the model and not against the oracle, and stay as they are.
 """
 import functools
 import json
