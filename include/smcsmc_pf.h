@@ -169,7 +169,10 @@ typedef struct pf_segments {
     const double* start;             /* [n] relative to -startpos (segdata.cpp:200-209) */
     const double* length;            /* [n] */
     const int8_t* state;             /* [n] 0 INVARIANT, 1 MISSING, 2 INVARIANT_PARTIAL */
-    const int8_t* alleles;           /* [n*nsam] -1 . , 0, 1, 2 / */
+    const int8_t* alleles;           /* [n*nsam] -1 . , 0, 1, 2 / .  A 2 marks an unphased heterozygous pair and stands on both samples
+                                        (2k, 2k + 1) of it: pf_load_segments refuses a row with a 2 on one sample of a pair only ("Found
+                                        inconsistent unphased heterozygous marks") and any other value ("Unknown character ..."), in one
+                                        host pass before the upload; the handle is left as it was */
     const int32_t* max_record_epoch; /* [n] max_epoch_to_update (smcsmc.cpp:266-275) */
 } pf_segments;
 

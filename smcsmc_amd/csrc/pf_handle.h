@@ -351,6 +351,15 @@ int pf_init_prior(pf_handle* h, double initial_position) {
 int pf_load_segments(pf_handle* h, const pf_segments* sg) {
     HIPCHK(hipSetDevice(h->device));
     const long long S = sg->n;
+    // what the .seg readers refuse, refused here too for callers that bring their own rows: an allele outside -1..2, and an unphased mark on
+    // one sample only of a pair (2k, 2k + 1) -- the kernels' forms of the phasing test differ on such a row
+    for (long long s = 0; s < S; ++s) {
+        const int8_t* a = sg->alleles + (size_t)s * h->n;
+        for (int i = 0; i < h->n; ++i)
+            if (a[i] < -1 || a[i] > 2) { g_err = "Unknown character found in .seg file; expect one of '.', '/', '0' or '1'."; return -1; }
+        for (int i = 0; i + 1 < h->n; i += 2)
+            if ((a[i] == 2) != (a[i + 1] == 2)) { g_err = "Found inconsistent unphased heterozygous marks"; return -1; }
+    }
     double *ds, *dl; int8_t *dst, *dal; int* dlim;
     int rc = 0;
     rc |= h->alloc(&ds, S); rc |= h->alloc(&dl, S); rc |= h->alloc(&dst, S);

@@ -12,8 +12,9 @@ One-population data come from smcsmc_amd.simulate.simulate_seg, structured data 
 mutations; none from the device.  tests/test_mc_model_cpu.py (oracle) and tests/test_gpu_mc_model.py (device) hold the
 filter to these numbers.
 
-Case 6 of the plan (an all-missing block and an unphased pair) is not generated: the emission of partially missing rows
-(the tracked branch length) is not stated in tests/mc_model.py.
+Unphased pairs and the flags dephase and ancestral_aware are stated in tests/mc_model.py and have a fixture of their own
+(make_mc_model_emission.py, on the rows stored here).  The emission of partially missing rows (the tracked branch length) is
+still not stated there, so no case has one.
 """
 import argparse
 import json

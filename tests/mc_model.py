@@ -32,8 +32,13 @@ Target (what the filter multiplies into a particle's weight; DESIGN.md section 6
   * a row of state 0 has a site at its end: the pruning likelihood of the tree in force there, two alleles, root prior
     1/2, 1/2, no change along a branch of length b with probability fastexp(-mu b), the other allele otherwise; a missing
     leaf has likelihood 1 for both alleles (so an all-missing row contributes 1);
-  * rows in which only some samples are missing and unphased pairs are not stated here (case 6 of the issue is left
-    out): run() refuses them.
+  * unphased pairs: a site whose row has the marks (2, 2) at samples (2k, 2k + 1) for k of its pairs weighs the arithmetic
+    mean, over the 2^k assignments (0, 1) / (1, 0) of those pairs, of the pruning likelihood above; a mark anywhere else (one
+    sample of a pair, the unpaired last sample of an odd n) is not data and is refused;
+  * model key dephase: every pair (2k, 2k + 1) whose two alleles are {0, 1} counts as marked, whatever its order;
+  * model key ancestral_aware: the root prior is 1 on allele 0 and 0 on allele 1;
+  * rows in which only some samples are missing are still not stated here (the tracked-branch rule of such rows is not part
+    of this statement): run() refuses them.
   p(data | model) is the prior expectation of the product of these factors.
 
 Sufficient statistics, as functionals of the ancestral recombination graph (all recorded: lags beyond the sequence):
@@ -96,6 +101,8 @@ class Model:
         self.mu = float(m["mutation_rate"])
         self.rho = float(m["recombination_rate"])
         self.L = float(m["loci_length"])
+        self.dephase = bool(m.get("dephase", False))
+        self.root_prior = (1.0, 0.0) if m.get("ancestral_aware", False) else (0.5, 0.5)
         self.nstat = 2 * E + 3 * E * P + E * P * P
 
     def epoch_of(self, t):
@@ -391,6 +398,21 @@ class ARG:
 
     # ---- emission
     def site_likelihood(self, alleles):
+        """the weight of a site: the pruning likelihood, or its mean over the phasings of the marked pairs"""
+        m = self.m
+        pairs = [i for i in range(0, m.n - 1, 2)
+                 if alleles[i] == 2 or (m.dephase and alleles[i] + alleles[i + 1] == 1 and alleles[i] * alleles[i + 1] == 0)]
+        if not pairs:
+            return self.pruning_likelihood(alleles)
+        a = list(alleles)
+        total = 0.0
+        for bits in range(1 << len(pairs)):
+            for k, i in enumerate(pairs):
+                a[i], a[i + 1] = (1, 0) if (bits >> k) & 1 else (0, 1)
+            total += self.pruning_likelihood(a)
+        return total / (1 << len(pairs))
+
+    def pruning_likelihood(self, alleles):
         m = self.m
         mu = m.mu
 
@@ -406,7 +428,7 @@ class ARG:
                 l1 *= c1 * p + c0 * (1 - p)
             return l0, l1
         r0, r1 = up(self.root)
-        return 0.5 * r0 + 0.5 * r1
+        return m.root_prior[0] * r0 + m.root_prior[1] * r1
 
     def leaves_below(self, v):
         if v < self.m.n:
@@ -423,8 +445,11 @@ def prepare_rows(model, rows):
     out = []
     for s in range(len(start)):
         miss = int((al[s] < 0).sum())
-        if miss not in (0, model.n) or (al[s] == 2).any():
-            raise ValueError("rows with some samples missing or unphased pairs are not stated in this model")
+        if miss not in (0, model.n):
+            raise ValueError("rows with some samples missing are not stated in this model")
+        marked = al[s] == 2
+        if (marked[0:model.n - 1:2] != marked[1:model.n:2]).any() or (model.n % 2 == 1 and marked[-1]):
+            raise ValueError("an unphased mark stands for a pair (2k, 2k + 1): a lone one is not data")
         assert s == 0 or start[s] == start[s - 1] + length[s - 1], "rows must be contiguous"
         end = min(start[s] + length[s], model.L)
         site = [int(a) for a in al[s]] if int(rows["state"][s]) == 0 and miss == 0 else None

@@ -266,6 +266,46 @@ def test_binary_end_to_end_matches_library_and_front_end_contract(oracle, hiplib
     assert d[(("Delay", -1, -1, -1, -1), "Count")] > 0
 
 
+def test_binary_end_to_end_with_dephase_and_ancestral_aware(hiplib, tmp_path):
+    """-dephase -ancestral_aware from the command line to the kernels: on four haplotypes of the project's simulator the binary's .out equals,
+    character for character, the table of the same run through ParticleFilter with both flags in the model, and differs from the run without."""
+    import json
+    import os
+    import subprocess
+    from smcsmc_amd import ParticleFilter, outfile, segments as segmod, simulate
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    binary = os.path.join(root, "bin", "smcsmc")
+    if not os.path.exists(binary):
+        from smcsmc_amd import build
+        build.build_all()
+    L, n = 100000, 4
+    base = cases.make_model(n=n, E=3, L=L)
+    seg = str(tmp_path / "four.seg")
+    simulate.write_seg(seg, simulate.simulate_seg(n, L, 2.5e-8, 1e-8, base["change_times"], base["pop_sizes"], seed=12))
+    core = ("-N0 10000 -t %g -r %g %d -eN 0 1 -eN 0.1 1 -eN 0.5 1" % (4e4 * 2.5e-8 * L, 4e4 * 1e-8 * L, L)).split()
+    common = ["-nsam", str(n), "-Np", "300", "-EM", "0", "-tmax", "4", "-lag", "50000", "-seed", "5", "-seg", seg]
+    text = {}
+    for name, extra in (("flags", ["-dephase", "-ancestral_aware"]), ("plain", [])):
+        r = subprocess.run([binary] + core + common + extra + ["-o", str(tmp_path / name)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        text[name] = open(tmp_path / (name + ".out")).read()
+    assert text["flags"] != text["plain"]
+    m = json.loads(subprocess.run([binary] + core + ["-nsam", str(n), "-tmax", "4", "-dumpmodel"], capture_output=True, text=True).stdout)
+    E = len(m["change_times"])
+    model = dict(change_times=np.array(m["change_times"]), pop_sizes=np.array(m["pop_sizes"])[:, 0], lags=np.full(E, 50000.0),
+                 nsam=n, loci_length=float(L), mutation_rate=m["mutation_rate"], recombination_rate=m["recombination_rate"])
+    segs = segmod.Segments(seg, n, L, max_segment_length=int(2.0 / (m["recombination_rate"] * 4 * m["N0"]))).pack(model["lags"])
+    al = np.asarray(segs["alleles"]).reshape(-1, n)
+    assert ((al[:, 0::2] + al[:, 1::2] == 1) & (al[:, 0::2] >= 0) & (al[:, 1::2] >= 0)).any(), "a heterozygous pair for -dephase to unphase"
+    for name, flags in (("flags", dict(dephase=True, ancestral_aware=True)), ("plain", dict())):
+        g = ParticleFilter(dict(model, **flags), 300, seed=5, max_trace_events=0)
+        try:
+            g.init_prior(segs["start"][0]); g.load_segments(segs); g.run(); g.finish()
+            assert outfile.outfile_text(model, g.counts(), 300) == text[name], name
+        finally:
+            g.close()
+
+
 @pytest.mark.parametrize("n,delay_type", [(4, 0), (2, 1), (6, 0), (12, 0), (10, 1), (4, 4), (12, 5)])   # + 4: every factor delayed
 def test_focused_sampling_and_delayed_importance_weights(oracle, hiplib, n, delay_type):
     """-bias_heights / -bias_strengths with delayed application of the importance weights

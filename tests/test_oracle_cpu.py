@@ -430,3 +430,42 @@ def test_delayed_factor_store_capacity(oracle):
     assert o2.logl() != logl            # early application changes the pilot weights, hence the resampling, hence everything
     with pytest.raises(RuntimeError, match="delayed-factor store overflow"):
         run(delay_cap=max(2, st["peak"] // 3))
+
+
+@pytest.mark.parametrize("shape", ["4", "7", "4-2"])
+def test_dephase_on_phased_rows_is_no_flag_on_marked_rows(oracle, shape):
+    """With dephase a phased heterozygous pair is treated exactly as a marked one (particleContainer.cpp:149: same first phasing (0, 1),
+    same order of summation), so dephase on phased rows equals, bit for bit, no flag on the same rows with every such pair rewritten as
+    (2, 2): n = 4, n = 7 (sample 6 has no partner) and n = 4 in two populations.  It fails if the enumeration starts at the data's phase,
+    and it asks nothing of the device (tests/test_gpu_emission_flags.py holds the same identity there)."""
+    import emission_cases as ec
+    a, b = ec.identity_oracle(shape, False), ec.identity_oracle(shape, True)
+    bits = lambda x: np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)     # noqa: E731
+    assert a["trace"]["resampled"].sum() > 0
+    assert a["logl"] != ec.oracle_run(shape, None)["logl"]
+    assert bits([a["logl"]])[0] == bits([b["logl"]])[0]
+    assert (a["trace"]["resampled"] == b["trace"]["resampled"]).all()
+    for k in ("T", "ess", "logl"):
+        assert (bits(a["trace"][k]) == bits(b["trace"][k])).all(), k
+    assert (a["events"][0] == b["events"][0]).all() and (a["events"][1] == b["events"][1]).all()
+    assert (a["particles"]["children"] == b["particles"]["children"]).all()
+    for k in ("heights", "w_post", "w_pilot", "next_base"):
+        assert (bits(a["particles"][k]) == bits(b["particles"][k])).all(), k
+    for k in a["counts"]:
+        assert (bits(a["counts"][k]) == bits(b["counts"][k])).all(), k
+    if "migrations" in a:
+        for k in ("n_events", "node_pops", "branch", "newpop"):
+            assert (a["migrations"][k] == b["migrations"][k]).all(), k
+        assert (bits(a["migrations"]["times"]) == bits(b["migrations"]["times"])).all()
+
+
+def test_emission_flag_cases_hold_what_they_are_for(oracle):
+    """tests/emission_cases.py on the CPU: the data of every shape contain the rows the cases are about (asserted in rows()), every run
+    resamples, and each flag setting moves the oracle's log-likelihood"""
+    import emission_cases as ec
+    for shape in ec.SHAPES:
+        ec.rows(shape)
+        la = ec.APF_LEVEL if shape == "8-apf" else 0
+        ll = {f: ec.oracle_run(shape, f, la) for f in [None] + list(ec.FLAGS)}
+        assert all(r["trace"]["resampled"].sum() > 0 for r in ll.values()), shape
+        assert len({r["logl"] for r in ll.values()}) == 4, (shape, {f: r["logl"] for f, r in ll.items()})
