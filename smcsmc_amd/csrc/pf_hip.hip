@@ -32,6 +32,7 @@
 #include "pf_lane.h"
 #include "pf_tree_reg.h"
 #include "pf_look_reg.h"
+#include "pf_row_parts.h"
 #include "pf_lds_body.h"
 #include "pf_mp_host.h"
 #include "pf_wide_host.h"
@@ -190,89 +191,7 @@ __device__ __forceinline__ void row_close_record(double* rec, double x_mark, dou
     rec[2] = 0.0; rec[3] = 0.0;
     rec[4] = __longlong_as_double((long long)make_meta(1, mark_limit, -1, n));
 }
-// the alleles of a row as masks over the haplotypes
-struct RowMasks { unsigned one = 0, zero = 0, present = 0, two = 0; int missing = 0; };
-template <int NM, class F>
-__device__ __forceinline__ RowMasks row_masks(int n, F&& allele) {
-    RowMasks m;
-#pragma unroll
-    for (int i = 0; i < NM; ++i) if (i < n) {
-        int d = allele(i);
-        m.missing += d == -1;
-        if (d == 1) m.one |= 1u << i;
-        if (d == 0) m.zero |= 1u << i;
-        if (d == 2) m.two |= 1u << i;
-        if (d >= 0) m.present |= 1u << i;
-    }
-    return m;
-}
-// the likelihood of a row's site under the tree, averaged over the phasings of its unphased pairs
-template <int NM>
-__device__ __forceinline__ double row_site_lik(const RTree<NM>& t, int n, double v_mu, unsigned one_mask, unsigned zero_mask, unsigned two_mask, bool dephase, bool anc) {
-    unsigned het_pairs = 0;
-    int ncfg = 1;
-    for (int i = 0; i + 1 < n; i += 2) {
-        bool d0_two = (two_mask >> i) & 1u;
-        bool one0 = (one_mask >> i) & 1u, one1 = (one_mask >> (i + 1)) & 1u;
-        bool zero0 = (zero_mask >> i) & 1u, zero1 = (zero_mask >> (i + 1)) & 1u;
-        bool het = d0_two || (dephase && ((one0 && zero1) || (zero0 && one1)));
-        if (het) {
-            ncfg *= 2;
-            het_pairs |= 1u << i;
-            one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
-            zero_mask |= 1u << i;
-            one_mask |= 1u << (i + 1);
-        }
-    }
-    double norm = 1.0 / (double)ncfg;
-    RBranchP<NM> bprob;
-    r_site_branch_probs(t, n, v_mu, bprob);     // once per row: the phasing configurations share them
-    double lik = 0;
-    for (;;) {
-        lik += r_site_lik_from(t, n, bprob, one_mask, zero_mask, anc);
-        if (ncfg == 1) break;
-        bool more = false;
-        for (int i = 0; i + 1 < n; i += 2) {
-            if (!((het_pairs >> i) & 1)) continue;
-            if ((zero_mask >> i) & 1) {
-                zero_mask &= ~(1u << i); one_mask |= 1u << i;
-                one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
-                more = true;
-                break;
-            }
-            one_mask &= ~(1u << i); zero_mask |= 1u << i;
-            zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
-        }
-        if (!more) break;
-    }
-    lik *= norm;
-    return lik;
-}
-// the five wavefront primitives behind the final weights of a row (the whole wavefront calls this), and where the row pipeline leaves them
-struct RowScans { double sc, sp, sq, scp, scm; };
-__device__ __forceinline__ RowScans row_scans(double w_post, double w_pilot, int lane) {
-    RowScans r;
-    r.sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
-    r.sp = wave_tree_sum(w_post);
-    r.sq = wave_tree_sum(w_pilot * w_pilot);
-    r.scp = wave_hs_scan(w_post, lane);
-    r.scm = wave_max_scan_d(r.sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
-    return r;
-}
-template <class KA>
-__device__ __forceinline__ void row_scans_store(const KA& A2, int cur, long long p, bool active, int lane, const RowScans& r) {
-    const long long chunk = p >> 6;
-    const size_t ro = (size_t)cur * A2.Np, co = (size_t)cur * A2.nc;
-    if (active) { A2.rg_scan1[ro + p] = r.sc; A2.rg_scanp[ro + p] = r.scp; A2.rg_scan1m[ro + p] = r.scm; }
-    if (p == A2.Np - 1) A2.ctrl->last1[cur] = r.sc;
-    if (lane == 63 && chunk < A2.nc) {
-        A2.rg_cpost[co + chunk] = r.sp;
-        A2.rg_csq[co + chunk] = r.sq;
-        A2.rg_cpil[co + chunk] = r.sc;
-        A2.rg_cpp[co + chunk] = r.scp;
-        A2.rg_cmx1[co + chunk] = r.scm;
-    }
-}
+// (RowMasks, row_masks, row_site_lik, RowScans, row_scans, row_scans_store: pf_row_parts.h)
 
 // the head of a row of the headline row kernels, requests only: what the decision on the row before needs and the window of pilot scans
 // that starts at wavefront spec_lo
@@ -402,40 +321,7 @@ __device__ __forceinline__ void row_copy_weights(double& w_post, double& w_pilot
     w_post = wp * adj;
     w_pilot = wq * adj;
 }
-// the stores of a row's end, but for the weights: the tree, ...
-template <int NM>
-__device__ __forceinline__ void row_store_tree(const DState& st1, size_t Np, long long p, int n, const RTree<NM>& t) {
-#pragma unroll
-    for (int r = 0; r < RTree<NM>::NI; ++r)
-        if (r < n - 1) {
-            st1.S[(size_t)r * Np + p] = t.S[r];
-            st1.C[(size_t)(2 * r) * Np + p] = (int8_t)t.C0[r];
-            st1.C[(size_t)(2 * r + 1) * Np + p] = (int8_t)t.C1[r];
-        }
-}
-// ... what the chain carries from row to row, ...
-template <class KA>
-__device__ __forceinline__ void row_store_chain(const KA& A1, const DState& st1, long long p, double next_base, double x_mark, int mark_limit, const RCtx& cx) {
-    st1.next_base[p] = next_base;
-    st1.x_mark[p] = x_mark;
-    st1.mark_limit[p] = mark_limit;
-    st1.Ltree[p] = cx.Ltree;
-    A1.rng_ctr[p] = cx.ctr;
-    A1.ebuf[p] = cx.ebuf;
-}
-// ... and the counters of the row pipeline
-template <class KA>
-__device__ __forceinline__ void row_store_counters(const KA& A1, const PipeRow& PR, int cur, long long p, unsigned long long ctr, unsigned widx, bool do_extend) {
-    if (PR.draws) A1.dt_ctr[(size_t)(PR.draws - 1) * A1.Np + p] = ctr;      // where the next row's draws start
-    A1.rg_widx[(size_t)cur * A1.Np + p] = widx;
-    if (!do_extend) A1.widx[p] = widx;              // the state goes back to the general kernels
-    if (PR.ahead) {
-        // running ahead of the counts: what they check of the ring (records appended as of the row they count) cannot see
-        // this row's writes, so the writer checks them itself against the oldest generation any pending count can ask for
-        const unsigned kold = A1.gstart[(size_t)(A1.ctrl->g_safe % A1.Gcap) * A1.Np + p];
-        if (widx - kold > A1.cap && !A1.ctrl->err) A1.ctrl->err = ERR_LOG_OVERFLOW;
-    }
-}
+// (the stores of a row's end -- row_store_tree, row_store_chain, row_store_counters: pf_row_parts.h)
 // the per-lane context of the update loop, but for the position in the recombination guide
 template <bool BIASED, bool TREES, bool PIPE, class KA>
 __device__ __forceinline__ void row_ctx(RCtx& cx, const KA& A, const double* sT, const double* sI, const double* sH, const double* sBH, const double* sBS, int n, long long p,
@@ -2689,12 +2575,7 @@ __global__ __launch_bounds__(PF_BS) void k_resample(KArgs A, long long s, int nb
         int dc = src.dcount[a];
         dst.dcount[q] = dc;
         dst.total_delayed[q] = src.total_delayed[a];
-        for (int k = 0; k < dc; ++k) {
-            dst.dpos[(size_t)k * Np + q] = src.dpos[(size_t)k * Np + a];
-            dst.dfac[(size_t)k * Np + q] = src.dfac[(size_t)k * Np + a];
-            dst.ddelta[(size_t)k * Np + q] = src.ddelta[(size_t)k * Np + a];
-            dst.dk[(size_t)k * Np + q] = src.dk[(size_t)k * Np + a];
-        }
+        row_copy_pending(dst, src, (size_t)Np, q, a, dc);
     }
     double nb = src.next_base[a];
     if (q != lo[a] && pos < A.L) {

@@ -94,7 +94,9 @@ __host__ __device__ static size_t smem_bytes(int n, int E) {
     return (size_t)3 * (n - 1) * PF_BS * 8 + (size_t)2 * E * 8 + (size_t)(E + (E & 1)) * 4 + (size_t)2 * (n - 1) * PF_BS;
 }
 
-__device__ __forceinline__ void load_model(const KArgs& A, Smem& m) {
+// (the argument block by value, or in the constant address space: the row pipelines)
+template <class KA>
+__device__ __forceinline__ void load_model(const KA& A, Smem& m) {
     for (int e = threadIdx.x; e < A.E; e += blockDim.x) {
         m.T[e] = A.T[e];
         m.I[e] = A.inv2N[e];
@@ -102,7 +104,8 @@ __device__ __forceinline__ void load_model(const KArgs& A, Smem& m) {
     }
 }
 
-__device__ __forceinline__ Lane make_lane(const KArgs& A, Smem& m, long long p) {
+template <class KA>
+__device__ __forceinline__ Lane make_lane(const KA& A, Smem& m, long long p) {
     Lane ln;
     ln.S = m.S + threadIdx.x;
     ln.C = m.C + threadIdx.x;

@@ -8,6 +8,7 @@
 #include "pf_types.h"
 #include "pf_lane.h"
 #include "pf_tree_reg.h"
+#include "pf_row_parts.h"
 
 // ------------------------------------------------------------------ k_init  (particleContainer.cpp:33-65)
 __device__ __forceinline__ void init_lds_body(const KArgs& A, double initial_position, double* smem) {
@@ -92,9 +93,9 @@ __device__ __forceinline__ void init_lds_body(const KArgs& A, double initial_pos
 // ------------------------------------------------------------------ k_extend
 // ParticleContainer::extend_ARGs + update_weight_at_site (particleContainer.cpp:98-135, 187-224)
 // with ForestState::extend_ARG (particle.cpp:743-918) per lane.
-// (extend_lds_pipe_body, pf_lds_pipe.h, repeats the row loop, the delayed-factor store, the site likelihood and the partials of this
-// body statement for statement for the row pipeline -- k_sweep_xl: a change to any of them here is a change there as well;
-// tests/test_gpu_sweep_lds.py compares the two bit for bit)
+// (extend_lds_pipe_body, pf_lds_pipe.h, repeats the skeleton of this body's row loop for the row pipeline -- k_sweep_xl: a change to the
+// loop here is a change there as well, and tests/test_gpu_sweep_lds.py compares the two bit for bit.  What the loop is made of -- the
+// guide's factor, the delayed-factor store, the site likelihood, the stores and the partials -- has one definition, pf_row_parts.h)
 __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, double* smem) {
     Smem m = carve(smem, A.n, A.E);
     load_model(A, m);
@@ -117,11 +118,7 @@ __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, dou
     if (active) {
         const DState st = state_slot(A, cur);
         Lane ln = make_lane(A, m, p);
-        for (int r = 0; r < n - 1; ++r) {
-            LS(ln, r) = st.S[(size_t)r * A.Np + p];
-            LC(ln, r, 0) = st.C[(size_t)(2 * r) * A.Np + p];
-            LC(ln, r, 1) = st.C[(size_t)(2 * r + 1) * A.Np + p];
-        }
+        lane_load_tree(ln, st, (size_t)A.Np, p, n);
         w_post = st.w_post[p];
         w_pilot = st.w_pilot[p];
         double next_base = st.next_base[p];
@@ -143,11 +140,7 @@ __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, dou
         const double seg_end = A.seg_start[s] + A.seg_len[s];
         const double extend_to = seg_end < A.L ? seg_end : A.L;
         const int limit = A.seg_limit[s];
-        int missing = 0;
-        for (int i = 0; i < n; ++i) missing += data[i] == -1;
-        int leaf_status = 0;
-        if (missing == 0) leaf_status = 1;
-        if (missing == n) leaf_status = -1;
+        const int leaf_status = lane_leaf_status(data, n, true);
 
         double updated_to = c->cur_pos;
         double B;
@@ -161,12 +154,7 @@ __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, dou
             w_post *= f;
             w_pilot *= f;
             if (guided) {
-                // importance_weight_over_segment (particle.cpp:1138-1181): true over guide rate for the stretch
-                // without recombination
-                const double dist = new_to - updated_to;
-                const double target_rate = dist * A.rho * ln.Ltree;
-                const double sampled_rate = dist * A.g_rho[ridx] * ln.Ltree;
-                const double iws = fastexp(sampled_rate - target_rate);
+                const double iws = row_guide_stretch(new_to - updated_to, A.rho, A.g_rho[ridx], ln.Ltree);
                 w_post *= iws;
                 w_pilot *= iws;
             }
@@ -205,15 +193,8 @@ __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, dou
                 if (leaf_status == 0) B = tracked_len_lane(ln, data, tmp0);
                 if (leaf_status == 1) B = ln.Ltree;
                 if (biased) {
-                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
-                    const int nbands = A.n_bias + 1;
                     const double delay_height = (A.delay_type & 3) == 0 ? h : tc;
-                    int idx = 0;
-                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
-                    if (idx >= nbands) idx = nbands - 1;
-                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
-                    const double delay = A.app_delays[epoch_of(ln, delay_height)];
-                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+                    row_delayed_factor(ds, sBH, sBS, A.n_bias + 1, A.delay_type, delay_height, iw, rbiw, A.app_delays[epoch_of(ln, delay_height)], updated_to, w_post, w_pilot);
                 }
                 next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
                 ln.uqn = 0;                    // the update's unused uniforms are dropped
@@ -222,101 +203,24 @@ __device__ __forceinline__ void extend_lds_body(const KArgs& A, long long s, dou
             }
         }
 
-        if (biased) {
-            // apply the factors that fell due during this extension (particle.cpp:910-916)
-            for (;;) {
-                if (ds.count == 0) break;
-                double pm = ds.pos[0];
-                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
-                if (!(pm < extend_to)) break;
-                d_apply_earliest(ds, w_pilot);
-            }
-            st.dcount[p] = ds.count;
-            st.total_delayed[p] = ds.total;
-            if (guided) st.ridx[p] = ridx;
-            has_pending = ds.count > 0;
-        }
+        if (biased) has_pending = row_apply_due(ds, st, p, extend_to, true, guided, ridx, w_pilot);
         if (A.seg_state[s] == 0) {
-            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
-            const bool dephase = A.flags & 2;
-            const bool anc = A.flags & 1;
-            pf_mask_t one_mask = 0, zero_mask = 0, het_pairs = 0;
-            int ncfg = 1;
-            for (int i = 0; i < n; ++i) {
-                if (data[i] == 1) one_mask |= (pf_mask_t)1 << i;
-                if (data[i] == 0) zero_mask |= (pf_mask_t)1 << i;
-            }
-            for (int i = 0; i + 1 < n; i += 2) {
-                bool het = (data[i] == 2) || (dephase && data[i] + data[i + 1] == 1);
-                if (het) {
-                    ncfg *= 2;
-                    het_pairs |= (pf_mask_t)1 << i;
-                    one_mask &= ~((pf_mask_t)3 << i); zero_mask &= ~((pf_mask_t)3 << i);
-                    zero_mask |= (pf_mask_t)1 << i;          // hap[i] = 0
-                    one_mask |= (pf_mask_t)1 << (i + 1);     // hap[i+1] = 1
-                }
-            }
-            double norm = 1.0 / (double)ncfg;
-            double lik = 0;
-            for (;;) {
-                lik += site_lik_lane(ln, one_mask, zero_mask, anc, tmp0, tmp1);
-                if (ncfg == 1) break;
-                bool more = false;                  // next_haplotype (pc.cpp:163-181)
-                for (int i = 0; i + 1 < n; i += 2) {
-                    if (!((het_pairs >> i) & 1)) continue;
-                    if ((zero_mask >> i) & 1) {     // phase 0 -> phase 1
-                        zero_mask &= ~((pf_mask_t)1 << i); one_mask |= (pf_mask_t)1 << i;
-                        one_mask &= ~((pf_mask_t)1 << (i + 1)); zero_mask |= (pf_mask_t)1 << (i + 1);
-                        more = true;
-                        break;
-                    }
-                    one_mask &= ~((pf_mask_t)1 << i); zero_mask |= (pf_mask_t)1 << i;
-                    zero_mask &= ~((pf_mask_t)1 << (i + 1)); one_mask |= (pf_mask_t)1 << (i + 1);
-                }
-                if (!more) break;
-            }
-            lik *= norm;
+            const double lik = lane_site_weight(ln, data, n, A.flags & 2, A.flags & 1, tmp0, tmp1);
             w_post *= lik;
             w_pilot *= lik;
         }
 
-        for (int r = 0; r < n - 1; ++r) {
-            st.S[(size_t)r * A.Np + p] = LS(ln, r);
-            st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
-            st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
-        }
+        lane_store_tree(ln, st, (size_t)A.Np, p, n);
         st.w_post[p] = w_post;
         st.w_pilot[p] = w_pilot;
-        st.next_base[p] = next_base;
-        st.x_mark[p] = x_mark;
-        st.mark_limit[p] = mark_limit;
-        st.Ltree[p] = ln.Ltree;
-        A.rng_ctr[p] = ln.ctr;
-        A.ebuf[p] = ln.ebuf;
+        lane_store_chain(A, st, p, next_base, x_mark, mark_limit, ln);
         A.widx[p] = widx;
         if (A.rec_trees && widx >= A.cap) A.ctrl->err = ERR_LOG_OVERFLOW;
         for (int r = 0; r < n - 1; ++r) A.snap_S[A.sp][(size_t)r * A.Np + p] = LS(ln, r);
         A.snap_w[A.sp][p] = w_post; A.snap_xm[A.sp][p] = x_mark; A.snap_ml[A.sp][p] = mark_limit; A.snap_widx[A.sp][p] = widx;
     }
     // per-wavefront canonical partials (level 1 of the radix-64 reduction / scan)
-    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
-    double sp = wave_tree_sum(w_post);
-    double sq = wave_tree_sum(w_pilot * w_pilot);
-    double scp = wave_hs_scan(w_post, lane);
-    double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
-    long long chunk = p >> 6;
-    if (active) { A.scan1[p] = sc; A.scanp2[A.sp][p] = scp; A.scan1m[p] = scm; }
-    if (lane == 63 && chunk < (A.Np + 63) / 64) {
-        A.chunk_post[chunk] = sp;
-        A.chunk_sq[chunk] = sq;
-        A.chunk_pil[chunk] = sc;
-        A.chunk_pp[chunk] = scp;
-        A.chunk_mx1[chunk] = scm;
-    }
-    if (biased) {
-        unsigned long long pend = __ballot(has_pending);
-        if (lane == 0 && chunk < (A.Np + 63) / 64) A.chunk_dpend[chunk] = __popcll(pend);
-    }
+    row_scans_store_general(A, p, active, lane, row_scans(w_post, w_pilot, lane), biased, has_pending);
 }
 
 // ------------------------------------------------------------------ k_calibrate

@@ -3,10 +3,11 @@
 // with the decision on the previous row, the parent search and k_resample's part taken into the prologue, as
 // extend_reg_body<..., PIPE> does for the register tree.  A function of its own: k_extend, k_extend_wide and the calibration
 // and simulation kernels keep the body they had, instruction for instruction.
-// The price is a second copy: from "the row" on, extend_lds_pipe_body repeats extend_lds_body's statements (row loop, delayed-factor
-// store, guide, site likelihood, partials), load_model_k / make_lane_k repeat load_model / make_lane (pf_lane.h), and the prologue
-// follows extend_reg_body<..., PIPE> (pf_hip.hip).  A fix to one of them belongs in both; tests/test_gpu_sweep_lds.py holds the
-// copies together bit for bit.
+// The price is a second copy of the skeleton: from "the row" on, extend_lds_pipe_body repeats extend_lds_body's row loop (the order of
+// its steps, the record of an update, the guide's change of rate), and the prologue follows extend_reg_body<..., PIPE> (pf_hip.hip).  A
+// change to that order belongs in both; tests/test_gpu_sweep_lds.py holds the copies together bit for bit.  What the steps are made of --
+// the guide's factor, the delayed-factor store, the site likelihood, the tree and chain stores, the wavefront partials -- has one
+// definition, in pf_row_parts.h.
 // The prologue (what is requested first, the decision and the parent search), k_resample's part, the log-ring check and the partials are
 // functions of their own (lds_pipe_request, lds_pipe_decide, lds_pipe_complete, pipe_log_ring_check, lds_pipe_partials): the extend role of
 // the structured models from 9 to 16 haplotypes (k_sweep_xlmp, pf_mp_pipe.h, 64 lanes a workgroup) calls the same ones.
@@ -16,31 +17,7 @@
 #include "pf_lane.h"
 #include "pf_pipe.h"
 #include "pf_look_lds.h"
-
-// load_model / make_lane for an argument block in either address space
-template <class KA>
-__device__ __forceinline__ void load_model_k(const KA& A, Smem& m) {
-    for (int e = threadIdx.x; e < A.E; e += blockDim.x) {
-        m.T[e] = A.T[e];
-        m.I[e] = A.inv2N[e];
-        m.RF[e] = A.recflags[e];
-    }
-}
-template <class KA>
-__device__ __forceinline__ Lane make_lane_k(const KA& A, Smem& m, long long p) {
-    Lane ln;
-    ln.S = m.S + threadIdx.x;
-    ln.C = m.C + threadIdx.x;
-    ln.T = m.T; ln.I = m.I; ln.RF = m.RF; ln.H = A.Hc;
-    ln.E = A.E; ln.n = A.n;
-    ln.L = A.L; ln.mu = A.mu; ln.rho = A.rho;
-    ln.seed = A.seed;
-    ln.slot = (unsigned)p;
-    ln.stream = 0;
-    ln.ctr = 0; ln.ebuf = 0; ln.Ltree = 0;
-    ln.vbc = A.vb_coal; ln.upd_fac = 1.0;
-    return ln;
-}
+#include "pf_row_parts.h"
 
 // the decision tables of the prologue lie where the lanes' tree columns (S, t0, t1) go afterwards
 __host__ __device__ inline bool lds_pipe_tables_fit(int n, int nc) { return pipe_lds_doubles(nc) <= (size_t)3 * (n - 1) * PF_BS; }
@@ -283,22 +260,9 @@ template <class KA>
 __device__ __forceinline__ void lds_pipe_partials(const KA& A, const PipeRow& PR, int cur, long long p, bool active, double w_post, double w_pilot,
                                                   bool biased, bool has_pending) {
     const int lane = threadIdx.x & 63;
-    double sc = wave_hs_scan(w_pilot, lane);       // first: its running maximum below is the longest chain of the five
-    double sp = wave_tree_sum(w_post);
-    double sq = wave_tree_sum(w_pilot * w_pilot);
-    double scp = wave_hs_scan(w_post, lane);
-    double scm = wave_max_scan_d(sc, lane);     // running max of the pilot scan (a parallel FP scan need not be monotone)
+    row_scans_store(A, cur, p, active, lane, row_scans(w_post, w_pilot, lane));
     const long long chunk = p >> 6;
-    const size_t ro = (size_t)cur * A.Np, co = (size_t)cur * A.nc;
-    if (active) { A.rg_scan1[ro + p] = sc; A.rg_scanp[ro + p] = scp; A.rg_scan1m[ro + p] = scm; }
-    if (p == A.Np - 1) A.ctrl->last1[cur] = sc;
-    if (lane == 63 && chunk < A.nc) {
-        A.rg_cpost[co + chunk] = sp;
-        A.rg_csq[co + chunk] = sq;
-        A.rg_cpil[co + chunk] = sc;
-        A.rg_cpp[co + chunk] = scp;
-        A.rg_cmx1[co + chunk] = scm;
-    }
+    const size_t co = (size_t)cur * A.nc;
     if (biased) {
         unsigned long long pend = __ballot(has_pending);
         if (lane == 0 && chunk < A.nc) {
@@ -329,7 +293,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
     const double sg_start = R.sg_start, sg_len = R.sg_len;
     const int sg_limit = R.sg_limit, sg_state = R.sg_state;
     const int fs = R.fs;
-    load_model_k(A, m);
+    load_model(A, m);
     if (threadIdx.x < PF_BIAS_MAX + 2) {
         sBH[threadIdx.x] = A.bias_H[threadIdx.x];
         if (threadIdx.x < PF_BIAS_MAX + 1) sBS[threadIdx.x] = A.bias_S[threadIdx.x];
@@ -347,13 +311,9 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
     if (active) {
         const DState st = state_slot(A, cur);
         const DState from = state_slot(A, from_slot);
-        Lane ln = make_lane_k(A, m, p);
+        Lane ln = make_lane(A, m, p);
         // the parent's tree into this lane's columns (its own when the row did not resample)
-        for (int r = 0; r < n - 1; ++r) {
-            LS(ln, r) = from.S[(size_t)r * A.Np + a];
-            LC(ln, r, 0) = from.C[(size_t)(2 * r) * A.Np + a];
-            LC(ln, r, 1) = from.C[(size_t)(2 * r + 1) * A.Np + a];
-        }
+        lane_load_tree(ln, from, (size_t)A.Np, a, n);
         w_post = from.w_post[a];
         w_pilot = from.w_pilot[a];
         double next_base = from.next_base[a];
@@ -371,12 +331,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
         if (biased) {
             ds.count = from.dcount[a]; ds.total = from.total_delayed[a];
             // the copy constructor copies the pending factors (particle.cpp:122-123); the ring moves them every row
-            for (int k = 0; k < ds.count; ++k) {
-                st.dpos[(size_t)k * A.Np + p] = from.dpos[(size_t)k * A.Np + a];
-                st.dfac[(size_t)k * A.Np + p] = from.dfac[(size_t)k * A.Np + a];
-                st.ddelta[(size_t)k * A.Np + p] = from.ddelta[(size_t)k * A.Np + a];
-                st.dk[(size_t)k * A.Np + p] = from.dk[(size_t)k * A.Np + a];
-            }
+            row_copy_pending(st, from, (size_t)A.Np, p, a, ds.count);
         }
         int ridx = guided ? from.ridx[a] : 0;
         double* tmp0 = m.t0 + threadIdx.x;
@@ -389,11 +344,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
         const double seg_end = do_extend ? sg_start + sg_len : 0.0;
         const double extend_to = seg_end < A.L ? seg_end : A.L;
         const int limit = sg_limit;
-        int missing = 0;
-        for (int i = 0; i < n && do_extend; ++i) missing += data[i] == -1;
-        int leaf_status = 0;
-        if (missing == 0) leaf_status = 1;
-        if (missing == n) leaf_status = -1;
+        const int leaf_status = lane_leaf_status(data, n, do_extend);
 
         double updated_to = completing ? pos_prev : c->cur_pos;
         if (!do_extend) updated_to = extend_to;             // completion only: the loop below does not run
@@ -410,12 +361,7 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             w_post *= f;
             w_pilot *= f;
             if (guided) {
-                // importance_weight_over_segment (particle.cpp:1138-1181): true over guide rate for the stretch
-                // without recombination
-                const double dist = new_to - updated_to;
-                const double target_rate = dist * A.rho * ln.Ltree;
-                const double sampled_rate = dist * A.g_rho[ridx] * ln.Ltree;
-                const double iws = fastexp(sampled_rate - target_rate);
+                const double iws = row_guide_stretch(new_to - updated_to, A.rho, A.g_rho[ridx], ln.Ltree);
                 w_post *= iws;
                 w_pilot *= iws;
             }
@@ -447,15 +393,8 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
                 if (leaf_status == 0) B = tracked_len_lane(ln, data, tmp0);
                 if (leaf_status == 1) B = ln.Ltree;
                 if (biased) {
-                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
-                    const int nbands = A.n_bias + 1;
                     const double delay_height = (A.delay_type & 3) == 0 ? h : tc;
-                    int idx = 0;
-                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
-                    if (idx >= nbands) idx = nbands - 1;
-                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
-                    const double delay = A.app_delays[epoch_of(ln, delay_height)];
-                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+                    row_delayed_factor(ds, sBH, sBS, A.n_bias + 1, A.delay_type, delay_height, iw, rbiw, A.app_delays[epoch_of(ln, delay_height)], updated_to, w_post, w_pilot);
                 }
                 next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
                 ln.uqn = 0;                    // the update's unused uniforms are dropped
@@ -464,60 +403,9 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             }
         }
 
-        if (biased) {
-            // apply the factors that fell due during this extension (particle.cpp:910-916)
-            for (;;) {
-                if (ds.count == 0 || !do_extend) break;
-                double pm = ds.pos[0];
-                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
-                if (!(pm < extend_to)) break;
-                d_apply_earliest(ds, w_pilot);
-            }
-            st.dcount[p] = ds.count;
-            st.total_delayed[p] = ds.total;
-            if (guided) st.ridx[p] = ridx;
-            has_pending = ds.count > 0;
-        }
+        if (biased) has_pending = row_apply_due(ds, st, p, extend_to, do_extend, guided, ridx, w_pilot);
         if (do_extend && sg_state == 0) {
-            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
-            const bool dephase = A.flags & 2;
-            const bool anc = A.flags & 1;
-            pf_mask_t one_mask = 0, zero_mask = 0, het_pairs = 0;
-            int ncfg = 1;
-            for (int i = 0; i < n; ++i) {
-                if (data[i] == 1) one_mask |= (pf_mask_t)1 << i;
-                if (data[i] == 0) zero_mask |= (pf_mask_t)1 << i;
-            }
-            for (int i = 0; i + 1 < n; i += 2) {
-                bool het = (data[i] == 2) || (dephase && data[i] + data[i + 1] == 1);
-                if (het) {
-                    ncfg *= 2;
-                    het_pairs |= (pf_mask_t)1 << i;
-                    one_mask &= ~((pf_mask_t)3 << i); zero_mask &= ~((pf_mask_t)3 << i);
-                    zero_mask |= (pf_mask_t)1 << i;          // hap[i] = 0
-                    one_mask |= (pf_mask_t)1 << (i + 1);     // hap[i+1] = 1
-                }
-            }
-            double norm = 1.0 / (double)ncfg;
-            double lik = 0;
-            for (;;) {
-                lik += site_lik_lane(ln, one_mask, zero_mask, anc, tmp0, tmp1);
-                if (ncfg == 1) break;
-                bool more = false;                  // next_haplotype (pc.cpp:163-181)
-                for (int i = 0; i + 1 < n; i += 2) {
-                    if (!((het_pairs >> i) & 1)) continue;
-                    if ((zero_mask >> i) & 1) {     // phase 0 -> phase 1
-                        zero_mask &= ~((pf_mask_t)1 << i); one_mask |= (pf_mask_t)1 << i;
-                        one_mask &= ~((pf_mask_t)1 << (i + 1)); zero_mask |= (pf_mask_t)1 << (i + 1);
-                        more = true;
-                        break;
-                    }
-                    one_mask &= ~((pf_mask_t)1 << i); zero_mask |= (pf_mask_t)1 << i;
-                    zero_mask &= ~((pf_mask_t)1 << (i + 1)); one_mask |= (pf_mask_t)1 << (i + 1);
-                }
-                if (!more) break;
-            }
-            lik *= norm;
+            const double lik = lane_site_weight(ln, data, n, A.flags & 2, A.flags & 1, tmp0, tmp1);
             w_post *= lik;
             w_pilot *= lik;
         }
@@ -534,19 +422,10 @@ __device__ __forceinline__ void extend_lds_pipe_body(const KA& A, long long s, c
             st.lookahead[p] = la_w;          // (the slot the general kernels and the step API read when the call ends here)
         }
 
-        for (int r = 0; r < n - 1; ++r) {
-            st.S[(size_t)r * A.Np + p] = LS(ln, r);
-            st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
-            st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
-        }
+        lane_store_tree(ln, st, (size_t)A.Np, p, n);
         st.w_post[p] = w_post;
         st.w_pilot[p] = w_pilot;
-        st.next_base[p] = next_base;
-        st.x_mark[p] = x_mark;
-        st.mark_limit[p] = mark_limit;
-        st.Ltree[p] = ln.Ltree;
-        A.rng_ctr[p] = ln.ctr;
-        A.ebuf[p] = ln.ebuf;
+        lane_store_chain(A, st, p, next_base, x_mark, mark_limit, ln);
         A.rg_widx[(size_t)cur * A.Np + p] = widx;
         if (!do_extend) A.widx[p] = widx;              // the state goes back to the general kernels
         pipe_log_ring_check(A, p, widx);

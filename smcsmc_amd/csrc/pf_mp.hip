@@ -18,6 +18,7 @@
 #include "pf_look_reg.h"
 #include "pf_mp_host.h"
 #include "pf_pipe.h"
+#include "pf_row_parts.h"
 
 // ------------------------------------------------------------------ structured models (P > 1): LDS-tree kernels
 // Same structure as k_init / k_extend / k_calibrate with the migration-aware genealogy update of pf_mp.h.
@@ -219,12 +220,8 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
         ds.count = 0; ds.total = 1.0;
         if (biased) { ds.count = st.dcount[p]; ds.total = st.total_delayed[p]; }
         int ridx = guided ? st.ridx[p] : 0;
-        for (int r = 0; r < n - 1; ++r) {
-            LS(ln, r) = st.S[(size_t)r * A.Np + p];
-            LC(ln, r, 0) = st.C[(size_t)(2 * r) * A.Np + p];
-            LC(ln, r, 1) = st.C[(size_t)(2 * r + 1) * A.Np + p];
-            LPn(ml, r) = st.Pn[(size_t)r * A.Np + p];
-        }
+        lane_load_tree(ln, st, (size_t)A.Np, p, n);
+        for (int r = 0; r < n - 1; ++r) LPn(ml, r) = st.Pn[(size_t)r * A.Np + p];
         ml.nm = st.nm[p];
         for (int q = 0; q < ml.nm; ++q) {
             LMt(ml, q) = st.Mt[(size_t)q * A.Np + p];
@@ -250,11 +247,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
         const double seg_end = A.seg_start[s] + A.seg_len[s];
         const double extend_to = seg_end < A.L ? seg_end : A.L;
         const int limit = A.seg_limit[s];
-        int missing = 0;
-        for (int i = 0; i < n; ++i) missing += data[i] == -1;
-        int leaf_status = 0;
-        if (missing == 0) leaf_status = 1;
-        if (missing == n) leaf_status = -1;
+        const int leaf_status = lane_leaf_status(data, n, true);
 
         double updated_to = c->cur_pos;
         double B;
@@ -272,11 +265,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
             w_post *= f;
             w_pilot *= f;
             if (guided) {
-                // importance_weight_over_segment (particle.cpp:1138-1181)
-                const double dist = new_to - updated_to;
-                const double target_rate = dist * A.rho * ln.Ltree;
-                const double sampled_rate = dist * A.g_rho[ridx] * ln.Ltree;
-                const double iws = fastexp(sampled_rate - target_rate);
+                const double iws = row_guide_stretch(new_to - updated_to, A.rho, A.g_rho[ridx], ln.Ltree);
                 w_post *= iws;
                 w_pilot *= iws;
             }
@@ -319,15 +308,8 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
                 if (leaf_status == 0) B = tracked_len_lane(ln, data, tmp0);
                 if (leaf_status == 1) B = ln.Ltree;
                 if (biased) {
-                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
-                    const int nbands = A.n_bias + 1;
                     const double delay_height = (A.delay_type & 3) == 0 ? h : ((A.delay_type & 3) == 2 ? tfirst : tc);
-                    int idx = 0;
-                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
-                    if (idx >= nbands) idx = nbands - 1;
-                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
-                    const double delay = A.app_delays[epoch_of(ln, delay_height)];
-                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+                    row_delayed_factor(ds, sBH, sBS, A.n_bias + 1, A.delay_type, delay_height, iw, rbiw, A.app_delays[epoch_of(ln, delay_height)], updated_to, w_post, w_pilot);
                 }
                 next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
                 x_mark = updated_to;
@@ -338,81 +320,21 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
         }
         MP_TICK(tk_loop);
         mp_report(A, ml);
-        if (biased) {
-            // apply the factors that fell due during this extension (particle.cpp:910-916)
-            for (;;) {
-                if (ds.count == 0) break;
-                double pm = ds.pos[0];
-                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
-                if (!(pm < extend_to)) break;
-                d_apply_earliest(ds, w_pilot);
-            }
-            st.dcount[p] = ds.count;
-            st.total_delayed[p] = ds.total;
-            if (guided) st.ridx[p] = ridx;
-            has_pending = ds.count > 0;
-        }
+        if (biased) has_pending = row_apply_due(ds, st, p, extend_to, true, guided, ridx, w_pilot);
 
         if (A.seg_state[s] == 0) {
-            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
-            const bool dephase = A.flags & 2;
-            const bool anc = A.flags & 1;
-            unsigned one_mask = 0, zero_mask = 0, het_pairs = 0;
-            int ncfg = 1;
-            for (int i = 0; i < n; ++i) {
-                if (data[i] == 1) one_mask |= 1u << i;
-                if (data[i] == 0) zero_mask |= 1u << i;
-            }
-            for (int i = 0; i + 1 < n; i += 2) {
-                bool het = (data[i] == 2) || (dephase && data[i] + data[i + 1] == 1);
-                if (het) {
-                    ncfg *= 2;
-                    het_pairs |= 1u << i;
-                    one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
-                    zero_mask |= 1u << i;
-                    one_mask |= 1u << (i + 1);
-                }
-            }
-            double norm = 1.0 / (double)ncfg;
-            double lik = 0;
-            for (;;) {
-                lik += site_lik_lane(ln, one_mask, zero_mask, anc, tmp0, tmp1);
-                if (ncfg == 1) break;
-                bool more = false;
-                for (int i = 0; i + 1 < n; i += 2) {
-                    if (!((het_pairs >> i) & 1)) continue;
-                    if ((zero_mask >> i) & 1) {
-                        zero_mask &= ~(1u << i); one_mask |= 1u << i;
-                        one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
-                        more = true;
-                        break;
-                    }
-                    one_mask &= ~(1u << i); zero_mask |= 1u << i;
-                    zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
-                }
-                if (!more) break;
-            }
-            lik *= norm;
+            const double lik = lane_site_weight(ln, data, n, A.flags & 2, A.flags & 1, tmp0, tmp1);
             w_post *= lik;
             w_pilot *= lik;
         }
         MP_TICK(tk_lik);
         MP_ACC(ml, 10, tk_loop, tk_lik);
 
-        for (int r = 0; r < n - 1; ++r) {
-            st.S[(size_t)r * A.Np + p] = LS(ln, r);
-            st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
-            st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
-        }
+        lane_store_tree(ln, st, (size_t)A.Np, p, n);
         store_mp_state(A, st, ln, ml, p);
         st.w_post[p] = w_post;
         st.w_pilot[p] = w_pilot;
-        st.next_base[p] = next_base;
-        st.x_mark[p] = x_mark;
-        st.mark_limit[p] = mark_limit;
-        st.Ltree[p] = ln.Ltree;
-        A.rng_ctr[p] = ln.ctr;
-        A.ebuf[p] = ln.ebuf;
+        lane_store_chain(A, st, p, next_base, x_mark, mark_limit, ln);
         A.widx[p] = widx;
         A.pidx[p] = pl.idx;
         if (TREES && (widx >= A.cap || pl.idx >= A.pcap)) A.ctrl->err = ERR_LOG_OVERFLOW;       // -arg keeps every record and piece
@@ -426,24 +348,7 @@ __global__ __launch_bounds__(PF_BS) void k_extend_mp(KArgs A, long long s) {
     __syncthreads();
     if (stamp_out && threadIdx.x < PF_STAMP_W) stamp_out[threadIdx.x] = g_mp_acc[threadIdx.x];
 #endif
-    double sp = wave_tree_sum(w_post);
-    double sq = wave_tree_sum(w_pilot * w_pilot);
-    double sc = wave_hs_scan(w_pilot, lane);
-    double scp = wave_hs_scan(w_post, lane);
-    double scm = wave_max_scan_d(sc, lane);
-    long long chunk = p >> 6;
-    if (active) { A.scan1[p] = sc; A.scanp2[A.sp][p] = scp; A.scan1m[p] = scm; }
-    if (lane == 63 && chunk < (A.Np + 63) / 64) {
-        A.chunk_post[chunk] = sp;
-        A.chunk_sq[chunk] = sq;
-        A.chunk_pil[chunk] = sc;
-        A.chunk_pp[chunk] = scp;
-        A.chunk_mx1[chunk] = scm;
-    }
-    if (biased) {
-        unsigned long long pend = __ballot(has_pending);
-        if (lane == 0 && chunk < (A.Np + 63) / 64) A.chunk_dpend[chunk] = __popcll(pend);
-    }
+    row_scans_store_general(A, p, active, lane, row_scans(w_post, w_pilot, lane), biased, has_pending);
 }
 
 // ------------------------------------------------------------------ structured models, LDS tree, on the row pipeline (9 <= n <= 16, PF_FLAG_MP_LDS_ROWS)
@@ -810,13 +715,7 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
         ds.count = 0; ds.total = 1.0;
         if (biased) {
             ds.count = from.dcount[a]; ds.total = from.total_delayed[a];
-            if (gather || PIPE)   // the copy constructor copies the pending factors (particle.cpp:122-123); the ring moves them every row
-                for (int k = 0; k < ds.count; ++k) {
-                    st.dpos[(size_t)k * A.Np + p] = from.dpos[(size_t)k * A.Np + a];
-                    st.dfac[(size_t)k * A.Np + p] = from.dfac[(size_t)k * A.Np + a];
-                    st.ddelta[(size_t)k * A.Np + p] = from.ddelta[(size_t)k * A.Np + a];
-                    st.dk[(size_t)k * A.Np + p] = from.dk[(size_t)k * A.Np + a];
-                }
+            if (gather || PIPE) row_copy_pending(st, from, (size_t)A.Np, p, a, ds.count);     // the ring moves them every row
         }
         w_post = ld_wpost;
         w_pilot = ld_wpilot;
@@ -869,16 +768,10 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
         const double seg_end = do_extend ? A.seg_start[s] + A.seg_len[s] : 0.0;
         const double extend_to = seg_end < A.L ? seg_end : A.L;
         const int limit = do_extend ? A.seg_limit[s] : 0;
-        unsigned one_mask = 0, zero_mask = 0, present_mask = 0, two_mask = 0;
-        int missing = 0;
-        for (int i = 0; i < n && do_extend; ++i) {
-            const int d = data[i];
-            missing += d == -1;
-            if (d == 1) one_mask |= 1u << i;
-            if (d == 0) zero_mask |= 1u << i;
-            if (d == 2) two_mask |= 1u << i;
-            if (d >= 0) present_mask |= 1u << i;
-        }
+        RowMasks rm;
+        if (do_extend) rm = row_masks<NM>(n, [&](int i) { return (int)data[i]; });
+        const unsigned one_mask = rm.one, zero_mask = rm.zero, present_mask = rm.present, two_mask = rm.two;
+        const int missing = rm.missing;
         int leaf_status = 0;
         if (missing == 0) leaf_status = 1;
         if (missing == n) leaf_status = -1;
@@ -904,11 +797,7 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
             w_post *= f;
             w_pilot *= f;
             if (guided) {
-                // importance_weight_over_segment (particle.cpp:1138-1181)
-                const double dist = new_to - updated_to;
-                const double target_rate = dist * A.rho * cx.Ltree;
-                const double sampled_rate = dist * A.g_rho[cx.ridx] * cx.Ltree;
-                const double iws = fastexp(sampled_rate - target_rate);
+                const double iws = row_guide_stretch(new_to - updated_to, A.rho, A.g_rho[cx.ridx], cx.Ltree);
                 w_post *= iws;
                 w_pilot *= iws;
             }
@@ -954,15 +843,8 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
                 if (leaf_status == 0) B = r_tracked_len(t, n, present_mask);
                 if (leaf_status == 1) B = cx.Ltree;
                 if (biased) {
-                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
-                    const int nbands = A.n_bias + 1;
                     const double delay_height = (A.delay_type & 3) == 0 ? h : ((A.delay_type & 3) == 2 ? tfirst : tc);
-                    int idx = 0;
-                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
-                    if (idx >= nbands) idx = nbands - 1;
-                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
-                    const double delay = A.app_delays[r_epoch_of(cx, delay_height)];
-                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+                    row_delayed_factor(ds, sBH, sBS, A.n_bias + 1, A.delay_type, delay_height, iw, rbiw, A.app_delays[r_epoch_of(cx, delay_height)], updated_to, w_post, w_pilot);
                 }
                 next_base = r_sample_next_base<false>(cx, updated_to);
                 x_mark = updated_to;
@@ -973,62 +855,10 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
         }
         MP_TICK(tk_loop);
         if (ml.err && !A.ctrl->err) A.ctrl->err = ml.err == 1 ? ERR_MIG_OVERFLOW : (ml.err == 2 ? ERR_MP_INTERNAL : ERR_NO_COALESCENCE);
-        if (biased) {
-            // apply the factors that fell due during this extension (particle.cpp:910-916)
-            for (;;) {
-                if (ds.count == 0 || !do_extend) break;
-                double pm = ds.pos[0];
-                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
-                if (!(pm < extend_to)) break;
-                d_apply_earliest(ds, w_pilot);
-            }
-            st.dcount[p] = ds.count;
-            st.total_delayed[p] = ds.total;
-            if (guided) st.ridx[p] = cx.ridx;
-            has_pending = ds.count > 0;
-        }
+        if (biased) has_pending = row_apply_due(ds, st, p, extend_to, do_extend, guided, cx.ridx, w_pilot);
 
         if (do_extend && A.seg_state[s] == 0) {
-            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
-            const bool dephase = A.flags & 2;
-            const bool anc = A.flags & 1;
-            unsigned het_pairs = 0;
-            int ncfg = 1;
-            for (int i = 0; i + 1 < n; i += 2) {
-                const bool d0_two = (two_mask >> i) & 1u;
-                const bool one0 = (one_mask >> i) & 1u, one1 = (one_mask >> (i + 1)) & 1u;
-                const bool zero0 = (zero_mask >> i) & 1u, zero1 = (zero_mask >> (i + 1)) & 1u;
-                const bool het = d0_two || (dephase && ((one0 && zero1) || (zero0 && one1)));
-                if (het) {
-                    ncfg *= 2;
-                    het_pairs |= 1u << i;
-                    one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
-                    zero_mask |= 1u << i;
-                    one_mask |= 1u << (i + 1);
-                }
-            }
-            double norm = 1.0 / (double)ncfg;
-            RBranchP<NM> bprob;
-            r_site_branch_probs(t, n, A.mu, bprob);     // once per row: the phasing configurations share them
-            double lik = 0;
-            for (;;) {
-                lik += r_site_lik_from(t, n, bprob, one_mask, zero_mask, anc);
-                if (ncfg == 1) break;
-                bool more = false;
-                for (int i = 0; i + 1 < n; i += 2) {
-                    if (!((het_pairs >> i) & 1)) continue;
-                    if ((zero_mask >> i) & 1) {
-                        zero_mask &= ~(1u << i); one_mask |= 1u << i;
-                        one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
-                        more = true;
-                        break;
-                    }
-                    one_mask &= ~(1u << i); zero_mask |= 1u << i;
-                    zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
-                }
-                if (!more) break;
-            }
-            lik *= norm;
+            const double lik = row_site_lik<NM>(t, n, A.mu, one_mask, zero_mask, two_mask, A.flags & 2, A.flags & 1);
             w_post *= lik;
             w_pilot *= lik;
         }
@@ -1047,12 +877,10 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
         MP_TICK(tk_lik);
         MP_ACC(ml, 10, tk_loop, tk_lik);
 
+        row_store_tree<NM>(st, (size_t)A.Np, p, n, t);
 #pragma unroll
         for (int r = 0; r < NI; ++r)
             if (r < n - 1) {
-                st.S[(size_t)r * A.Np + p] = t.S[r];
-                st.C[(size_t)(2 * r) * A.Np + p] = (int8_t)t.C0[r];
-                st.C[(size_t)(2 * r + 1) * A.Np + p] = (int8_t)t.C1[r];
                 st.Pn[(size_t)r * A.Np + p] = (int8_t)pk2_get(ml.pn, r);
                 if constexpr (!PIPE) A.snap_S[A.sp][(size_t)r * A.Np + p] = t.S[r];
             }
@@ -1064,21 +892,11 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
         }
         st.w_post[p] = w_post;
         st.w_pilot[p] = w_pilot;
-        st.next_base[p] = next_base;
-        st.x_mark[p] = x_mark;
-        st.mark_limit[p] = mark_limit;
-        st.Ltree[p] = cx.Ltree;
-        A.rng_ctr[p] = cx.ctr;
-        A.ebuf[p] = cx.ebuf;
+        row_store_chain(A, st, p, next_base, x_mark, mark_limit, cx);
         if constexpr (PIPE) {
             A.rg_widx[(size_t)cur * A.Np + p] = widx;
             if (!do_extend) A.widx[p] = widx;              // the state goes back to the general kernels
-            {
-                // this launch runs up to PF_RING - 2 rows ahead of the counts: the writer itself checks that it has not overwritten a
-                // record that a pending count can still ask for (Ctrl::g_safe: the oldest generation those counts reach)
-                const unsigned kold = A.gstart[(size_t)(A.ctrl->g_safe % A.Gcap) * A.Np + p];
-                if (widx - kold > A.cap && !A.ctrl->err) A.ctrl->err = ERR_LOG_OVERFLOW;
-            }
+            pipe_log_ring_check(A, p, widx);
         } else {
             A.widx[p] = widx;
         }
@@ -1100,38 +918,18 @@ __device__ __forceinline__ void extend_mpr_body(const KA& A, long long s, int fu
         const long long q = (long long)blockIdx.x * 64 + lane;
         const bool live = q < A.Np;
         const double wq_post = sWpost[lane], wq_pilot = sWpilot[lane];
-        double sp = wave_tree_sum(wq_post);
-        double sq = wave_tree_sum(wq_pilot * wq_pilot);
-        double sc = wave_hs_scan(wq_pilot, lane);
-        double scp = wave_hs_scan(wq_post, lane);
-        double scm = wave_max_scan_d(sc, lane);
-        const long long chunk = blockIdx.x;
+        const RowScans rs = row_scans(wq_post, wq_pilot, lane);
         if constexpr (PIPE) {
-            const size_t ro = (size_t)cur * A.Np, co = (size_t)cur * A.nc;
-            if (live) { A.rg_scan1[ro + q] = sc; A.rg_scanp[ro + q] = scp; A.rg_scan1m[ro + q] = scm; }
-            if (q == A.Np - 1) A.ctrl->last1[cur] = sc;
-            if (lane == 63) {
-                A.rg_cpost[co + chunk] = sp; A.rg_csq[co + chunk] = sq; A.rg_cpil[co + chunk] = sc;
-                A.rg_cpp[co + chunk] = scp; A.rg_cmx1[co + chunk] = scm;
-            }
+            const long long chunk = blockIdx.x;
+            const size_t co = (size_t)cur * A.nc;
+            row_scans_store(A, cur, q, live, lane, rs);
             unsigned long long pend = __ballot(sPend[lane] != 0);
             if (lane == 0) {
                 A.rg_dpend[co + chunk] = __popcll(pend);
                 if (!PR.extend) A.chunk_dpend[chunk] = __popcll(pend);
             }
         } else {
-        if (live) { A.scan1[q] = sc; A.scanp2[A.sp][q] = scp; A.scan1m[q] = scm; }
-        if (lane == 63) {
-            A.chunk_post[chunk] = sp;
-            A.chunk_sq[chunk] = sq;
-            A.chunk_pil[chunk] = sc;
-            A.chunk_pp[chunk] = scp;
-            A.chunk_mx1[chunk] = scm;
-        }
-        if (biased) {
-            unsigned long long pend = __ballot(sPend[lane] != 0);
-            if (lane == 0) A.chunk_dpend[chunk] = __popcll(pend);
-        }
+            row_scans_store_general(A, q, live, lane, rs, biased, sPend[lane] != 0);
         }
     }
 }

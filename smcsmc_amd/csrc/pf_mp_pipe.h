@@ -5,8 +5,10 @@
 // Included by pf_mp.hip behind k_extend_mp (SmemMP, carve_mp, load_model_mp, make_mlane, mp_report, store_mp_state, piece_ref are that file's).
 //   prologue, k_resample's part, log-ring check, partials: the functions of pf_lds_pipe.h, shared with k_sweep_xl (64 lanes a workgroup here)
 //   the gather: tree, node populations and the migration list of the parent into this lane's LDS columns
-//   the row: k_extend_mp's statements (sample_point*, mp_genealogy_rest and the walk of pf_mp.h), from "the row" on; a fix to one belongs in
-//            both, tests/test_gpu_sweep_structured_lds.py holds them together through the oracle, bit for bit
+//   the row: the skeleton of k_extend_mp's row loop (the order of its steps, sample_point*, mp_genealogy_rest and the walk of pf_mp.h, the record
+//            of an update), from "the row" on; a change to that order belongs in both, tests/test_gpu_sweep_structured_lds.py holds them together
+//            through the oracle, bit for bit.  What the steps are made of (guide's factor, delayed-factor store, site likelihood, tree and chain
+//            stores) has one definition, in pf_row_parts.h
 // No -arg on this path (create_plan, run_path).  A look-ahead: the LOOK instance (k_sweep_xlmp<false, true>), on handles whose look-ahead was
 // loaded with PF_LA_ROW_PIPELINE_LDS (run_path: look_on_rows_lds); without the bit such a handle goes to the general kernels.
 #pragma once
@@ -46,7 +48,7 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
     const bool guided = BIASED && A.g_K > 0;
     const bool biased = BIASED && (A.n_bias > 0 || guided);          // a guide alone runs with one band of strength 1
     const LdsPipeReq R = lds_pipe_request(A, s, PR, p, active);
-    load_model_k(A, m);
+    load_model(A, m);
     load_model_mp(A, mm);
     if (threadIdx.x < PF_BIAS_MAX + 2) {
         sBH[threadIdx.x] = A.bias_H[threadIdx.x];
@@ -64,15 +66,11 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
     if (active) {
         const DState st = state_slot(A, cur);
         const DState from = state_slot(A, R.fs);
-        Lane ln = make_lane_k(A, m, p);
+        Lane ln = make_lane(A, m, p);
         MLane ml = make_mlane(A, mm);
         // the parent's tree, node populations and migration list into this lane's columns (its own when the row did not resample)
-        for (int r = 0; r < n - 1; ++r) {
-            LS(ln, r) = from.S[(size_t)r * A.Np + a];
-            LC(ln, r, 0) = from.C[(size_t)(2 * r) * A.Np + a];
-            LC(ln, r, 1) = from.C[(size_t)(2 * r + 1) * A.Np + a];
-            LPn(ml, r) = from.Pn[(size_t)r * A.Np + a];
-        }
+        lane_load_tree(ln, from, (size_t)A.Np, a, n);
+        for (int r = 0; r < n - 1; ++r) LPn(ml, r) = from.Pn[(size_t)r * A.Np + a];
         ml.nm = from.nm[a];
         for (int q = 0; q < ml.nm; ++q) {
             LMt(ml, q) = from.Mt[(size_t)q * A.Np + a];
@@ -96,12 +94,7 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
         if (biased) {
             ds.count = from.dcount[a]; ds.total = from.total_delayed[a];
             // the copy constructor copies the pending factors (particle.cpp:122-123); the ring moves them every row
-            for (int k = 0; k < ds.count; ++k) {
-                st.dpos[(size_t)k * A.Np + p] = from.dpos[(size_t)k * A.Np + a];
-                st.dfac[(size_t)k * A.Np + p] = from.dfac[(size_t)k * A.Np + a];
-                st.ddelta[(size_t)k * A.Np + p] = from.ddelta[(size_t)k * A.Np + a];
-                st.dk[(size_t)k * A.Np + p] = from.dk[(size_t)k * A.Np + a];
-            }
+            row_copy_pending(st, from, (size_t)A.Np, p, a, ds.count);
         }
         int ridx = guided ? from.ridx[a] : 0;
         PLog pl;
@@ -117,11 +110,7 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
         const double seg_end = do_extend ? R.sg_start + R.sg_len : 0.0;
         const double extend_to = seg_end < A.L ? seg_end : A.L;
         const int limit = R.sg_limit;
-        int missing = 0;
-        for (int i = 0; i < n && do_extend; ++i) missing += data[i] == -1;
-        int leaf_status = 0;
-        if (missing == 0) leaf_status = 1;
-        if (missing == n) leaf_status = -1;
+        const int leaf_status = lane_leaf_status(data, n, do_extend);
 
         double updated_to = completing ? pos_prev : c->cur_pos;
         if (!do_extend) updated_to = extend_to;             // completion only: the loop below does not run
@@ -138,11 +127,7 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
             w_post *= f;
             w_pilot *= f;
             if (guided) {
-                // importance_weight_over_segment (particle.cpp:1138-1181)
-                const double dist = new_to - updated_to;
-                const double target_rate = dist * A.rho * ln.Ltree;
-                const double sampled_rate = dist * A.g_rho[ridx] * ln.Ltree;
-                const double iws = fastexp(sampled_rate - target_rate);
+                const double iws = row_guide_stretch(new_to - updated_to, A.rho, A.g_rho[ridx], ln.Ltree);
                 w_post *= iws;
                 w_pilot *= iws;
             }
@@ -181,15 +166,8 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
                 if (leaf_status == 0) B = tracked_len_lane(ln, data, tmp0);
                 if (leaf_status == 1) B = ln.Ltree;
                 if (biased) {
-                    // particle.cpp:866-891: immediate vs delayed application of the importance weight
-                    const int nbands = A.n_bias + 1;
                     const double delay_height = (A.delay_type & 3) == 0 ? h : ((A.delay_type & 3) == 2 ? tfirst : tc);
-                    int idx = 0;
-                    while (idx + 1 < nbands + 1 && sBH[idx + 1] < delay_height) ++idx;
-                    if (idx >= nbands) idx = nbands - 1;
-                    if (sBS[idx] == 1.0 && !(A.delay_type & 4)) { w_post *= rbiw; w_pilot *= rbiw; iw /= rbiw; }   // bit 2: every factor delayed (pf_model.delay_type)
-                    const double delay = A.app_delays[epoch_of(ln, delay_height)];
-                    d_adjust_with_delay(ds, w_post, w_pilot, iw, delay, updated_to);
+                    row_delayed_factor(ds, sBH, sBS, A.n_bias + 1, A.delay_type, delay_height, iw, rbiw, A.app_delays[epoch_of(ln, delay_height)], updated_to, w_post, w_pilot);
                 }
                 next_base = sample_next_base_guided(ln, updated_to, A.g_K, A.g_pos, A.g_rho, ridx);
                 x_mark = updated_to;
@@ -197,61 +175,10 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
             }
         }
         mp_report(A, ml);
-        if (biased) {
-            // apply the factors that fell due during this extension (particle.cpp:910-916)
-            for (;;) {
-                if (ds.count == 0 || !do_extend) break;
-                double pm = ds.pos[0];
-                for (int i = 1; i < ds.count; ++i) { double pi = ds.pos[(size_t)i * ds.Np]; if (pi < pm) pm = pi; }
-                if (!(pm < extend_to)) break;
-                d_apply_earliest(ds, w_pilot);
-            }
-            st.dcount[p] = ds.count;
-            st.total_delayed[p] = ds.total;
-            if (guided) st.ridx[p] = ridx;
-            has_pending = ds.count > 0;
-        }
+        if (biased) has_pending = row_apply_due(ds, st, p, extend_to, do_extend, guided, ridx, w_pilot);
 
         if (do_extend && R.sg_state == 0) {
-            // update_weight_at_site: marginalise over phasings of unphased hets (pc.cpp:138-224)
-            const bool dephase = A.flags & 2;
-            const bool anc = A.flags & 1;
-            unsigned one_mask = 0, zero_mask = 0, het_pairs = 0;
-            int ncfg = 1;
-            for (int i = 0; i < n; ++i) {
-                if (data[i] == 1) one_mask |= 1u << i;
-                if (data[i] == 0) zero_mask |= 1u << i;
-            }
-            for (int i = 0; i + 1 < n; i += 2) {
-                bool het = (data[i] == 2) || (dephase && data[i] + data[i + 1] == 1);
-                if (het) {
-                    ncfg *= 2;
-                    het_pairs |= 1u << i;
-                    one_mask &= ~(3u << i); zero_mask &= ~(3u << i);
-                    zero_mask |= 1u << i;
-                    one_mask |= 1u << (i + 1);
-                }
-            }
-            double norm = 1.0 / (double)ncfg;
-            double lik = 0;
-            for (;;) {
-                lik += site_lik_lane(ln, one_mask, zero_mask, anc, tmp0, tmp1);
-                if (ncfg == 1) break;
-                bool more = false;
-                for (int i = 0; i + 1 < n; i += 2) {
-                    if (!((het_pairs >> i) & 1)) continue;
-                    if ((zero_mask >> i) & 1) {
-                        zero_mask &= ~(1u << i); one_mask |= 1u << i;
-                        one_mask &= ~(1u << (i + 1)); zero_mask |= 1u << (i + 1);
-                        more = true;
-                        break;
-                    }
-                    one_mask &= ~(1u << i); zero_mask |= 1u << i;
-                    zero_mask &= ~(1u << (i + 1)); one_mask |= 1u << (i + 1);
-                }
-                if (!more) break;
-            }
-            lik *= norm;
+            const double lik = lane_site_weight(ln, data, n, A.flags & 2, A.flags & 1, tmp0, tmp1);
             w_post *= lik;
             w_pilot *= lik;
         }
@@ -270,20 +197,11 @@ __device__ __forceinline__ void extend_mp_pipe_body(const KA& A, long long s, co
             st.lookahead[p] = la_w;          // (the slot the general kernels and the step API read when the call ends here)
         }
 
-        for (int r = 0; r < n - 1; ++r) {
-            st.S[(size_t)r * A.Np + p] = LS(ln, r);
-            st.C[(size_t)(2 * r) * A.Np + p] = LC(ln, r, 0);
-            st.C[(size_t)(2 * r + 1) * A.Np + p] = LC(ln, r, 1);
-        }
+        lane_store_tree(ln, st, (size_t)A.Np, p, n);
         store_mp_state(A, st, ln, ml, p);
         st.w_post[p] = w_post;
         st.w_pilot[p] = w_pilot;
-        st.next_base[p] = next_base;
-        st.x_mark[p] = x_mark;
-        st.mark_limit[p] = mark_limit;
-        st.Ltree[p] = ln.Ltree;
-        A.rng_ctr[p] = ln.ctr;
-        A.ebuf[p] = ln.ebuf;
+        lane_store_chain(A, st, p, next_base, x_mark, mark_limit, ln);
         A.rg_widx[(size_t)cur * A.Np + p] = widx;
         if (!do_extend) A.widx[p] = widx;              // the state goes back to the general kernels
         A.pidx[p] = pl.idx;

@@ -13,6 +13,7 @@
 #include "pf_device.h"
 #include "pf_types.h"
 #include "pf_lane.h"
+#include "pf_row_parts.h"
 #include "pf_lds_body.h"
 #include "pf_wide_host.h"
 
